@@ -270,17 +270,39 @@ __global__ __launch_bounds__(WM* WN * 64) void conv_igemm_kernel(ConvArgs a) {
   }
 }
 
-template <typename T, int WM, int WN, int NT>
-int launch_conv(const ConvArgs& a, hipStream_t s) {
-  constexpr int BM = WM * 64, BN = WN * NT * 16;
-  ConvArgs k = a;
-  k.MT = (a.M + BM - 1) / BM;
-  k.NTILES = (a.Nst + BN - 1) / BN;
-  const int nvirt = ((k.MT + 7) / 8) * 8 * k.NTILES;
+// Tile and persistent grid of the generic kernel for a descriptor: the launch below and the query gan_conv_igemm_variant both read this
+struct IgemmPlan { int wm, wn, nt, bm, bn, mt, ntiles, nvirt, grid; };
+
+int igemm_plan(const gan_conv_desc* d, IgemmPlan* p) {
+  const int64_t M = (int64_t)d->B * d->Ho * d->Wo;
+  // tile choice by the packed weight height (the packer pads Nw to the tile the launcher will use)
+  if (d->Nw % 128 == 0) { p->wm = 2; p->wn = 2; p->nt = 4; }
+  else if (d->Nw % 64 == 0) { p->wm = 2; p->wn = 2; p->nt = 2; }
+  else if (d->Nw == 16) {
+    // few rows and a long reduction (the discriminator's 512 -> 1 4x4 convolution: 113 tiles of 256 rows x 128 K-steps -- 85 us for 31 MB of input on
+    // less than half of the CUs): 64-row tiles, one wave per block, four times the blocks
+    if ((M + 255) / 256 < 256) { p->wm = 1; p->wn = 1; p->nt = 1; }
+    else { p->wm = 4; p->wn = 1; p->nt = 1; }
+  } else {
+    return gan_set_error(-1, "conv: Nw=%d must be 16 or a multiple of 64", d->Nw);
+  }
+  p->bm = p->wm * 64; p->bn = p->wn * p->nt * 16;
+  p->mt = (int)((M + p->bm - 1) / p->bm);
+  p->ntiles = (d->Nst + p->bn - 1) / p->bn;
+  p->nvirt = ((p->mt + 7) / 8) * 8 * p->ntiles;
   // persistent: as many blocks as the chip holds at once (LDS: two 2 x 32 KB blocks per CU on 256 CUs), a multiple of 8 (XCD mapping)
   static const int resident = [] { const char* e = getenv("GAN_IGEMM_BLOCKS"); const int v = e ? atoi(e) : 512; return v >= 8 ? (v / 8) * 8 : 512; }();
-  const int grid = nvirt < resident ? nvirt : resident;
-  hipLaunchKernelGGL((conv_igemm_kernel<T, WM, WN, NT>), dim3(grid), dim3(WM * WN * 64), 0, s, k);
+  p->grid = p->nvirt < resident ? p->nvirt : resident;
+  return 0;
+}
+
+template <typename T, int WM, int WN, int NT>
+int launch_conv(const ConvArgs& a, const IgemmPlan& p, hipStream_t s) {
+  GAN_CHECK(p.wm == WM && p.wn == WN && p.nt == NT, "conv: plan %dx%dx%d launched as %dx%dx%d", p.wm, p.wn, p.nt, WM, WN, NT);
+  ConvArgs k = a;
+  k.MT = p.mt;
+  k.NTILES = p.ntiles;
+  hipLaunchKernelGGL((conv_igemm_kernel<T, WM, WN, NT>), dim3(p.grid), dim3(WM * WN * 64), 0, s, k);
   GAN_LAUNCH_CHECK();
   return 0;
 }
@@ -332,16 +354,24 @@ extern "C" int gan_conv_igemm(const gan_conv_desc* d, void* stream) {
   { const char* e = getenv("GAN_CONV_DEBUG"); a.dbg = e ? atoi(e) : 0; }
   a.mask_Hp = d->mask_Hp; a.mask_Wp = d->mask_Wp; a.mask_y0 = d->mask_y0; a.mask_x0 = d->mask_x0;
   hipStream_t s = (hipStream_t)stream;
-  // tile choice by the packed weight height (the packer pads Nw to the tile the launcher will use)
-  if (d->Nw % 128 == 0) {
-    GAN_DISPATCH_DTYPE(d->dtype, return launch_conv<T, 2, 2, 4>(a, s);)
-  } else if (d->Nw % 64 == 0) {
-    GAN_DISPATCH_DTYPE(d->dtype, return launch_conv<T, 2, 2, 2>(a, s);)
-  } else {
-    GAN_CHECK(d->Nw == 16, "conv: Nw=%d must be 16 or a multiple of 64", d->Nw);
-    // few rows and a long reduction (the discriminator's 512 -> 1 4x4 convolution: 113 tiles of 256 rows x 128 K-steps -- 85 us for 31 MB of input on
-    // less than half of the CUs): 64-row tiles, one wave per block, four times the blocks
-    if ((M + 255) / 256 < 256) { GAN_DISPATCH_DTYPE(d->dtype, return launch_conv<T, 1, 1, 1>(a, s);) }
-    GAN_DISPATCH_DTYPE(d->dtype, return launch_conv<T, 4, 1, 1>(a, s);)
-  }
+  IgemmPlan p;
+  if (igemm_plan(d, &p) != 0) return -1;
+  if (p.nt == 4) { GAN_DISPATCH_DTYPE(d->dtype, return launch_conv<T, 2, 2, 4>(a, p, s);) }
+  if (p.nt == 2) { GAN_DISPATCH_DTYPE(d->dtype, return launch_conv<T, 2, 2, 2>(a, p, s);) }
+  if (p.wm == 1) { GAN_DISPATCH_DTYPE(d->dtype, return launch_conv<T, 1, 1, 1>(a, p, s);) }
+  GAN_DISPATCH_DTYPE(d->dtype, return launch_conv<T, 4, 1, 1>(a, p, s);)
+}
+
+int gan_conv_patch_plan(const gan_conv_desc* d, int32_t* info);
+int gan_conv_win7_plan(const gan_conv_desc* d, int32_t* info);
+
+extern "C" int gan_conv_igemm_variant(const gan_conv_desc* d, int32_t* info) {
+  GAN_CHECK(d && info, "conv_igemm_variant: null argument");
+  if (d->w_layout == 1) return gan_conv_patch_plan(d, info);
+  if (d->w_layout == 2) return gan_conv_win7_plan(d, info);
+  GAN_CHECK(d->w_layout == 0, "conv_igemm_variant: bad w_layout %d", d->w_layout);
+  IgemmPlan p;
+  if (igemm_plan(d, &p) != 0) return -1;
+  info[0] = p.bm; info[1] = p.bn; info[2] = p.nvirt; info[3] = p.grid;
+  return 0;
 }

@@ -942,11 +942,23 @@ static int patch_variant(const gan_conv_desc* d) {
 }
 extern "C" int gan_conv_patch_variant(const gan_conv_desc* d) { return gan_conv_patch_ok(d) ? patch_variant(d) : 0; }
 
+// persistent grid of a launch with `tiles` tiles: one block per CU; a block walks tiles b, b + grid, ... (the next tile's first slab in flight)
+static int patch_grid(int tiles) { constexpr int ncu = 256; return tiles < ncu ? tiles : ncu; }
+
+// gan_conv_igemm_variant for w_layout 1: {tile rows, tile columns, tiles, grid} of the launch gan_conv_patch_launch makes
+int gan_conv_patch_plan(const gan_conv_desc* d, int32_t* info) {
+  GAN_CHECK(gan_conv_patch_ok(d), "conv_igemm_variant: w_layout 1 but the descriptor does not qualify for the range-patch kernel");
+  const int variant = patch_variant(d);
+  const int BM = variant & 0xfff, BN = (variant >> 12) & 0xfff;
+  const int tiles = d->B * ((d->Ho * d->Wo + BM - 1) / BM) * ((d->Nst + BN - 1) / BN);
+  info[0] = BM; info[1] = BN; info[2] = tiles; info[3] = patch_grid(tiles);
+  return 0;
+}
+
 int gan_conv_patch_launch(const gan_conv_desc* d, hipStream_t s) {
   if (!gan_conv_patch_ok(d)) return gan_set_error(-1, "conv: w_layout=1 (fragment-major weights) but the descriptor does not qualify for the range-patch kernel");
   PatchArgs a;
   const int M_img = d->Ho * d->Wo;
-  const int ncu = 256;
   const int variant = patch_variant(d);
   const int BM = variant & 0xfff, BN = (variant >> 12) & 0xfff;
   a.in = (const char*)d->in; a.w = (const char*)d->w; a.bias = d->bias; a.out = (char*)d->out; a.mask = (const char*)d->mask; a.tapoff = d->tapoff;
@@ -994,7 +1006,7 @@ int gan_conv_patch_launch(const gan_conv_desc* d, hipStream_t s) {
     return v;
   }();
   a.stamps = (stamps_sel[0] == 0 || (stamps_sel[0] == BM && stamps_sel[1] == BN && stamps_sel[2] == d->B && stamps_sel[3] == (a.smode != 0) && stamps_sel[4] == d->ntaps)) ? stamps_env : nullptr;
-  const int grid = a.tiles < ncu ? a.tiles : ncu;
+  const int grid = patch_grid(a.tiles);
   // the dynamic-LDS limit is a per-device function attribute: one bit per device, set on that device's first launch
   static std::atomic<uint64_t> attr_devs{0};
   int dev = 0;

@@ -515,16 +515,23 @@ __global__ __launch_bounds__(256) void wgrad_reduce_coop_kernel(const float* __r
   }
 }
 
+// lanes per output quad of gan_wgrad_reduce: enough threads to cover the load latency (~64 k), at most one lane per 4 slabs;
+// GAN_WGRAD_REDUCE_COOP (A/B switch) = 0 | 1: one lane, 2 .. 32: forced
+extern "C" int gan_wgrad_reduce_lanes(int nsplit, int N_real, int ntaps, int Cx) {
+  const int64_t total = (int64_t)N_real * ntaps * (Cx / 4);
+  static const int coop_env = [] { const char* e = getenv("GAN_WGRAD_REDUCE_COOP"); return e ? atoi(e) : -1; }();
+  int G = 1;
+  while (G < 32 && total * G < 65536 && G * 8 <= nsplit) G *= 2;
+  if (coop_env >= 0) G = coop_env <= 1 ? 1 : coop_env >= 32 ? 32 : coop_env >= 16 ? 16 : coop_env >= 8 ? 8 : coop_env >= 4 ? 4 : 2;
+  return G;
+}
+
 extern "C" int gan_wgrad_reduce(const float* part, int nsplit, int N, int ntaps, int Cx, int N_real, int C_real, int swap, int I2,
                                 int KK, const int32_t* khw, float* grad, int accumulate, void* stream) {
   GAN_CHECK(part && khw && grad && nsplit > 0 && N_real <= N && C_real <= Cx, "wgrad_reduce: bad arguments");
   GAN_CHECK(Cx % 4 == 0 && ((uintptr_t)part % 16) == 0, "wgrad_reduce: Cx must be a multiple of 4 and part 16-byte aligned");
   const int64_t total = (int64_t)N_real * ntaps * (Cx / 4);
-  // lanes per output quad: enough threads to cover the load latency (~64 k), at most one lane per 4 slabs
-  static const int coop_env = [] { const char* e = getenv("GAN_WGRAD_REDUCE_COOP"); return e ? atoi(e) : -1; }();    // A/B: 0 = off, else forced G
-  int G = 1;
-  while (G < 32 && total * G < 65536 && G * 8 <= nsplit) G *= 2;
-  if (coop_env >= 0) G = coop_env <= 1 ? 1 : coop_env >= 32 ? 32 : coop_env >= 16 ? 16 : coop_env >= 8 ? 8 : coop_env >= 4 ? 4 : 2;
+  const int G = gan_wgrad_reduce_lanes(nsplit, N_real, ntaps, Cx);
   const int64_t thr = total * G;
   const int grid = (int)((thr + 255) / 256 < 8192 ? (thr + 255) / 256 : 8192);
 #define GAN_REDUCE_COOP(GG) hipLaunchKernelGGL(wgrad_reduce_coop_kernel<GG>, dim3(grid), dim3(256), 0, (hipStream_t)stream, part, nsplit, N, ntaps, Cx, \

@@ -252,6 +252,18 @@ int gan_conv_win7_stats_parts(const gan_conv_desc* d) {
   return ((d->Wo + TS - 1) / TS) * ((d->Ho + TS - 1) / TS);
 }
 
+// 16x16-pixel tiles of a window launch: one block per tile (the forward kernels do not walk tiles)
+static int64_t win7_tiles(const gan_conv_desc* d) { return (int64_t)d->B * ((d->Wo + TS - 1) / TS) * ((d->Ho + TS - 1) / TS); }
+
+// gan_conv_igemm_variant for w_layout 2: {tile pixels, tile columns, tiles, grid} of the launch gan_conv_win7_launch makes
+int gan_conv_win7_plan(const gan_conv_desc* d, int32_t* info) {
+  GAN_CHECK(gan_conv_win7_ok(d), "conv_igemm_variant: w_layout 2 on a descriptor the 7x7 window kernel does not cover");
+  const int64_t tiles = win7_tiles(d);
+  GAN_CHECK(tiles < (1ll << 31), "conv(7x7 window): too many tiles");
+  info[0] = TS * TS; info[1] = d->Nst; info[2] = (int)tiles; info[3] = (int)tiles;
+  return 0;
+}
+
 int gan_conv_win7_launch(const gan_conv_desc* d, hipStream_t s) {
   GAN_CHECK(gan_conv_win7_ok(d), "conv: w_layout 2 set on a descriptor the 7x7 window kernel does not cover");
   // every tap of every real output pixel must lie inside the allocation (the planner's halos guarantee it; checked here)
@@ -263,7 +275,7 @@ int gan_conv_win7_launch(const gan_conv_desc* d, hipStream_t s) {
   a.in_Hp = d->in_Hp; a.in_Wp = d->in_Wp; a.in_y0 = d->in_y0; a.in_x0 = d->in_x0; a.ty0 = d->win_ty0; a.tx0 = d->win_tx0;
   a.out_Hp = d->out_Hp; a.out_Wp = d->out_Wp; a.out_y0 = d->out_y0; a.out_x0 = d->out_x0;
   a.act = d->act; a.stats = d->stats;
-  const int64_t blocks = (int64_t)d->B * a.tiles_x * a.tiles_y;
+  const int64_t blocks = win7_tiles(d);
   GAN_CHECK(blocks < (1ll << 31), "conv(7x7 window): too many tiles");
   static bool attr_set = false;
   if (!attr_set) {

@@ -313,6 +313,17 @@ class HipOps:
         return {} if v == 0 else {"rows": v & 0xfff, "cols": (v >> 12) & 0xfff, "slices": (v >> 24) & 0xf, "fp8": bool((v >> 28) & 1), "static9": bool((v >> 29) & 1),
                                       "static_taps": 9 if (v >> 29) & 1 else (0, 4, 2, 16)[(v >> 30) & 3]}
 
+    def conv_igemm_variant(self, c: ConvCall) -> dict:
+        """Tiling of the launch gan_conv_igemm makes for this planned call (generic, range-patch or 7x7 window kernel, by its weight
+        layout): rows and cols per tile, tiles, and the blocks launched (grid)."""
+        info = (C.c_int32 * 4)()
+        _lib.check(self.lib.gan_conv_igemm_variant(C.byref(self._conv_desc(c)), info), "gan_conv_igemm_variant")
+        return {"rows": info[0], "cols": info[1], "tiles": info[2], "grid": info[3]}
+
+    def wgrad_reduce_lanes(self, nsplit: int, N_real: int, ntaps: int, Cx: int) -> int:
+        """Lanes G that gan_wgrad_reduce lets share one output quad for these arguments."""
+        return int(self.lib.gan_wgrad_reduce_lanes(nsplit, N_real, ntaps, Cx))
+
     def conv_win7_ok(self, c: ConvCall, ty0: int, tx0: int) -> bool:
         """True if the 7x7 window kernel takes this call with its 49 row-major taps starting at (ty0, tx0)."""
         d = self._conv_desc(c)

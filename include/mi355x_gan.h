@@ -133,6 +133,12 @@ int gan_conv_patch_tile_cols(const gan_conv_desc* d);
  * schedules << 30 (1: 4 taps, 2: 2 taps, 3: 16 taps -- the sub-pixel phases and the discriminator's 4x4 windows).  The value uses bit 31:
  * read it as unsigned.  Pure host-side query: tests assert with it that a case really reaches the kernel it is meant to cover. */
 int gan_conv_patch_variant(const gan_conv_desc* d);
+/* the tiling of the launch gan_conv_igemm makes for the descriptor, by its w_layout: info[0] = pixels per tile, info[1] = output channels
+ * per tile, info[2] = tiles (generic kernel: virtual tiles, the M tiles rounded up to a multiple of 8 times the N tiles), info[3] = blocks
+ * launched.  A block of the generic kernel (w_layout 0, grid <= 512) and of the range-patch kernel (1, grid <= 256) walks tiles
+ * b, b + grid, ...; the 7x7 window kernel (2) launches one block per 16x16 tile.  Returns 0, or non-zero (gan_last_error) if the
+ * descriptor does not qualify for its w_layout.  Pure host-side query: the launch reads the same plan. */
+int gan_conv_igemm_variant(const gan_conv_desc* d, int32_t* info);
 /* 1 if the descriptor qualifies for a 7x7 window kernel (bf16, stride 1, 49 row-major taps located by win_ty0/win_tx0, act none or
  * tanh, no mask / stats): Cin = 64, Nw = 16, Nst = out_C = 8 (the 64 -> 3 channel layers) or Cin = 8, Nw = Nst = out_C = 64 with the
  * tap list padded to >= 52 (the 3 -> 64 channel layers) */
@@ -148,6 +154,8 @@ int gan_wgrad_patch_splits(const gan_wgrad_desc* d);
 /* slabs the 7x7 window weight-gradient kernels write (0: the descriptor does not qualify: bf16, 49 row-major taps, stride 1, and
  * Cx = 64, N = g_C = 8 -- the generator's 64 -> 3 channel output convolution -- or Cx = 8, N = g_C = 64 -- its 3 -> 64 first one) */
 int gan_wgrad_win7_splits(const gan_wgrad_desc* d);
+/* lanes G (1, 2 ... 32) gan_wgrad_reduce lets share one output quad for these arguments (GAN_WGRAD_REDUCE_COOP forces one); pure query */
+int gan_wgrad_reduce_lanes(int nsplit, int N_real, int ntaps, int Cx);
 int gan_wgrad_reduce(const float* part, int nsplit, int N, int ntaps, int Cx, int N_real, int C_real, int swap, int I2,
                      int KK, const int32_t* khw, float* grad, int accumulate, void* stream);
 /* dst[n][t][c] = src[(a*I2 + b)*KK + khw[t]] (0 where n>=N_real, c>=C_real or khw[t]<0); dst dtype GAN_*.

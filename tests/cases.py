@@ -1,5 +1,7 @@
 """Shared test bodies, parametrised over the op backend: EmuOps on CPU (host-logic tests) or HipOps on a MI355X
 (parity tests proper, through the C ABI)."""
+import math
+
 import numpy as np
 import torch
 import torch.nn.functional as F
@@ -49,6 +51,90 @@ GEOMS = [  # cin, cout, k, s, p, transposed, H, reflect
 ]
 
 
+# ---------------------------------------------------------------------------------------------- float64 references and their error bound
+# Every output element of a convolution kernel is checked against a float64 reference computed from the SAME (bf16-rounded) operands:
+#     |got - ref| <= u_out * |ref| + BOUND_C * sqrt(K) * 2^-24 * A
+# with A the same operation on |operands| and K the reduction length.  Products of bf16 operands are exact in fp32; each of the K fp32
+# additions rounds by at most 2^-24 times a partial sum, and every partial sum is at most A whatever the summation order (sequential,
+# blocked, split-K slabs, reduction trees).  Independent zero-mean rounding errors of that size sum to a standard deviation of at most
+# sqrt(K / 3) * 2^-24 * A; BOUND_C = 4 puts the bound ~7 such deviations out (no false alarm over 1e9 elements), while a real indexing
+# error -- a dropped tap, a missed image, a tile written twice -- is of the order A / sqrt(K), far above it for every K here.
+# u_out covers the rounding of the stored result: 2^-8 for bf16 (its unit roundoff: 8 significant bits; measured worst 0.996 of the
+# bound on the 16-term input gradients, where nothing else contributes), 2^-24 for an fp32 output, 0 for the fp32
+# weight gradient (its slabs are summed in fp32 and stored as they are: covered by the K term).
+BOUND_C = 4.0
+U_BF16, U_F32 = 2.0 ** -8, 2.0 ** -24
+
+
+def derived_bound(ref: torch.Tensor, A: torch.Tensor, K: int, u_out: float) -> torch.Tensor:
+    return u_out * ref.abs() + BOUND_C * math.sqrt(K) * 2.0 ** -24 * A
+
+
+def bound_ratio(got: torch.Tensor, ref: torch.Tensor, A: torch.Tensor, K: int, u_out: float) -> float:
+    """max |got - ref| / bound over all elements (<= 1: within the derived bound).  A zero bound admits only an exact match."""
+    got, ref, A = got.double(), ref.double().to(got.device), A.double().to(got.device)
+    return float(((got - ref).abs() / (derived_bound(ref, A, K, u_out) + 1e-300)).max())
+
+
+def assert_within_bound(got, ref, A, K, u_out, what=""):
+    r = bound_ratio(got, ref, A, K, u_out)
+    assert r <= 1.0, f"{what}: max |got - ref| / bound = {r:.3g} (K={K}, u_out={u_out:.3g})"
+    return r
+
+
+def _c_fwd(xp, w, s):
+    """Plain convolution of an explicitly padded input: unfold + matmul (no library convolution path)."""
+    co, k = w.shape[0], w.shape[2]
+    Ho, Wo = (xp.shape[2] - k) // s + 1, (xp.shape[3] - k) // s + 1
+    return torch.matmul(w.reshape(co, -1), F.unfold(xp, k, stride=s)).view(xp.shape[0], co, Ho, Wo)
+
+
+def _c_bwd_in(dy, w, s, Hp, Wp):
+    """Gradient of _c_fwd with respect to its (padded) input of size Hp x Wp."""
+    co, k = w.shape[0], w.shape[2]
+    return F.fold(torch.matmul(w.reshape(co, -1).t(), dy.flatten(2)), (Hp, Wp), k, stride=s)
+
+
+def _c_bwd_w(xp, dy, k, s):
+    """Gradient of _c_fwd with respect to its weight, summed over the batch."""
+    co, ci = dy.shape[1], xp.shape[1]
+    return torch.matmul(dy.flatten(2), F.unfold(xp, k, stride=s).transpose(1, 2)).sum(0).view(co, ci, k, k)
+
+
+def conv_ref64(op, k, s, p, tr, reflect, w, x=None, dy=None, x_hw=None, padded_domain=False):
+    """float64 reference of one direction of an nn.Conv2d (zero or reflect padding p, stride s) or of the k3 s2 p1 op1 nn.ConvTranspose2d
+    (weight in the layer's own layout, no bias): op 'fwd' (x), 'dgrad' (dy; x_hw = input size; padded_domain: the gradient on the padded
+    input domain, before the reflection fold) or 'wgrad' (x, dy).  Returns (ref, A, K): A is the same operation on |operands|."""
+    mode = "reflect" if reflect else "constant"
+
+    def run(wv, xv, dyv):
+        if tr:      # the transposed layer is the input gradient of the k3 s2 p1 convolution whose weight is w (out = w.shape[0])
+            if op == "fwd":
+                H, W = xv.shape[2], xv.shape[3]
+                return _c_bwd_in(xv, wv, 2, 2 * H + 2, 2 * W + 2)[:, :, 1:2 * H + 1, 1:2 * W + 1]
+            if op == "dgrad":
+                return _c_fwd(F.pad(dyv, (1, 1, 1, 1)), wv, 2)
+            return _c_bwd_w(F.pad(dyv, (1, 1, 1, 1)), xv, 3, 2)
+        if op == "fwd":
+            return _c_fwd(F.pad(xv, (p, p, p, p), mode=mode), wv, s)
+        if op == "dgrad":
+            H, W = x_hw
+            full = _c_bwd_in(dyv, wv, s, H + 2 * p, W + 2 * p)
+            return full if padded_domain else full[:, :, p:p + H, p:p + W]
+        return _c_bwd_w(F.pad(xv, (p, p, p, p), mode=mode), dyv, k, s)
+    a = lambda t: None if t is None else t.abs()
+    ref, A = run(w, x, dy), run(w.abs(), a(x), a(dy))
+    cin, cout = (w.shape[1], w.shape[0]) if not tr else (w.shape[0], w.shape[1])
+    if op == "fwd":
+        K = k * k * cin
+    elif op == "dgrad":
+        K = k * k * cout
+    else:
+        src = x if tr else dy
+        K = src.shape[0] * src.shape[2] * src.shape[3]
+    return ref, A, K
+
+
 def run_conv_geometry(ctx, geom, dtype, B=2):
     cin, cout, k, s, p, tr, H, reflect = geom
     torch.manual_seed(0)
@@ -79,6 +165,10 @@ def run_conv_geometry(ctx, geom, dtype, B=2):
         op()
     tol = dict(rtol=1e-4, atol=1e-4) if dtype == F32 else dict(rtol=3e-2, atol=6e-2)
     np.testing.assert_allclose(from_view(y, cout).numpy(), y_ref.detach().numpy(), **tol)
+    u_out = U_F32 if dtype == F32 else U_BF16
+    w64, x64 = w_ref.double(), x.double()
+    r64, A, K = conv_ref64("fwd", k, s, p, tr, reflect, w64, x=x64)
+    assert_within_bound(from_view(y, cout), r64 + b.cpu().double().view(1, -1, 1, 1), A + b.cpu().double().abs().view(1, -1, 1, 1), K, u_out, "forward")
     # backward
     gy = torch.randn_like(y_ref)
     if dtype == BF16:
@@ -108,6 +198,14 @@ def run_conv_geometry(ctx, geom, dtype, B=2):
     out = ctx.view(B, H, H, cpad(cin), 0)
     ctx.ops.fold_add(None, dx, fold, out)()
     np.testing.assert_allclose(from_view(out, cin).numpy(), xr.grad.numpy(), **tol)
+    gy64 = gy.double()
+    if fold:      # the kernel's result is the gradient on the reflect-padded domain (fold_add above is a separate pass): check it there
+        r64, A, K = conv_ref64("dgrad", k, s, p, tr, reflect, w64, dy=gy64, x_hw=(H, H), padded_domain=True)
+        got = dx.padded().float()[..., :cin].permute(0, 3, 1, 2).cpu()
+    else:
+        r64, A, K = conv_ref64("dgrad", k, s, p, tr, reflect, w64, dy=gy64, x_hw=(H, H))
+        got = from_view(dx, cin)
+    assert_within_bound(got, r64, A, K, u_out, "input gradient")
     for op in layer.wgrad(xin, dyv, accumulate=False):
         op()
     wtol = dict(rtol=1e-3, atol=1e-3) if dtype == F32 else dict(rtol=3e-2, atol=3e-1)
@@ -115,6 +213,9 @@ def run_conv_geometry(ctx, geom, dtype, B=2):
         torch.cuda.synchronize()
     np.testing.assert_allclose(gw.cpu().numpy(), wr.grad.numpy(), **wtol)
     np.testing.assert_allclose(gb.cpu().numpy(), br.grad.numpy(), **wtol)
+    r64, A, K = conv_ref64("wgrad", k, s, p, tr, reflect, w64, x=x64, dy=gy64)
+    assert_within_bound(gw.cpu(), r64, A, K, 0.0, "weight gradient")
+    assert_within_bound(gb.cpu(), gy64.sum((0, 2, 3)), gy64.abs().sum((0, 2, 3)), gy64[:, 0].numel(), 0.0, "bias gradient")
 
 
 

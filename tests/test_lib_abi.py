@@ -25,6 +25,17 @@ def test_errors_are_reported_not_swallowed():
     assert rc != 0 and b"null" in lib.gan_last_error()
 
 
+def test_dispatch_queries_are_pure_and_bound():
+    """gan_wgrad_reduce_lanes and gan_conv_igemm_variant answer on the host (the launches read the same plans)."""
+    import ctypes
+    lib = _lib.load()
+    assert lib.gan_wgrad_reduce_lanes(1, 256, 9, 256) == 1            # one slab: nothing to share
+    assert lib.gan_wgrad_reduce_lanes(256, 3, 49, 64) == 32           # 7x7 64 -> 3 layer: few outputs, 256 slabs
+    assert lib.gan_wgrad_reduce_lanes(16, 3, 49, 64) == 4             # at most one lane per 4 slabs
+    info = (ctypes.c_int32 * 4)()
+    assert lib.gan_conv_igemm_variant(None, info) != 0 and b"null" in lib.gan_last_error()
+
+
 def test_missing_library_fails_loudly(tmp_path):
     import importlib
     import pytest
