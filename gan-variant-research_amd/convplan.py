@@ -8,7 +8,6 @@ discriminator_patchgan.py:27-51; Basic_GAN/src/models.py:12-103) lives here; the
 """
 from __future__ import annotations
 
-import os
 
 from typing import List, Optional, Tuple
 
@@ -237,7 +236,7 @@ class ConvLayer:
             call = pk.finalize(ConvCall(x.B, ho, wo, pk.cred, pk.ntaps, pk.nw, min(pk.nw, y.C), x, x.halo - p, x.halo - p, s, s,
                                         pk.tapoff(x.Wp), None, self.bias_k if use_bias else None, y, y.halo, y.halo, 1, 1, act, mask,
                                         mask.halo if mask else 0, mask.halo if mask else 0, pk.max_tapoff(x.Wp)))
-            if stats_ws is not None and (call.w_frag or call.win7 is not None) and call.Nst == y.C and not os.environ.get("GAN_NO_FUSED_STATS"):
+            if stats_ws is not None and (call.w_frag or call.win7 is not None) and call.Nst == y.C:
                 n = ops.conv_stats_parts(call)
                 if 0 < n and x.B * n * y.C * 2 <= stats_ws.numel():
                     call.stats, self.stats_parts = stats_ws, n
@@ -256,7 +255,7 @@ class ConvLayer:
         call = pk.finalize8(ConvCall(x8.B, y.H, y.W, pk.cred, pk.ntaps, pk.nw, min(pk.nw, y.C), x8, x8.halo - p, x8.halo - p, 1, 1, pk.tapoff(x8.Wp), None,
                                      self.bias_k, y, y.halo, y.halo, 1, 1, act, None, 0, 0, pk.max_tapoff(x8.Wp), in_scale=in_scale))
         self.stats_parts = 0
-        if stats_ws is not None and call.Nst == y.C and not os.environ.get("GAN_NO_FUSED_STATS"):
+        if stats_ws is not None and call.Nst == y.C:
             n = ops.conv_stats_parts(call)
             if 0 < n and x8.B * n * y.C * 2 <= stats_ws.numel():
                 call.stats, self.stats_parts = stats_ws, n
@@ -282,7 +281,7 @@ class ConvLayer:
         """Lazily built _PairPack per phase row (see there); None when the layer does not qualify."""
         key = id(packs)
         if key not in self._pairs:
-            ok = (self.ctx.dtype == BF16 and packs[0].n_real == 64 and packs[0].cred % 64 == 0 and not os.environ.get("GAN_NO_PHASE_PAIRS"))
+            ok = (self.ctx.dtype == BF16 and packs[0].n_real == 64 and packs[0].cred % 64 == 0)
             self._pairs[key] = [_PairPack(self.ctx, packs[2 * ry], packs[2 * ry + 1]) for ry in range(2)] if ok else None
             if ok:
                 self.packs += self._pairs[key]

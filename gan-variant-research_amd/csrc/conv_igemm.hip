@@ -29,7 +29,6 @@ struct ConvArgs {
   int out_Hp, out_Wp, out_C, out_y0, out_x0, out_sy, out_sx;
   int Nst, act, MT, NTILES;
   int mask_Hp, mask_Wp, mask_y0, mask_x0;
-  int dbg;  // timing-only ablations (GAN_CONV_DEBUG): 1 skip A staging after step 0, 2 skip B staging, 4 skip MFMA
 };
 
 template <typename T> struct Mma;
@@ -68,7 +67,7 @@ __global__ __launch_bounds__(WM* WN * 64) void conv_igemm_kernel(ConvArgs a) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   // PERSISTENT blocks (round 3): a block walks virtual block ids L = blockIdx.x, + gridDim.x, ... and stages the first K-step of its next
   // tile before the epilogue of the current one.  Measured on the 3x3 stride-2 64->128 layer (9 K-steps per tile, 32 images): 121 of the
-  // 199 us were prologue + first stage + epilogue of 4096 one-tile blocks (GAN_CONV_DEBUG=8); the MFMAs were 9 us of it.
+  // 199 us were prologue + first stage + epilogue of 4096 one-tile blocks (a one-K-step ablation build); the MFMAs were 9 us of it.
   // XCD-aware tile mapping: virtual blocks L and L+8 share an XCD (gridDim.x is a multiple of 8); give them the same M-tile.
   const int nvirt = ((a.MT + 7) / 8) * 8 * a.NTILES;
   auto decode = [&](int L, int& m0, int& n0) {
@@ -125,16 +124,12 @@ __global__ __launch_bounds__(WM* WN * 64) void conv_igemm_kernel(ConvArgs a) {
     char* sb = sa + BM * 128;
     const int kk = ks * BKE + cc * EPC;
     const uint32_t koff = (uint32_t)(taptab[kk >> a.lgCin] + (kk & (a.Cin - 1))) * (uint32_t)sizeof(T);
-    if (!((a.dbg & 1) && ks > 0)) {
 #pragma unroll
-      for (int i = 0; i < AI; ++i) glds16(a.in, a_row[i] + koff, sa + lds_thr + i * (RSTEP * 128));
-    }
+    for (int i = 0; i < AI; ++i) glds16(a.in, a_row[i] + koff, sa + lds_thr + i * (RSTEP * 128));
     const uint32_t kb = (uint32_t)(ks * BKE) * (uint32_t)sizeof(T);
-    if (!((a.dbg & 2) && ks > 0)) {
 #pragma unroll
-      for (int i = 0; i < BI; ++i)
-        if (BN >= RSTEP * (i + 1) || rr + RSTEP * i < BN) glds16(a.w, b_row[i] + kb, sb + lds_thr + i * (RSTEP * 128));
-    }
+    for (int i = 0; i < BI; ++i)
+      if (BN >= RSTEP * (i + 1) || rr + RSTEP * i < BN) glds16(a.w, b_row[i] + kb, sb + lds_thr + i * (RSTEP * 128));
   };
 
   const int wm = wave / WN, wn = wave % WN;
@@ -148,7 +143,7 @@ __global__ __launch_bounds__(WM* WN * 64) void conv_igemm_kernel(ConvArgs a) {
 #pragma unroll
   for (int j = 0; j < NT; ++j) wb[j] = (uint32_t)(BM * 128 + (wn * NT * 16 + j * 16 + fr) * 128);
 
-  const int nk = (a.dbg & 8) ? 1 : a.nk;  // dbg 8: prologue + one K-step + epilogue only
+  const int nk = a.nk;
   T* out = reinterpret_cast<T*>(a.out);
   const T* mask = reinterpret_cast<const T*>(a.mask);
   int buf = 0;
@@ -180,13 +175,6 @@ __global__ __launch_bounds__(WM* WN * 64) void conv_igemm_kernel(ConvArgs a) {
         for (int i = 0; i < 4; ++i) xf[i] = *reinterpret_cast<const u32x4_t*>(sbuf + xa[i] + co);
 #pragma unroll
         for (int j = 0; j < NT; ++j) wf[j] = *reinterpret_cast<const u32x4_t*>(sbuf + wb[j] + co);
-        if (a.dbg & 4) {
-#pragma unroll
-          for (int i = 0; i < 4; ++i) asm volatile("" ::"v"(xf[i]));
-#pragma unroll
-          for (int j = 0; j < NT; ++j) asm volatile("" ::"v"(wf[j]));
-          continue;
-        }
 #pragma unroll
         for (int i = 0; i < 4; ++i)
 #pragma unroll
@@ -216,7 +204,7 @@ __global__ __launch_bounds__(WM* WN * 64) void conv_igemm_kernel(ConvArgs a) {
           // bf16, Nst % 8 == 0: lanes 16 apart hold the same pixel and adjacent channel quads; of each pair of channel tiles even fg keeps
           // the first and odd fg the second (v_permlane16_swap, as in conv_patch.hip) -> one 16-byte store per lane and tile pair instead of
           // two 8-byte ones (the 8-byte stores of the 3x3 s2 64->128 layer were 43 of its 135 us)
-          const bool vec16 = sizeof(T) == 2 && NT % 2 == 0 && (a.Nst & 7) == 0 && (a.out_C & 7) == 0 && !(a.dbg & 16);
+          const bool vec16 = sizeof(T) == 2 && NT % 2 == 0 && (a.Nst & 7) == 0 && (a.out_C & 7) == 0;
           u32x2_t pkv[NT];
 #pragma unroll
           for (int j = 0; j < NT; ++j) {
@@ -234,7 +222,6 @@ __global__ __launch_bounds__(WM* WN * 64) void conv_igemm_kernel(ConvArgs a) {
 #pragma unroll
               for (int e = 0; e < 4; ++e) v[e] *= (ld1<T>(mask + mb + n + e) > 0.f ? 1.f : 0.2f);
             }
-            if (a.dbg & 16) { asm volatile("" ::"v"(v[0]), "v"(v[1]), "v"(v[2]), "v"(v[3])); continue; }
             if constexpr (sizeof(T) == 4) {
               *reinterpret_cast<f32x4_t*>(out + ob + n) = f32x4_t{v[0], v[1], v[2], v[3]};
             } else {
@@ -291,7 +278,7 @@ int igemm_plan(const gan_conv_desc* d, IgemmPlan* p) {
   p->ntiles = (d->Nst + p->bn - 1) / p->bn;
   p->nvirt = ((p->mt + 7) / 8) * 8 * p->ntiles;
   // persistent: as many blocks as the chip holds at once (LDS: two 2 x 32 KB blocks per CU on 256 CUs), a multiple of 8 (XCD mapping)
-  static const int resident = [] { const char* e = getenv("GAN_IGEMM_BLOCKS"); const int v = e ? atoi(e) : 512; return v >= 8 ? (v / 8) * 8 : 512; }();
+  constexpr int resident = 512;
   p->grid = p->nvirt < resident ? p->nvirt : resident;
   return 0;
 }
@@ -351,7 +338,6 @@ extern "C" int gan_conv_igemm(const gan_conv_desc* d, void* stream) {
   a.out_Hp = d->out_Hp; a.out_Wp = d->out_Wp; a.out_C = d->out_C; a.out_y0 = d->out_y0; a.out_x0 = d->out_x0;
   a.out_sy = d->out_sy; a.out_sx = d->out_sx;
   a.Nst = d->Nst; a.act = d->act; a.MT = 0; a.NTILES = 0;
-  { const char* e = getenv("GAN_CONV_DEBUG"); a.dbg = e ? atoi(e) : 0; }
   a.mask_Hp = d->mask_Hp; a.mask_Wp = d->mask_Wp; a.mask_y0 = d->mask_y0; a.mask_x0 = d->mask_x0;
   hipStream_t s = (hipStream_t)stream;
   IgemmPlan p;

@@ -24,7 +24,6 @@
 //    emits the InstanceNorm statistics of its tile (gan_conv_desc.stats) with DPP row reductions.
 #include <stdlib.h>
 #include <type_traits>
-#include <array>
 #include <atomic>
 #include "common.h"
 
@@ -46,7 +45,6 @@ struct PatchArgs {
   const float* w_scale; const float* in_scale;   // FP8: dequantisation scales (weights: one float; input: per image or NULL)
   float* stats;                 // optional per-tile InstanceNorm partials [B][MT_img][out_C][2] (sum, sum of squares), plain stores
   int smode;                    // statistics mode (gan_conv_desc.stats_mode)
-  unsigned long long* stamps;   // diagnostic build only (GAN_PATCH_STAMPS): [block][32] s_memtime stamps of wave 0
 };
 
 constexpr int NTHR = 512;   // the tile is a template parameter: BM = 256 (4 x 2 waves of 64 x 64) or 288 (2 x 4 waves of 144 x 32) rows by BN = 128 channels,
@@ -161,26 +159,7 @@ __device__ __forceinline__ void conv_patch_body(const PatchArgs& a) {
     for (int j = 0; j < FJ; ++j)
       f[j] = __builtin_bit_cast(u32x4_t, __builtin_amdgcn_raw_buffer_load_b128(wrsrc, lane16, base + j * a.KB * 1024, 0));
   };
-  const bool dbg_w0 = a.stamps && ((uintptr_t)a.stamps & 2);   // diagnostic: every weight fetch reads block 0 (L1-resident)
-  auto kb_of = [&](int c, int t) { return dbg_w0 ? 0 : (t * a.Cin + c * 64) >> 5; };
-
-  int nstamp = 0;
-  auto stamp = [&]() {
-    if (a.stamps && wave == 0 && nstamp < 30) {
-      unsigned long long t;
-      asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
-      if (lane == 0) {
-        unsigned long long* sb = (unsigned long long*)((uintptr_t)a.stamps & ~(uintptr_t)7) + blockIdx.x * 32;
-        sb[nstamp] = t;
-        // slots 30 / 31: the 100 MHz wall counter at the first / latest stamp (in-kernel clock = d(s_memtime) / d(s_memrealtime) * 100 MHz)
-        const unsigned long long rt = __builtin_amdgcn_s_memrealtime();
-        if (nstamp == 0) sb[30] = rt;
-        sb[31] = rt;
-      }
-      ++nstamp;
-    }
-  };
-  stamp();
+  auto kb_of = [&](int c, int t) { return (t * a.Cin + c * 64) >> 5; };
   TileGeo g = tile_geo<BM, BN>(a, tau);
   // prologue: first slab -> LDS buffer 0, first tap's weights -> registers
   {
@@ -206,7 +185,6 @@ __device__ __forceinline__ void conv_patch_body(const PatchArgs& a) {
   else w_load(g.n0, kb_of(0, 0), Wa);
 
   __syncthreads();   // tap table + slab 0 visible
-  stamp();
 
   int pcur = 0;
   while (true) {
@@ -325,7 +303,6 @@ __device__ __forceinline__ void conv_patch_body(const PatchArgs& a) {
           }
         }
         __syncthreads();   // every wave is done with this slab; the other buffer is completely written
-        stamp();
       };
       for (int c = 0; c < a.nchunk; c += 2) {   // nchunk is even: every tile starts on buffer 0
         static_slab(std::integral_constant<int, 0>{}, c);
@@ -403,7 +380,6 @@ __device__ __forceinline__ void conv_patch_body(const PatchArgs& a) {
         }
         __syncthreads();
         pcur ^= 1;
-        stamp();
       }
     } else if constexpr (BN == 256) {
       // 256-channel tile: a wave owns (BM/2) x 64 outputs = 8-9 pixel fragments x 4 channel fragments, 32-36 MFMAs per k-step against
@@ -495,7 +471,6 @@ __device__ __forceinline__ void conv_patch_body(const PatchArgs& a) {
         for (int t = STAGED_TAPS; t < a.ntaps; ++t) tap(IC{}, IC{}, IC{}, IC{}, t);
         __syncthreads();
         pcur ^= 1;
-        stamp();
       }
     } else
     for (int c = 0; c < a.nchunk; ++c) {
@@ -573,7 +548,6 @@ __device__ __forceinline__ void conv_patch_body(const PatchArgs& a) {
       }
       __syncthreads();   // every wave is done with slab `pcur`; slab `pcur^1` is completely written
       pcur ^= 1;
-      stamp();
     }
 
     // ---- epilogue (the next tile's slab is in LDS and its first weights are in flight).  Specialised on the activation at
@@ -809,7 +783,6 @@ __device__ __forceinline__ void conv_patch_body(const PatchArgs& a) {
       else epilogue(integral_constant<int, GAN_ACT_TANH>{}, integral_constant<bool, false>{}, integral_constant<bool, false>{});
     }
 
-    stamp();
     if (!has_next) break;
     tau = tau_next;
     g = gn;
@@ -881,9 +854,7 @@ static int patch_tile_rows(const gan_conv_desc* d, bool planning = false) {
 // Pure predicate (no device access): does this descriptor qualify for the range-patch kernel?  The planner asks at
 // build time because qualifying calls need the fragment-major weight packing (gan_pack_weight layout 1).
 extern "C" int gan_conv_patch_ok(const gan_conv_desc* d) {
-  static int disabled = -1;
-  if (disabled < 0) { const char* e = getenv("GAN_NO_PATCH"); disabled = (e && atoi(e)) ? 1 : 0; }
-  if (disabled || !d) return 0;
+  if (!d) return 0;
   constexpr int BN = 128;
   if (d->mask && d->act != GAN_ACT_NONE) return 0;   // the masked epilogue is specialised for act = none
   const bool fp8 = d->dtype == GAN_FP8;
@@ -926,14 +897,13 @@ extern "C" int gan_conv_stats_parts(const gan_conv_desc* d) {
 // Which instantiation a qualifying descriptor runs on (the launch and the planner's query share this decision):
 // tile rows | tile columns << 12 | LDS slices (7: maps up to 64 pixels wide, 9: up to 128) << 24 | e4m3 operands << 28 | static 3x3 schedule << 29
 static int patch_variant(const gan_conv_desc* d) {
-  static const bool static_off = [] { const char* e = getenv("GAN_PATCH_STATIC"); return e && !atoi(e); }();
   const int BM = patch_tile_rows(d);
   const int BN = patch_bn(d, BM);
   const bool fp8 = d->dtype == GAN_FP8;
   const int slots = fp8 ? d->Cin / 2 : d->Cin;
   const bool wide = BM == 256 && patch_span(d, 256) > RMAX;      // needs the 9-slice buffers (maps wider than 64 pixels)
   const bool chain = d->stats_mode != 0;      // backward-chain epilogue: generic tap loop
-  const bool st_ok = !fp8 && !chain && BN == 128 && BM == 256 && (slots / 64) % 2 == 0 && !static_off;
+  const bool st_ok = !fp8 && !chain && BN == 128 && BM == 256 && (slots / 64) % 2 == 0;
   const bool st9 = st_ok && !wide && d->ntaps == 9;
   // static schedules for the other tap counts of the two networks (bits 30-31: 1 = 4 taps, 2 = 2 taps, 3 = 16 taps): the sub-pixel phases of the
   // transposed convolutions / strided input gradients (2 and 4 taps, also on the 9-slice buffers) and the discriminator's 4x4 windows
@@ -996,16 +966,6 @@ int gan_conv_patch_launch(const gan_conv_desc* d, hipStream_t s) {
     if (d->mask_y0 + d->Ho > d->mask_Hp || d->mask_x0 + d->Wo > d->mask_Wp) return gan_set_error(-1, "conv: stats_mode 1: the operand does not cover the output domain");
   }
   a.mask_Hp = d->mask_Hp; a.mask_Wp = d->mask_Wp; a.mask_y0 = d->mask_y0; a.mask_x0 = d->mask_x0;
-  // diagnostic environment (stamp buffer, static-schedule switch): read once per process, not per launch
-  static unsigned long long* const stamps_env = [] { const char* e = getenv("GAN_PATCH_STAMPS"); return e ? (unsigned long long*)strtoull(e, nullptr, 0) : nullptr; }();
-  // GAN_PATCH_STAMPS_SEL="rows,cols,batch,chain,taps": only launches of that tile, batch and epilogue stamp (tools/step_clock.py reads one kernel
-  // of the running step)
-  static const std::array<int, 5> stamps_sel = [] {
-    std::array<int, 5> v{0, 0, 0, 0, 0};
-    if (const char* e = getenv("GAN_PATCH_STAMPS_SEL")) sscanf(e, "%d,%d,%d,%d,%d", &v[0], &v[1], &v[2], &v[3], &v[4]);
-    return v;
-  }();
-  a.stamps = (stamps_sel[0] == 0 || (stamps_sel[0] == BM && stamps_sel[1] == BN && stamps_sel[2] == d->B && stamps_sel[3] == (a.smode != 0) && stamps_sel[4] == d->ntaps)) ? stamps_env : nullptr;
   const int grid = patch_grid(a.tiles);
   // the dynamic-LDS limit is a per-device function attribute: one bit per device, set on that device's first launch
   static std::atomic<uint64_t> attr_devs{0};

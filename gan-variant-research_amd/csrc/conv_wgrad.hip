@@ -459,8 +459,7 @@ extern "C" int gan_conv_wgrad(const gan_wgrad_desc* d, void* stream) {
   a.Cx = d->Cx; a.lgCx = __builtin_ctz(d->Cx); a.ntaps = d->ntaps; a.Ktot = d->ntaps * d->Cx; a.N = d->N;
   a.x_Hp = d->x_Hp; a.x_Wp = d->x_Wp; a.x_y0 = d->x_y0; a.x_x0 = d->x_x0; a.x_sy = d->x_sy; a.x_sx = d->x_sx;
   a.g_Hp = d->g_Hp; a.g_Wp = d->g_Wp; a.g_C = d->g_C; a.g_y0 = d->g_y0; a.g_x0 = d->g_x0; a.g_sy = d->g_sy; a.g_sx = d->g_sx;
-  static const bool no_fast = [] { const char* e = getenv("GAN_WGRAD_SLOW_ADDR"); return e && atoi(e); }();     // A/B switch
-  a.fast = (!no_fast && a.HoWo % 64 == 0 && (a.Wo % 64 == 0 || 64 % a.Wo == 0)) ? 1 : 0;
+  a.fast = (a.HoWo % 64 == 0 && (a.Wo % 64 == 0 || 64 % a.Wo == 0)) ? 1 : 0;
   const int JT = 16 * epc;
   a.JTILES = (a.Ktot + JT - 1) / JT;
   hipStream_t s = (hipStream_t)stream;
@@ -515,14 +514,11 @@ __global__ __launch_bounds__(256) void wgrad_reduce_coop_kernel(const float* __r
   }
 }
 
-// lanes per output quad of gan_wgrad_reduce: enough threads to cover the load latency (~64 k), at most one lane per 4 slabs;
-// GAN_WGRAD_REDUCE_COOP (A/B switch) = 0 | 1: one lane, 2 .. 32: forced
+// lanes per output quad of gan_wgrad_reduce: enough threads to cover the load latency (~64 k), at most one lane per 4 slabs
 extern "C" int gan_wgrad_reduce_lanes(int nsplit, int N_real, int ntaps, int Cx) {
   const int64_t total = (int64_t)N_real * ntaps * (Cx / 4);
-  static const int coop_env = [] { const char* e = getenv("GAN_WGRAD_REDUCE_COOP"); return e ? atoi(e) : -1; }();
   int G = 1;
   while (G < 32 && total * G < 65536 && G * 8 <= nsplit) G *= 2;
-  if (coop_env >= 0) G = coop_env <= 1 ? 1 : coop_env >= 32 ? 32 : coop_env >= 16 ? 16 : coop_env >= 8 ? 8 : coop_env >= 4 ? 4 : 2;
   return G;
 }
 

@@ -242,7 +242,6 @@ extern "C" int gan_conv_win7_ok(const gan_conv_desc* d) {
   if (d->in_sy != 1 || d->in_sx != 1 || d->out_sy != 1 || d->out_sx != 1 || d->mask || (d->stats && !from3)) return 0;
   if (d->act != GAN_ACT_NONE && !(to3 && d->act == GAN_ACT_TANH)) return 0;
   if (d->max_tapoff != ((d->win_ty0 + 6) * d->in_Wp + d->win_tx0 + 6) * d->Cin) return 0;
-  { const char* e = getenv("GAN_NO_WIN7"); if (e && atoi(e)) return 0; }
   return 1;
 }
 
@@ -516,7 +515,6 @@ extern "C" int gan_wgrad_win7_splits(const gan_wgrad_desc* d) {
   if (!to3 && !from3) return 0;
   if (d->x_sy != 1 || d->x_sx != 1 || d->g_sy != 1 || d->g_sx != 1) return 0;
   if (d->max_tapoff != (6 * d->x_Wp + 6) * d->Cx) return 0;           // 49 row-major taps from (x_y0, x_x0)
-  { const char* e = getenv("GAN_NO_WIN7"); if (e && atoi(e)) return 0; }
   const int64_t tiles = (int64_t)d->B * ((d->Ho + TS - 1) / TS) * ((d->Wo + TS - 1) / TS);
   return (int)(tiles < 256 ? tiles : 256);
 }

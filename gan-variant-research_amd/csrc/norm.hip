@@ -685,11 +685,7 @@ int check_lanes(const gan_view* v, const char* what) {
   return 0;
 }
 // row-chunks per image for the statistics passes: ~2048 16-byte loads per block, at most MAXCH (workspace bound)
-int work_per_block() {   // 16-byte loads per block and operand; GAN_NORM_WORK overrides (tuning aid)
-  static int w = 0;
-  if (!w) { const char* e = getenv("GAN_NORM_WORK"); w = e ? atoi(e) : 4096; if (w < 256) w = 256; }
-  return w;
-}
+constexpr int WORK_PER_BLOCK = 4096;   // 16-byte loads per block and operand
 // partials per image for the passes whose consumer sums them itself (<= MAXPARTS): as many as keep ~2 blocks per CU busy
 int nparts_for(int B, int HW, int cl) {
   int64_t n = ((int64_t)HW * cl + 2047) / 2048;       // at least 2048 loads per block
@@ -700,7 +696,7 @@ int nparts_for(int B, int HW, int cl) {
   return (int)n;
 }
 int nchunks_for(int HW, int cl) {
-  const int W = work_per_block();
+  const int W = WORK_PER_BLOCK;
   int64_t n = ((int64_t)HW * cl + W - 1) / W;
   if (n < 1) n = 1;
   if (n > MAXCH) n = MAXCH;
@@ -708,7 +704,7 @@ int nchunks_for(int HW, int cl) {
 }
 // blocks per image for the apply passes (no workspace bound)
 int nblocks_for(int pixels, int cl) {
-  const int W = work_per_block();
+  const int W = WORK_PER_BLOCK;
   int64_t n = ((int64_t)pixels * cl + W - 1) / W;
   if (n < 1) n = 1;
   if (n > 1024) n = 1024;
@@ -725,22 +721,9 @@ int fold_ok(const gan_view* g, int fold) {
 }  // namespace
 
 // pixels in flight per thread of the streaming kernels: 2 for the backward family (fits beside a resident weight-gradient block: <= 80
-// registers), 4 for the forward passes, which run alone.  GAN_NORM_UNR / GAN_NORM_UNR_FWD = 2, 3 or 4 override (tuning aid, read once).
-static int norm_unroll(bool fwd) {
-  static int u[2] = {0, 0};
-  if (!u[fwd]) { const char* e = getenv(fwd ? "GAN_NORM_UNR_FWD" : "GAN_NORM_UNR"); const int v = e ? atoi(e) : (fwd ? 4 : 2); u[fwd] = v >= 2 && v <= 4 ? v : (fwd ? 4 : 2); }
-  return u[fwd];
-}
-#define GAN_DISPATCH_NORM_U(dt, fwd, ...)                                            \
-  {                                                                                  \
-    const int unr__ = norm_unroll(fwd);                                              \
-    if ((dt) == GAN_F32) { typedef float T;                                          \
-      if (unr__ == 2) { constexpr int U = 2; __VA_ARGS__ } else if (unr__ == 3) { constexpr int U = 3; __VA_ARGS__ } else { constexpr int U = 4; __VA_ARGS__ } } \
-    else { typedef bf16_t T;                                                         \
-      if (unr__ == 2) { constexpr int U = 2; __VA_ARGS__ } else if (unr__ == 3) { constexpr int U = 3; __VA_ARGS__ } else { constexpr int U = 4; __VA_ARGS__ } } \
-  }
-#define GAN_DISPATCH_NORM(dt, ...) GAN_DISPATCH_NORM_U(dt, false, __VA_ARGS__)
-#define GAN_DISPATCH_NORM_FWD(dt, ...) GAN_DISPATCH_NORM_U(dt, true, __VA_ARGS__)
+// registers), 4 for the forward passes, which run alone.
+#define GAN_DISPATCH_NORM(dt, ...) { constexpr int U = 2; GAN_DISPATCH_DTYPE(dt, __VA_ARGS__) }
+#define GAN_DISPATCH_NORM_FWD(dt, ...) { constexpr int U = 4; GAN_DISPATCH_DTYPE(dt, __VA_ARGS__) }
 
 #define VCHK(v, name) do { if (gan_check_view(v, name)) return -1; } while (0)
 #define SAME_SHAPE(a, b, what) GAN_CHECK((a)->B == (b)->B && (a)->H == (b)->H && (a)->W == (b)->W && (a)->C == (b)->C && (a)->dtype == (b)->dtype, what ": shape/dtype mismatch")

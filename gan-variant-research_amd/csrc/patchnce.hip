@@ -426,9 +426,7 @@ extern "C" int64_t gan_patchnce_ws_floats(int B, int P, int C) {
 
 // the MFMA tiling: 16-channel k chunks per load, 4 waves x C/4 output channels in 16-wide tiles, 16-patch k chunks
 static bool nce_mfma_ok(int P, int C) {
-  static int off = -1;
-  if (off < 0) { const char* e = getenv("GAN_NO_NCE_MFMA"); off = (e && atoi(e)) ? 1 : 0; }
-  return !off && C % 64 == 0 && C <= 256 && P % 16 == 0 && P <= 256;
+  return C % 64 == 0 && C <= 256 && P % 16 == 0 && P <= 256;
 }
 
 static int nce_check(const gan_view* t, int P, int C) {

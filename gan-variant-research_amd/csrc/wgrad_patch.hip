@@ -221,9 +221,7 @@ __global__ __launch_bounds__(512) void wgrad_patch_kernel(WpArgs a) {
 // splits per image the range-patch weight-gradient kernel wants for this problem (0 = descriptor does not qualify).
 // The planner sizes `part` for B * spi slabs and sets nsplit = B * spi, variant = 1.
 extern "C" int gan_wgrad_patch_splits(const gan_wgrad_desc* d) {
-  static int disabled = -1;
-  if (disabled < 0) { const char* e = getenv("GAN_NO_WPATCH"); disabled = (e && atoi(e)) ? 1 : 0; }
-  if (disabled || !d) return 0;
+  if (!d) return 0;
   if (d->dtype != GAN_BF16 || d->ntaps != NT || d->Cx % CB != 0 || d->N % NB != 0 || d->N != d->g_C) return 0;
   if (d->x_sy != 1 || d->x_sx != 1 || d->g_sy != 1 || d->g_sx != 1) return 0;
   // 3x3 window in row-major tap order over a map whose width is a power of two dividing the stage

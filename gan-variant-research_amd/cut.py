@@ -727,13 +727,6 @@ class CutTrainer:
         if self.device.type != "cuda":
             return dist.all_reduce(opt.flat_g, group=self.pg, async_op=True), None
         cur = opt.ctx.ops._ts()                                  # the stream the gradients were produced on
-        if os.environ.get("GAN_COMM_STREAM"):                    # a communication stream of our own in front of RCCL's (not needed: see below)
-            if self._comm_stream is None:
-                self._comm_stream = torch.cuda.Stream(device=self.device)
-            self._comm_stream.wait_stream(cur)
-            with torch.cuda.stream(self._comm_stream):
-                work = dist.all_reduce(opt.flat_g, group=self.pg, async_op=True)
-            return work, cur
         # RCCL runs the collective on its own internal stream, ordered after everything queued on the stream that is current at the
         # call: issuing it under the producing stream needs no extra stream (four compute/communication streams = four hardware queues)
         with torch.cuda.stream(cur):
@@ -794,10 +787,6 @@ class CutTrainer:
             return
         with torch.cuda.stream(cur):                             # the stream that produced the gradients (and will consume the
             work.wait()                                          # reduced ones) waits for the collective; the host does not
-        if self._comm_stream is not None:
-            cur.wait_stream(self._comm_stream)
-
-    _comm_stream = None
 
     # ---- the two events per step that order the main stream and the discriminator's stream
     def _ev_fake_ready(self):

@@ -166,18 +166,15 @@ class GPass:
             out = self.acts[i] if out is None else out
             halo = self.halo_mode(i) if out is self.acts[i] else net.pad_mode
             ws = net.in_ws(self.B, raw.C)
-            fused = not os.environ.get("GAN_NO_FUSED_FINALIZE")
             if conv is not None and conv.stats_parts:     # the convolution's epilogue already wrote per-tile (sum, sum of squares)
-                if fused and conv.stats_parts <= 16:          # few tiles: the apply pass adds them up itself (no statistics launch at all)
+                if conv.stats_parts <= 16:          # few tiles: the apply pass adds them up itself (no statistics launch at all)
                     prog.add(ops.in_apply_parts(raw, ws, conv.stats_parts, IN_EPS, stats, act, residual, out, halo, out8))
                     return
                 prog.add(ops.in_stats_from_parts(ws, conv.stats_parts, self.B, raw.C, raw.H * raw.W, IN_EPS, stats))
-            elif fused:
+            else:
                 prog.add(ops.in_partial(raw, ws))
                 prog.add(ops.in_apply_parts(raw, ws, ops.in_partial_count(raw), IN_EPS, stats, act, residual, out, halo, out8))
                 return
-            else:
-                prog.add(ops.in_stats(raw, IN_EPS, stats, ws))
             prog.add(ops.in_apply(raw, stats, act, residual, out, halo))
             if out8 is not None:
                 prog.add(ops.quantize_fp8(out, out8))
@@ -258,43 +255,32 @@ class GPass:
 
         # bias gradients in front of a norm are column sums of dx: the norm backward leaves per-block partials in a buffer of the
         # layer's own and ONE launch at the end of the program sums them for every layer (two tiny launches per layer less on the chain)
-        defer = os.environ.get("GAN_BIAS_DEFER", "1") != "0"
         bias_items = []
         if not hasattr(self, "_bias_parts"):
             self._bias_parts = {}
+
+        def bias_part(conv, raw):
+            """The layer's own buffer of per-block bias partials (listed for the summing launch), or None when `conv` has no bias."""
+            if conv is None or conv.grad_b is None:
+                return None
+            nparts = ops.in_bwd_bias_parts(raw)
+            part = self._bias_parts.get(id(conv))
+            if part is None:
+                part = self._bias_parts[id(conv)] = ctx.f32(nparts * raw.C)
+            bias_items.append((part, nparts, raw.C, conv.grad_b, conv.cout, acc))
+            return part
 
         def inbwd(raw, stats, act, gy, fold, dx, conv=None, amax=None, parts=None):
             """InstanceNorm backward; with `conv`, its bias gradient (column sums of dx) comes out of the same pass; with `amax`, max|dx|
             per image too (the scale of dx's e4m3 copy); with `parts` = (ws, nparts, mode) the two sums were written by the producer of gy
             (an input-gradient epilogue, ConvLayer.dgrad(chain=...)) and only the apply half runs."""
+            part = bias_part(conv, raw)
             if parts is not None:
-                part = None
-                if conv is not None and conv.grad_b is not None:
-                    nparts = ops.in_bwd_bias_parts(raw)
-                    part = self._bias_parts.get(id(conv))
-                    if part is None:
-                        part = self._bias_parts[id(conv)] = ctx.f32(nparts * raw.C)
-                    bias_items.append((part, nparts, raw.C, conv.grad_b, conv.cout, acc))
                 prog.add(ops.in_bwd_parts(raw, stats, act, gy, fold, dx, parts[0], parts[1], parts[2], part))
-                return
-            if amax is not None:
-                part = None
-                if conv is not None and conv.grad_b is not None:
-                    nparts = ops.in_bwd_bias_parts(raw)
-                    part = self._bias_parts.get(id(conv))
-                    if part is None:
-                        part = self._bias_parts[id(conv)] = ctx.f32(nparts * raw.C)
-                    bias_items.append((part, nparts, raw.C, conv.grad_b, conv.cout, acc))
+            elif amax is not None:
                 prog.add(ops.in_bwd_amax(raw, stats, act, gy, fold, dx, net.in_ws(B, raw.C), part, amax))
-            elif conv is not None and conv.grad_b is not None and defer:
-                nparts = ops.in_bwd_bias_parts(raw)
-                part = self._bias_parts.get(id(conv))
-                if part is None:
-                    part = self._bias_parts[id(conv)] = ctx.f32(nparts * raw.C)
+            elif part is not None:
                 prog.add(ops.in_bwd_bias_deferred(raw, stats, act, gy, fold, None, dx, net.in_ws(B, raw.C), part))
-                bias_items.append((part, nparts, raw.C, conv.grad_b, conv.cout, acc))
-            elif conv is not None and conv.grad_b is not None:
-                prog.add(ops.in_bwd_bias(raw, stats, act, gy, fold, None, dx, net.in_ws(B, raw.C), conv.grad_b, conv.cout, acc))
             else:
                 prog.add(ops.in_bwd(raw, stats, act, gy, fold, None, dx, net.in_ws(B, raw.C)))
 
@@ -528,18 +514,12 @@ class DPass:
         # The discriminator's weight gradients stay on its own stream: they are 2 % of the step, and a fourth compute stream would
         # share a hardware queue with another one as soon as RCCL adds its stream (HIP multiplexes streams onto four queues;
         # measured: the discriminator's stream landed on the main stream's queue and the step lost 1.1 ms)
-        side = ops.side() if (wgrad and keep is None and os.environ.get("GAN_D_SIDE")) else None
         for li in range(net.nconv - 1, -1, -1):
             conv = net.convs[li]
             xin = self.acts[li - 1] if li > 0 else self.x
             if keep is not None:
                 keep.append(dy)
-            if wgrad and side is not None:
-                ev = ops.new_event()
-                prog.add(ops.record(ev))
-                prog.add(side.wait(ev))
-                prog.add(conv.wgrad(xin, dy, accumulate, bias_too=bias_grads, ops=side))
-            elif wgrad:
+            if wgrad:
                 prog.add(conv.wgrad(xin, dy, accumulate, bias_too=bias_grads))
             if li == 0:
                 if need_input_grad:
@@ -559,8 +539,4 @@ class DPass:
                 nxt = net.gbuf(tag, B, a.H, a.W, a.C, halo)
                 prog.add(ops.in_bwd(self.raw[li - 1], self.stats[li - 1], ACT_LRELU, g_a, False, None, nxt, net.in_ws(B, a.C)))
             dy = nxt
-        if side is not None:
-            join = ops.new_event()
-            prog.add(side.record(join))
-            prog.add(ops.wait(join))
         return prog

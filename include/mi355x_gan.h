@@ -154,7 +154,7 @@ int gan_wgrad_patch_splits(const gan_wgrad_desc* d);
 /* slabs the 7x7 window weight-gradient kernels write (0: the descriptor does not qualify: bf16, 49 row-major taps, stride 1, and
  * Cx = 64, N = g_C = 8 -- the generator's 64 -> 3 channel output convolution -- or Cx = 8, N = g_C = 64 -- its 3 -> 64 first one) */
 int gan_wgrad_win7_splits(const gan_wgrad_desc* d);
-/* lanes G (1, 2 ... 32) gan_wgrad_reduce lets share one output quad for these arguments (GAN_WGRAD_REDUCE_COOP forces one); pure query */
+/* lanes G (1, 2 ... 32) gan_wgrad_reduce lets share one output quad for these arguments; pure query */
 int gan_wgrad_reduce_lanes(int nsplit, int N_real, int ntaps, int Cx);
 int gan_wgrad_reduce(const float* part, int nsplit, int N, int ntaps, int Cx, int N_real, int C_real, int swap, int I2,
                      int KK, const int32_t* khw, float* grad, int accumulate, void* stream);

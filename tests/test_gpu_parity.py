@@ -118,8 +118,7 @@ def test_wgrad_patch_splits_spanning_images():
 @pytest.mark.parametrize("geom", [g for g in cases.GEOMS if g[2] == 7 and max(g[0], g[1]) == 64])
 def test_conv_7x7_window_kernel_is_taken(geom):
     """The 64 <-> 3 channel 7x7 layers run on the two window kernels in bf16 (64->3: output conv forward, first conv's input gradient;
-    3->64: first conv forward, output conv's input gradient) and stay correct (run_conv_geometry compares with torch);
-    GAN_NO_WIN7=1 would send them back to the generic kernel."""
+    3->64: first conv forward, output conv's input gradient) and stay correct (run_conv_geometry compares with torch)."""
     ctx = hip_ctx(BF16)
     seen, wg = [], []
     orig, orig_w = ctx.ops.conv_igemm, ctx.ops.conv_wgrad

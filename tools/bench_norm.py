@@ -33,7 +33,7 @@ cases = {
     "in_bwd_bias_deferred fold": ([ops.in_bwd_bias_deferred(x, stats, _lib.ACT_RELU, gy, True, None, dx2, ws, bp)], 3),
     "fold_add (read a,g, write out)": ([ops.fold_add(x, gy, True, dx)], 3),
 }
-print(f"shape B={B} {H}x{W}x{Cc} bf16, {nbytes/1e6:.1f} MB per tensor, GAN_NORM_UNR={os.environ.get('GAN_NORM_UNR', '4')} GAN_NORM_WORK={os.environ.get('GAN_NORM_WORK', 'default')}")
+print(f"shape B={B} {H}x{W}x{Cc} bf16, {nbytes/1e6:.1f} MB per tensor")
 for name, (ol, mult) in cases.items():
     for _ in range(3):
         for o in ol: o()
