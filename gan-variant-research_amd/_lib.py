@@ -50,6 +50,11 @@ class GanPackDesc(C.Structure):
                 ("swap", i32), ("I2", i32), ("KK", i32), ("layout", i32), ("first_block", i32), ("nblocks", i32), ("scale", vp)]
 
 
+class GanSnDesc(C.Structure):
+    _fields_ = [("W", vp), ("u", vp), ("v", vp), ("sigma", vp), ("u_snap", vp), ("v_snap", vp), ("G", vp), ("dW", vp), ("ws", vp),
+                ("h", i32), ("w", i32), ("first_block", i32), ("nblocks", i32)]
+
+
 class GanBiasPartDesc(C.Structure):
     _fields_ = [("part", vp), ("grad", vp), ("nparts", i32), ("C", i32), ("N_real", i32), ("accumulate", i32), ("first_block", i32), ("_pad", i32)]
 
@@ -112,6 +117,10 @@ PROTOTYPES = {
     "gan_spectral_norm_ws_floats": (C.c_int64, [C.c_int, C.c_int]),
     "gan_spectral_norm_fwd": (C.c_int, [vp, C.c_int, C.c_int, vp, vp, C.c_int, C.c_float, vp, vp, vp, vp]),
     "gan_spectral_norm_bwd": (C.c_int, [vp, vp, vp, vp, vp, C.c_int, C.c_int, vp, vp, vp]),
+    "gan_spectral_norm_batch_ws_floats": (C.c_int64, [C.c_int, C.c_int]),
+    "gan_spectral_norm_batch_blocks": (C.c_int, [C.c_int, C.c_int]),
+    "gan_spectral_norm_batch_fwd": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_float, vp]),
+    "gan_spectral_norm_batch_bwd": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp]),
     "gan_avgpool_bwd": (C.c_int, [PV, PV, C.c_int, vp]),
     "gan_diffaug_fwd": (C.c_int, [PV, C.c_int, vp, PV, vp, vp]),
     "gan_diffaug_bwd": (C.c_int, [PV, C.c_int, vp, PV, vp, vp]),

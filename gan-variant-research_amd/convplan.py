@@ -73,8 +73,9 @@ class _Pack:
         c.tile_cols = self.ctx.ops.conv_patch_tile_cols(c)
         return c
 
-    def pack_ops(self, master: torch.Tensor):
-        """Refreshes every operand copy that some planned call uses (plan all calls BEFORE building the repack program)."""
+    def pack_ops(self, master: torch.Tensor, scale: Optional[torch.Tensor] = None):
+        """Refreshes every operand copy that some planned call uses (plan all calls BEFORE building the repack program).
+        scale: device float the bf16 / fp32 copies are divided by (spectral norm's sigma), or None."""
         out = []
         if self._wf8 is not None:
             out.append(self.ctx.ops.pack_weight(master, self._wf8, FP8, self.nw, self.ntaps, self.cred, self.n_real, self.c_real, self.swap,
@@ -82,7 +83,7 @@ class _Pack:
         for buf, layout in ((self._w, 0), (self._wf, 1)):
             if buf is not None:
                 out.append(self.ctx.ops.pack_weight(master, buf, self.ctx.dtype, self.nw, self.ntaps, self.cred, self.n_real, self.c_real,
-                                                    self.swap, self.i2, self.kk, self.khw, layout))
+                                                    self.swap, self.i2, self.kk, self.khw, layout, scale))
         return out
 
     def finalize(self, c: ConvCall) -> ConvCall:
@@ -131,13 +132,13 @@ class _PairPack(_Pack):
         self.dmin, self.dmax = (dmy, dmx), (max(pa.dmax[0], pb.dmax[0]), max(pa.dmax[1], pb.dmax[1]))
         self.phase_row = pa.phase[0]
 
-    def pack_ops(self, master: torch.Tensor):
+    def pack_ops(self, master: torch.Tensor, scale: Optional[torch.Tensor] = None):
         out, half = [], 64 * self.ntaps * self.cred       # 64 rows = four 16-row fragment groups: the same element count in both layouts
         for buf, layout in ((self._w, 0), (self._wf, 1)):
             if buf is not None:
                 for h, khw in enumerate(self.khw_halves):
                     out.append(self.ctx.ops.pack_weight(master, buf[h * half:(h + 1) * half], self.ctx.dtype, 64, self.ntaps, self.cred, self.n_half,
-                                                        self.c_real, self.swap, self.i2, self.kk, khw, layout))
+                                                        self.c_real, self.swap, self.i2, self.kk, khw, layout, scale))
         return out
 
 
@@ -189,6 +190,7 @@ class ConvLayer:
         self._wg_tapoff = {}
         self._pairs = {}
         self.bias_pair = None     # [bias | bias] for paired phases (allocated with the first paired plan)
+        self.pack_scale = None    # spectral norm: device sigma; the operand copies hold weight / sigma (nets.SpectralNorm)
 
     def _phase_packs(self, n_real, c_real, i2):
         """Four sub-pixel phases (ry, rx); index [ry*2+rx] -> (_Pack, dmin_y, dmin_x)."""
@@ -207,7 +209,7 @@ class ConvLayer:
 
     # ------------------------------------------------------------------ weights
     def repack_ops(self):
-        out = [op for pk in self.packs for op in pk.pack_ops(self.weight)]
+        out = [op for pk in self.packs for op in pk.pack_ops(self.weight, self.pack_scale)]
         if not out:
             # the operand copies are allocated when a call is planned: a repack program built before any fwd / dgrad plan would pack
             # nothing and the launches planned afterwards would multiply by zeros (measured that way, they also run ~20 % too fast:
@@ -376,9 +378,9 @@ class ConvLayer:
             ns -= 1
         return ns
 
-    def wgrad(self, x: View, dy: View, accumulate: bool, bias_too: bool = True, ops=None):
+    def wgrad(self, x: View, dy: View, accumulate: bool, bias_too: bool = True, ops=None, bias_accumulate: Optional[bool] = None):
         """grad_w (+)= dL/dW from the layer input `x` and the output gradient `dy`.  ops: op layer to build the launches on
-        (default: the context's; the backward programs pass the second-stream layer)."""
+        (default: the context's; the backward programs pass the second-stream layer).  bias_accumulate: for grad_b (default: accumulate)."""
         ctx, k, p = self.ctx, self.k, self.p
         ops = ctx.ops if ops is None else ops
         epc = 4 if ctx.dtype == F32 else 8
@@ -417,5 +419,6 @@ class ConvLayer:
         out = [ops.conv_wgrad(call),
                ops.wgrad_reduce(part, ns, n, self.kk, cx, n_real, c_real, False, i2, self.kk, self.wg_khw, self.grad_w, accumulate)]
         if bias_too and self.grad_b is not None:
-            out.append(ops.bias_grad(dy, self.cout, self.grad_b, accumulate, ctx.scratch("bias_ws", 256 * max(dy.C, 256))))
+            ba = accumulate if bias_accumulate is None else bias_accumulate
+            out.append(ops.bias_grad(dy, self.cout, self.grad_b, ba, ctx.scratch("bias_ws", 256 * max(dy.C, 256))))
         return out

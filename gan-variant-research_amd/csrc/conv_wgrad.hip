@@ -291,6 +291,7 @@ __device__ __forceinline__ void pack_one(const gan_pack_desc& D, int lb) {
   const float* __restrict__ src = D.src;
   T* __restrict__ dst = reinterpret_cast<T*>(D.dst);
   const int64_t total = (int64_t)D.Nw * D.ntaps * D.Cin;
+  const float sc = D.scale ? *D.scale : 1.f;     // spectral norm: the copy of W / sigma (a true division, as W_sn = W / sigma rounds)
   for (int64_t i = lb * (int64_t)blockDim.x + threadIdx.x; i < total; i += (int64_t)D.nblocks * blockDim.x) {
     const int c = (int)(i % D.Cin);
     const int t = (int)((i / D.Cin) % D.ntaps);
@@ -298,6 +299,7 @@ __device__ __forceinline__ void pack_one(const gan_pack_desc& D, int lb) {
     float v = 0.f;
     const int k = D.khw[t];
     if (n < D.N_real && c < D.C_real && k >= 0) v = src[D.swap ? ((int64_t)c * D.I2 + n) * D.KK + k : ((int64_t)n * D.I2 + c) * D.KK + k];
+    if (D.scale) v = v / sc;
     int64_t o = i;
     if (D.layout == 1) {
       const int kk = t * D.Cin + c, KB = D.ntaps * D.Cin / 32;
@@ -343,6 +345,7 @@ __device__ __forceinline__ void pack_one_bf16x8(const gan_pack_desc& D, int lb) 
   const int C8 = D.Cin >> 3;
   const int64_t units = (int64_t)D.Nw * C8 * D.ntaps;
   const int KB = D.ntaps * D.Cin / 32;
+  const float sc = D.scale ? *D.scale : 1.f;     // see pack_one
   for (int64_t u = lb * (int64_t)blockDim.x + threadIdx.x; u < units; u += (int64_t)D.nblocks * blockDim.x) {
     const int t = (int)(u % D.ntaps);                    // neighbouring threads: the taps of one (n, 8 channels) group -- they share its source lines
     const int64_t r = u / D.ntaps;
@@ -357,6 +360,7 @@ __device__ __forceinline__ void pack_one_bf16x8(const gan_pack_desc& D, int lb) 
         const int ce = c + 2 * h + q;
         const bool ok = k >= 0 && n < D.N_real && ce < D.C_real;
         v[q] = ok ? src[(D.swap ? ((int64_t)ce * D.I2 + n) : ((int64_t)n * D.I2 + ce)) * D.KK + k] : 0.f;
+        if (D.scale) v[q] = v[q] / sc;
       }
       pk[h] = (uint32_t)f2bf(v[0]) | ((uint32_t)f2bf(v[1]) << 16);
     }

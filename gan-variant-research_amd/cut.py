@@ -20,7 +20,7 @@ import torch
 import torch.nn as nn
 
 from ._lib import ACT_NONE, BF16, F32, HALO_NONE, HALO_ZERO
-from .nets import DiscriminatorNet, GeneratorNet
+from .nets import GeneratorNet, MultiscaleDiscriminatorNet, SpectralNorm
 from .runtime import ADAM_CHUNK, Ctx, HipOps, Program, View, cpad
 
 NCE_LAYERS_DEFAULT = (0, 4, 8, 12, 16)
@@ -197,8 +197,8 @@ class _PatchGANParams(nn.Module):
 
 
 class MultiscaleDiscriminator(nn.Module):
-    """Signature and defaults of models/discriminator_patchgan.py:81-88.  The baseline config (one scale, no spectral norm) is what the
-    fused CutTrainer runs; more scales and spectral norm run through this module API (autograd.py)."""
+    """Signature and defaults of models/discriminator_patchgan.py:81-88.  The fused CutTrainer runs every scale count with or without
+    spectral norm (nets.MultiscaleDiscriminatorNet); forward() is the module API (autograd.py)."""
 
     def __init__(self, input_nc=3, ndf=64, n_layers=3, num_scales=3, use_spectral_norm=True):
         super().__init__()
@@ -408,6 +408,7 @@ def feature_layers_present(layer_ids, n_blocks=9, n_down=2) -> List[int]:
 # the trainer
 # ------------------------------------------------------------------------------------------------
 LOSS_SLOTS = {"d_real": 0, "d_fake": 1, "r1": 2, "g_adv": 3, "nce": 4, "identity": 5, "scratch": 6, "idw": 7}
+SCALE_SLOTS = ("d_real", "d_fake", "g_adv")      # discriminator scales 1.. : three more slots each, after LOSS_SLOTS
 
 
 class CutTrainer:
@@ -451,13 +452,17 @@ class CutTrainer:
         if getattr(generator, "_layerwise", False) or getattr(generator, "padding_type", "reflect") != "reflect" or getattr(generator, "activation", "relu") != "relu":
             raise NotImplementedError("the fused CutTrainer runs the reference configuration (reflect padding, ReLU blocks); "
                                       "module_step.train_step drives the other generator variants on the same kernels")
-        if getattr(discriminator, "num_scales", 1) != 1 or getattr(discriminator, "use_spectral_norm", False):
-            raise NotImplementedError("the fused CutTrainer runs the reference configuration (one discriminator scale, no spectral norm); "
-                                      "module_step.train_step drives the optional discriminator variants on the same kernels")
+        self.num_scales = int(getattr(discriminator, "num_scales", 1))
+        self.spectral_norm = bool(getattr(discriminator, "use_spectral_norm", False))
 
         # ---- parameters -> flat fp32 blocks (master weights, grads, Adam moments, EMA shadow)
         gsd = {k: v.detach().to(self.device, torch.float32) for k, v in generator.state_dict().items()}
-        dsd = {k: v.detach().to(self.device, torch.float32) for k, v in discriminator.state_dict().items()}
+        dnames = set(k for k, _ in discriminator.named_parameters())
+        dsd = {k: v.detach().to(self.device, torch.float32) for k, v in discriminator.state_dict().items() if k in dnames}
+        # spectral norm's weight_u / weight_v: device buffers the power iterations update in place; the module's buffers alias them
+        self.d_buffers = {k: v.detach().to(self.device, torch.float32).clone().contiguous() for k, v in discriminator.named_buffers()}
+        for k, b in discriminator.named_buffers():
+            b.data = self.d_buffers[k]
         og, od = get_optimizer_config(config["optim"]["G"]), get_optimizer_config(config["optim"]["D"])
         self.opt_G = FusedAdam(self.ctx, list(gsd), [v.shape for v in gsd.values()], gsd, og["lr"], og["betas"], 1e-8, og["weight_decay"],
                                ema_decay=config["ema"]["decay"])
@@ -469,9 +474,14 @@ class CutTrainer:
         B, S = self.B, self.S
         nb, ngf = generator.n_blocks, generator.ngf
         self.G = GeneratorNet(self.ctx, self.opt_G.params, self.opt_G.grads, "cut", nb, ngf, need_input_grad=True, fp8=self.fp8)
-        self.D = DiscriminatorNet(self.ctxD, self.opt_D.params, self.opt_D.grads, "cut", ndf=discriminator.ndf, n_layers=discriminator.n_layers)
-        self.D32 = self.D if self.ctx32 is self.ctxD else DiscriminatorNet(self.ctx32, self.opt_D.params, self.opt_D.grads, "cut",
-                                                                          ndf=discriminator.ndf, n_layers=discriminator.n_layers)
+        K = self.num_scales
+        self.sn = None
+        if self.spectral_norm:
+            keys = [k[:-len(".weight_orig")] for k in self.opt_D.names if k.endswith(".weight_orig")]
+            self.sn = SpectralNorm(self.ctxD, keys, self.opt_D.params, self.opt_D.grads, self.d_buffers)
+        self.D = MultiscaleDiscriminatorNet(self.ctxD, self.opt_D.params, self.opt_D.grads, discriminator.ndf, discriminator.n_layers, K, self.sn)
+        self.D32 = self.D if self.ctx32 is self.ctxD else MultiscaleDiscriminatorNet(self.ctx32, self.opt_D.params, self.opt_D.grads,
+                                                                                    discriminator.ndf, discriminator.n_layers, K, self.sn)
         self.nce_layers = feature_layers_present(config["patchnce"]["nce_layers"], nb) if lw["patchnce"] > 0 else []
         self.P = config["patchnce"]["num_patches"]
         # Identity warm-up (identity weight > 0): G(photos) and G(monets) are two full passes through the same weights, and
@@ -479,14 +489,17 @@ class CutTrainer:
         # after the warm-up the generator pass holds the photos only.  `merge_identity_pass: false` keeps three separate passes.
         self.merge_identity = bool(config.get("merge_identity_pass", True))
         self.p2 = self.G.new_pass(B, S, S, last_layer=max(self.nce_layers)) if self.nce_layers else None
-        self.d_rf, self.d_fake = self.D.new_pass(2 * B, S, S), self.D.new_pass(B, S, S)   # D-step pass (real | fake), G-step pass
+        # D-step pass: real | fake as one pass of 2B images; with spectral norm the halves are separate forwards (each its own power
+        # iteration, train_cutpp.py:238-240) that reuse one pass of B images.  Then the G-step pass.
+        self.d_rf = self.D.new_pass(B if self.sn is not None else 2 * B, S, S)
+        self.d_fake = self.D.new_pass(B, S, S)
         self.d_r1 = self.D32.new_pass(B, S, S)
 
         f32 = self.ctx.f32
         self.both = torch.zeros(2 * B, 3, S, S, dtype=torch.float32, device=self.device)   # photos | monets, one staging tensor
         self.photos, self.monets = self.both[:B], self.both[B:]
         self.fake_out = torch.zeros_like(self.photos)
-        self.losses = f32(16)
+        self.losses = f32(max(16, len(LOSS_SLOTS) + len(SCALE_SLOTS) * (K - 1)))
         self.nce_hw = [(S >> (0 if i == 0 else 1 if i == 1 else 2 if i < 3 + nb else 1 if i == 3 + nb else 0)) ** 2 for i in self.nce_layers]
         # every per-step random draw (3 DiffAugment tables, PatchNCE ids) lives in ONE device block filled by ONE non-blocking copy
         # from pinned memory: seven small pageable copies would each stall the host until the stream drains (measured: 7 idle gaps
@@ -508,9 +521,14 @@ class CutTrainer:
         self._use_mode(self.merge_identity and identity_weight_at(0, config) > 0)
 
     # ------------------------------------------------------------------ program construction
-    def _slot(self, name) -> torch.Tensor:
-        i = LOSS_SLOTS[name]
+    def _slot(self, name, scale: int = 0) -> torch.Tensor:
+        """Loss slot; d_real / d_fake / g_adv have one per discriminator scale (gan_patch_loss overwrites its slot)."""
+        i = LOSS_SLOTS[name] if scale == 0 else len(LOSS_SLOTS) + len(SCALE_SLOTS) * (scale - 1) + SCALE_SLOTS.index(name)
         return self.losses[i:i + 1]
+
+    def _scale_sum(self, v, name) -> float:
+        return sum(v[LOSS_SLOTS[name] if s == 0 else len(LOSS_SLOTS) + len(SCALE_SLOTS) * (s - 1) + SCALE_SLOTS.index(name)]
+                   for s in range(self.num_scales))
 
     def _aug_fwd(self, src: View, dst: View, prm) -> list:
         ops = self.opsD                          # DiffAugment feeds the discriminator: its stream
@@ -567,16 +585,28 @@ class CutTrainer:
         prog_gfwd.add(ops.nchw_to_view(self.photos, 3, photos_v, HALO_ZERO))
 
         # ---- D step (train_cutpp.py:231-254): D(aug(photos)) and D(aug(fake.detach())) as ONE pass over 2B images (the
-        # discriminator has no cross-sample statistics); the two hinge terms read / write their halves of the logits
+        # discriminator has no cross-sample statistics); the two hinge terms read / write their halves of the logits.  Every scale's
+        # terms carry the reference's 1 / num_scales (adv_hinge.py).
         pd = Program("D-step")
-        drf = self.d_rf
-        pd.add(self._aug_fwd(photos_v, drf.x.batch(0, B), self.prm["real"]))
-        pd.add(self._aug_fwd(fake, drf.x.batch(B, B), self.prm["fake_d"]))
-        pd.add(drf.fwd_program())
-        gl = drf.grad_logits_view()
-        pd.add(self.opsD.patch_loss(drf.logits.batch(0, B), 0, 0.0, 0.5, self._slot("d_real"), gl.batch(0, B)))
-        pd.add(self.opsD.patch_loss(drf.logits.batch(B, B), 1, 0.0, 0.5, self._slot("d_fake"), gl.batch(B, B)))
-        pd.add(drf.bwd_program(gl, wgrad=True, accumulate=False))
+        drf, K = self.d_rf, self.num_scales
+        gls = drf.grad_logits_views()
+        if self.sn is None:
+            pd.add(self._aug_fwd(photos_v, drf.x.batch(0, B), self.prm["real"]))
+            pd.add(self._aug_fwd(fake, drf.x.batch(B, B), self.prm["fake_d"]))
+            pd.add(drf.fwd_program())
+            for s, (lg, gl) in enumerate(zip(drf.logits, gls)):
+                pd.add(self.opsD.patch_loss(lg.batch(0, B), 0, 0.0, 0.5 / K, self._slot("d_real", s), gl.batch(0, B)))
+                pd.add(self.opsD.patch_loss(lg.batch(B, B), 1, 0.0, 0.5 / K, self._slot("d_fake", s), gl.batch(B, B)))
+            pd.add(drf.bwd_program(gls, wgrad=True, accumulate=False))
+        else:
+            # spectral norm: real forward -> real backward -> fake forward -> fake backward.  Neither backward needs the other half's
+            # forward, so the gradients are the merged pass's, and the two halves share one pass and one set of operand copies.
+            for half, (src, key, mode, name) in enumerate(((photos_v, "real", 0, "d_real"), (fake, "fake_d", 1, "d_fake"))):
+                pd.add(self._aug_fwd(src, drf.x, self.prm[key]))
+                pd.add(drf.fwd_program())
+                for s, (lg, gl) in enumerate(zip(drf.logits, gls)):
+                    pd.add(self.opsD.patch_loss(lg, mode, 0.0, 0.5 / K, self._slot(name, s), gl))
+                pd.add(drf.bwd_program(gls, wgrad=True, accumulate=half == 1))
 
         # ---- G step (train_cutpp.py:266-308).  Two programs: `prog_g_features` -- the PatchNCE target-feature forward G.encode(fake)
         # and the PatchNCE losses -- does not touch the discriminator, so it runs while the discriminator's gradient all-reduce is
@@ -608,9 +638,10 @@ class CutTrainer:
         dp = self.d_fake
         pa.add(self._aug_fwd(fake, dp.x, self.prm["fake_g"]))
         pa.add(dp.fwd_program())
-        gl = dp.grad_logits_view()
-        pa.add(self.opsD.patch_loss(dp.logits, 2, 0.0, lw["adv"], self._slot("g_adv"), gl))
-        pa.add(dp.bwd_program(gl, wgrad=False, need_input_grad=True))
+        gls = dp.grad_logits_views()
+        for s, (lg, gl) in enumerate(zip(dp.logits, gls)):
+            pa.add(self.opsD.patch_loss(lg, 2, 0.0, lw["adv"] / K, self._slot("g_adv", s), gl))
+        pa.add(dp.bwd_program(gls, wgrad=False, need_input_grad=True))
         if self.aug is not None:
             g_adv_img = self.ctxD.view(B, S, S, 8, 0)
             pa.add(self.opsD.diffaug_bwd(dp.g_input, 3, self.prm["fake_g"], g_adv_img, self.ctxD.scratch("aug_ws", B + 16)))
@@ -660,17 +691,17 @@ class CutTrainer:
             pr = Program("R1-body")
             rp, dnet = self.d_r1, self.D32
             pr.add(ops.nchw_to_view(self.photos, 3, rp.x, HALO_ZERO))
-            pr.add(rp.fwd_program())
             scale = cfg["r1"]["gamma"] * cfg["r1"]["every"]
-            pr.add(rp.r1_program(scale, self._slot("r1"), self._slot("scratch")))
+            pr.add(rp.r1_program(scale, self._slot("r1"), self._slot("scratch")))     # forward (+ power iteration) and R1, every scale
             skip = []
-            for li, conv in enumerate(dnet.convs):   # biases: zero grad except the last one, whose grad is None (skipped)
-                if conv.grad_b is None:
-                    continue
-                if li == dnet.nconv - 1:
-                    skip.append([k for k, v in self.opt_D.grads.items() if v is conv.grad_b][0])
-                else:
-                    pr.add(ops.fill(conv.grad_b, 0.0))
+            for net in dnet.nets:
+                for li, conv in enumerate(net.convs):   # biases: zero grad except each scale's last one, whose grad is None (skipped)
+                    if conv.grad_b is None:
+                        continue
+                    if li == net.nconv - 1:
+                        skip.append([k for k, v in self.opt_D.grads.items() if v is conv.grad_b][0])
+                    else:
+                        pr.add(ops.fill(conv.grad_b, 0.0))
             self._r1_body, self._r1_skip = pr, skip
         self.prog_d_update = Program("D-update")
         self.prog_d_update.add(self.opt_D.step_op(cfg.get("grad_clip_d", 10.0), gs))
@@ -685,6 +716,8 @@ class CutTrainer:
         self.prog_g_update = Program("G-update")
         self.prog_g_update.add(self.opt_G.step_op(cfg.get("grad_clip_g", 10.0), gs))
         self.prog_g_update.add(self.G.repack_program())
+        self.D.refresh_pack()                   # spectral norm: the pack every D forward runs covers the copies planned so far
+        self.D32.refresh_pack()
 
     # ------------------------------------------------------------------ per-step randomness
     def sample_randomness(self, generator: Optional[torch.Generator] = None, nce_generator: Optional[torch.Generator] = None) -> dict:
@@ -875,7 +908,7 @@ class CutTrainer:
             # every step's dict is still delivered and NaN-checked, one call late, and the host never idles the GPU (-2 % step time)
             prev = self._collect_losses()
             if self._pinned is None:
-                self._pinned = [torch.zeros(16, dtype=torch.float32, pin_memory=self.device.type == "cuda") for _ in range(2)]
+                self._pinned = [torch.zeros(self.losses.numel(), dtype=torch.float32, pin_memory=self.device.type == "cuda") for _ in range(2)]
                 self._events = [torch.cuda.Event() if self.device.type == "cuda" else None for _ in range(2)]
             i = step & 1
             self._pinned[i].copy_(self.losses, non_blocking=True)
@@ -890,7 +923,9 @@ class CutTrainer:
     def _loss_dict(self, v, meta) -> dict:
         step, idw, do_r1 = meta
         lw = self.config["loss_weights"]
-        out = {"d_loss": v[0] + v[1], "g_adv": v[3] / lw["adv"] if lw["adv"] != 0 else 0.0, "nce": v[4] / lw["patchnce"] if lw["patchnce"] > 0 else 0.0,
+        d_loss = self._scale_sum(v, "d_real") + self._scale_sum(v, "d_fake")
+        g_adv = self._scale_sum(v, "g_adv")
+        out = {"d_loss": d_loss, "g_adv": g_adv / lw["adv"] if lw["adv"] != 0 else 0.0, "nce": v[4] / lw["patchnce"] if lw["patchnce"] > 0 else 0.0,
                "identity": v[5] if idw > 0 else 0.0, "r1": v[2] if do_r1 else 0.0, "identity_weight": idw}
         out["g_loss"] = lw["adv"] * out["g_adv"] + lw["patchnce"] * out["nce"] + idw * out["identity"]
         if any(not math.isfinite(x) for k, x in out.items() if k != "identity_weight"):
@@ -935,12 +970,12 @@ class CutTrainer:
         """Resume (train_cutpp.py:372-397): weights, Adam moments and step counts, EMA shadow; then refresh the operand copies.
         Files are read with weights_only=True (tensors and plain containers only)."""
         ck = path_or_dict if isinstance(path_or_dict, dict) else torch.load(path_or_dict, map_location=self.device, weights_only=True)
-        for mod, opt, key in ((self.generator, self.opt_G, "generator"), (self.discriminator, self.opt_D, "discriminator")):
-            missing = set(opt.params) ^ set(ck[key])
+        for opt, bufs, key in ((self.opt_G, {}, "generator"), (self.opt_D, self.d_buffers, "discriminator")):
+            missing = (set(opt.params) | set(bufs)) ^ set(ck[key])
             if missing:
                 raise KeyError(f"checkpoint['{key}'] keys differ from the model's: {sorted(missing)[:4]} ...")
             for k, v in ck[key].items():
-                opt.params[k].copy_(v)
+                (opt.params[k] if k in opt.params else bufs[k]).copy_(v)
         if "opt_G" in ck:
             _load_adam_state_dict(self.opt_G, ck["opt_G"])
         if "opt_D" in ck:

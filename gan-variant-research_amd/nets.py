@@ -504,9 +504,9 @@ class DPass:
         return self.net.gbuf("g_logits", self.B, lg.H, lg.W, lg.C, 2)
 
     def bwd_program(self, g_logits: View, wgrad: bool = True, accumulate: bool = False, need_input_grad: bool = False,
-                    keep: Optional[list] = None, bias_grads: bool = True) -> Program:
+                    keep: Optional[list] = None, bias_grads: bool = True, bias_accumulate: Optional[bool] = None) -> Program:
         """Backward from dL/dlogits.  keep: if a list, the per-layer output gradients (delta_i) are appended to it and
-        live in dedicated buffers (R1's second-order pass needs them)."""
+        live in dedicated buffers (R1's second-order pass needs them).  bias_accumulate: for the bias gradients (default: accumulate)."""
         net, ops, B = self.net, self.net.ctx.ops, self.B
         prog = Program("D.bwd")
         dy = g_logits
@@ -520,7 +520,8 @@ class DPass:
             if keep is not None:
                 keep.append(dy)
             if wgrad:
-                prog.add(conv.wgrad(xin, dy, accumulate, bias_too=bias_grads))
+                kw = {} if bias_accumulate is None else {"bias_accumulate": bias_accumulate}
+                prog.add(conv.wgrad(xin, dy, accumulate, bias_too=bias_grads, **kw))
             if li == 0:
                 if need_input_grad:
                     self.g_input = net.gbuf("g_dx", B, self.H, self.W, self.x.C, 0)
@@ -540,3 +541,166 @@ class DPass:
                 prog.add(ops.in_bwd(self.raw[li - 1], self.stats[li - 1], ACT_LRELU, g_a, False, None, nxt, net.in_ws(B, a.C)))
             dy = nxt
         return prog
+
+
+# ------------------------------------------------------------------------------------------------ multiscale / spectral norm
+SN_EPS = 1e-12          # torch.nn.utils.spectral_norm default
+
+
+class SpectralNorm:
+    """(u, v, sigma) of every spectral-norm convolution of a discriminator, all scales (discriminator_patchgan.py:21-23), for the fused
+    trainer: one gan_spectral_norm_batch_fwd per D forward (a power iteration, sigma and the snapshots its backward reads) and one
+    gan_spectral_norm_batch_bwd per weight-gradient pass.  The convolutions' weight gradients (dL/dW_sn) land in the per-layer
+    scratch `G`; the backward turns them into dL/dweight_orig in the optimiser's block.  W_sn itself is never formed: the operand
+    copies are packed from weight_orig with scale = sigma (ConvLayer.pack_scale)."""
+
+    def __init__(self, ctx: Ctx, keys: Sequence[str], params: Dict[str, torch.Tensor], grads: Dict[str, torch.Tensor],
+                 buffers: Dict[str, torch.Tensor]):
+        """keys: convolution prefixes; params / grads hold `<key>.weight_orig`, buffers `<key>.weight_u` / `<key>.weight_v` (device
+        fp32, updated in place)."""
+        self.ctx, self.keys = ctx, list(keys)
+        ops = ctx.ops
+        self.entries, self.G, self.sigma = [], {}, {}
+        for k in self.keys:
+            W = params[k + ".weight_orig"]
+            h, w = W.shape[0], W.numel() // W.shape[0]
+            e = {"W": W, "u": buffers[k + ".weight_u"], "v": buffers[k + ".weight_v"], "sigma": ctx.f32(1, 1.0), "u_snap": ctx.f32(h),
+                 "v_snap": ctx.f32(w), "G": torch.zeros_like(W), "dW": grads[k + ".weight_orig"],
+                 "ws": ctx.f32(ops.spectral_norm_batch_ws_floats(h, w))}
+            self.entries.append(e)
+            self.G[k], self.sigma[k] = e["G"], e["sigma"]
+        self._fwd = ops.spectral_norm_batch_fwd(self.entries, True, SN_EPS)
+        self._bwd = {a: ops.spectral_norm_batch_bwd(self.entries, a) for a in (False, True)}
+
+    def fwd_op(self):
+        return self._fwd
+
+    def bwd_op(self, accumulate: bool):
+        return self._bwd[bool(accumulate)]
+
+
+class MultiscaleDiscriminatorNet:
+    """MultiscaleDiscriminator (discriminator_patchgan.py:75-116): `num_scales` CUT PatchGAN nets (keys discriminators.{s}.model.{2i}),
+    scale s on the input average-pooled s times, optionally spectral-normalised (`sn`).  With one scale and no spectral norm every
+    program is the single DiscriminatorNet's."""
+
+    def __init__(self, ctx: Ctx, params: Dict[str, torch.Tensor], grads: Dict[str, torch.Tensor], ndf=64, n_layers=3, num_scales=1,
+                 sn: Optional[SpectralNorm] = None, in_c=3):
+        self.ctx, self.sn, self.num_scales, self.in_c = ctx, sn, num_scales, in_c
+        if sn is not None:         # the convolutions read weight_orig (packed / sigma) and write dL/dW_sn into the scratch
+            params, grads = dict(params), dict(grads)
+            for k in sn.keys:
+                params[k + ".weight"], grads[k + ".weight"] = params[k + ".weight_orig"], sn.G[k]
+        self.nets = [DiscriminatorNet(ctx, params, grads, "cut", f"discriminators.{s}.model.", ndf, n_layers, in_c) for s in range(num_scales)]
+        self.nconv = self.nets[0].nconv
+        if sn is not None:
+            for s, net in enumerate(self.nets):
+                for i, conv in enumerate(net.convs):
+                    conv.pack_scale = sn.sigma[f"discriminators.{s}.model.{2 * i}"]
+        self._pack = None
+
+    @property
+    def convs(self) -> List[ConvLayer]:
+        return [c for net in self.nets for c in net.convs]
+
+    def _pack_all(self):
+        ops = [op for net in self.nets for layer in net.layers for op in layer.repack_ops()]
+        return self.ctx.ops.pack_weight_batch([op.pack_args for op in ops])
+
+    def repack_program(self) -> Program:
+        """Operand copies after an optimiser step: one batched launch.  A spectral-norm network has none here: its copies depend on the
+        sigma of the next forward, which packs them itself (pack_op)."""
+        if self.sn is not None:
+            return Program("repack")
+        if len(self.nets) == 1:
+            return self.nets[0].repack_program()
+        prog = Program("repack")
+        prog.add(self._pack_all())
+        return prog
+
+    def refresh_pack(self):
+        """(Re)builds the forward's pack launch over every operand copy planned so far; call after planning new passes."""
+        if self.sn is not None:
+            self._pack = self._pack_all()
+
+    def pack_op(self):
+        return lambda: self._pack()
+
+    def new_pass(self, B, H, W) -> "MSDPass":
+        return MSDPass(self, B, H, W)
+
+
+class MSDPass:
+    """Buffers of one multiscale discriminator forward (+ backward): one DPass per scale."""
+
+    def __init__(self, net: MultiscaleDiscriminatorNet, B, H, W):
+        self.net, self.B, self.H, self.W = net, B, H, W
+        self.dps = []
+        for n in net.nets:
+            self.dps.append(n.new_pass(B, H, W))
+            H, W = (H - 1) // 2 + 1, (W - 1) // 2 + 1       # AvgPool2d(3, 2, 1)
+        self.x = self.dps[0].x
+        self.logits = [dp.logits for dp in self.dps]
+        self.g_input = None
+
+    def fwd_program(self) -> Program:
+        """With spectral norm: one power iteration over every scale's convolutions, the pack of this network's operand copies with
+        scale = sigma, then the scales."""
+        ops = self.net.ctx.ops
+        prog = Program("MSD.fwd")
+        if self.net.sn is not None:
+            prog.add(self.net.sn.fwd_op())
+            prog.add(self.net.pack_op())
+        for s, dp in enumerate(self.dps):
+            if s > 0:
+                prog.add(ops.avgpool_fwd(self.dps[s - 1].x, dp.x))
+            prog.add(dp.fwd_program())
+        return prog
+
+    def grad_logits_views(self) -> List[View]:
+        return [dp.grad_logits_view() for dp in self.dps]
+
+    def bwd_program(self, g_logits: Sequence[View], wgrad: bool = True, accumulate: bool = False, need_input_grad: bool = False) -> Program:
+        """Per-scale backward; input gradients summed down to scale 0 through the pools (self.g_input).  With spectral norm the
+        weight gradients (dL/dW_sn) overwrite the scratch and one batched backward adds / writes dL/dweight_orig; the biases
+        take theirs directly."""
+        ops, sn = self.net.ctx.ops, self.net.sn
+        prog = Program("MSD.bwd")
+        for dp, gl in zip(self.dps, g_logits):
+            if sn is None:
+                prog.add(dp.bwd_program(gl, wgrad=wgrad, accumulate=accumulate, need_input_grad=need_input_grad))
+            else:
+                prog.add(dp.bwd_program(gl, wgrad=wgrad, accumulate=False, need_input_grad=need_input_grad, bias_accumulate=accumulate))
+        if need_input_grad:
+            for i in range(len(self.dps) - 2, -1, -1):      # dL/dx_i += pool^T dL/dx_{i+1}
+                prog.add(ops.avgpool_bwd(self.dps[i + 1].g_input, self.dps[i].g_input, True))
+            self.g_input = self.dps[0].g_input
+        if wgrad and sn is not None:
+            prog.add(sn.bwd_op(accumulate))
+        return prog
+
+    def r1_program(self, scale: float, loss: torch.Tensor, scratch: torch.Tensor) -> Program:
+        """R1 over every scale after this pass's input is in place (autograd.py, _r1_slot): the forward (with its power iteration
+        and pack), the first-order half at every scale, the input gradients pooled back to scale 0 and reduced, then each scale's
+        second-order half seeded with the total u_0 pooled down to its resolution; with spectral norm one batched backward."""
+        net, ctx, ops = self.net, self.net.ctx, self.net.ctx.ops
+        if len(self.dps) == 1 and net.sn is None:
+            pr = Program("R1")
+            pr.add(self.dps[0].fwd_program())
+            pr.add(self.dps[0].r1_program(scale, loss, scratch))
+            return pr
+        pr = Program("R1.multiscale")
+        pr.add(self.fwd_program())
+        for dp in self.dps:
+            pr.add(dp.r1_first(scratch))
+        for i in range(len(self.dps) - 2, -1, -1):
+            pr.add(ops.avgpool_bwd(self.dps[i + 1].g_input, self.dps[i].g_input, True))
+        us = [ctx.view(self.B, dp.H, dp.W, dp.x.C, 1) for dp in self.dps]
+        pr.add(ops.r1_reduce(self.dps[0].g_input, net.in_c, scale, loss, us[0], ctx.scratch("r1_ws", 1024)))
+        for i, dp in enumerate(self.dps):
+            if i > 0:
+                pr.add(ops.avgpool_fwd(us[i - 1], us[i]))
+            pr.add(dp.r1_second(us[i]))
+        if net.sn is not None:
+            pr.add(net.sn.bwd_op(False))
+        return pr

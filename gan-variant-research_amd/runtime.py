@@ -376,11 +376,13 @@ class HipOps:
     def pack_weight(self, src, dst, dtype, Nw, ntaps, Cin, N_real, C_real, swap, I2, KK, khw, layout=0, scale=None) -> Op:
         """One operand copy.  dtype FP8 (e4m3, needs `scale`: a device float the batch launch fills with max|W| / 448) exists only in
         the batched form: the returned op then only carries its arguments for pack_weight_batch."""
-        if dtype == FP8:
-            assert scale is not None and layout == 1
+        if dtype == FP8 or scale is not None:
+            # fp8: scale = max|W| / 448, filled by the batch launch; bf16 / fp32: a device float the copy is divided by (spectral norm's
+            # sigma).  Both exist only in the batched form.
+            assert dtype != FP8 or layout == 1
 
             def op():
-                raise _lib.GanError("fp8 operand copies are packed by pack_weight_batch")
+                raise _lib.GanError("scaled operand copies are packed by pack_weight_batch")
         else:
             op = self._call("gan_pack_weight", self._p(src), self._p(dst), dtype, Nw, ntaps, Cin, N_real, C_real, int(swap), I2, KK,
                             self._p(khw), int(layout), self._s())
@@ -541,6 +543,45 @@ class HipOps:
         assert u.numel() == h and v.numel() == w and dW.numel() == G.numel() and ws.numel() >= self.spectral_norm_ws_floats(h, w)
         return self._call("gan_spectral_norm_bwd", self._p(G), self._p(Wsn), self._p(u), self._p(v), self._p(sigma), h, w, self._p(dW),
                           self._p(ws), self._s())
+
+    def spectral_norm_batch_ws_floats(self, h, w) -> int:
+        return int(_lib.load().gan_spectral_norm_batch_ws_floats(h, w))
+
+    _SN_FIELDS = ("W", "u", "v", "sigma", "u_snap", "v_snap", "G", "dW", "ws")
+
+    def _sn_table(self, entries: Sequence[dict]):
+        """entries: dicts of fp32 contiguous tensors W (weight_orig, any shape with h = shape[0]), u [h], v [w], sigma [1], u_snap [h],
+        v_snap [w], ws (>= spectral_norm_batch_ws_floats) and, for the backward, G and dW (W's size).  -> (device table, total blocks)."""
+        arr = (_lib.GanSnDesc * len(entries))()
+        first = 0
+        for d, e in zip(arr, entries):
+            W = e["W"]
+            h, w = W.shape[0], W.numel() // W.shape[0]
+            for k in self._SN_FIELDS:
+                t = e.get(k)
+                assert t is not None or k in ("G", "dW"), k
+                if t is not None:
+                    assert t.dtype == torch.float32 and t.is_contiguous() and t.device == W.device, k
+                    setattr(d, k, t.data_ptr())
+            assert e["u"].numel() == h == e["u_snap"].numel() and e["v"].numel() == w == e["v_snap"].numel() and e["sigma"].numel() >= 1
+            assert e["ws"].numel() >= self.spectral_norm_batch_ws_floats(h, w)
+            assert all(e.get(k) is None or e[k].numel() == W.numel() for k in ("G", "dW"))
+            d.h, d.w = h, w
+            d.nblocks = int(_lib.load().gan_spectral_norm_batch_blocks(h, w))
+            d.first_block, first = first, first + d.nblocks
+        self._keep.append(list(entries))
+        return torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(self.device), first
+
+    def spectral_norm_batch_fwd(self, entries: Sequence[dict], power_iter: bool, eps: float) -> Op:
+        """One gan_spectral_norm_batch_fwd over every entry (see _sn_table): power iteration (u, v in place), sigma, snapshots."""
+        table, total = self._sn_table(entries)
+        return self._call("gan_spectral_norm_batch_fwd", self._p(table), len(entries), total, int(power_iter), C.c_float(eps), self._s())
+
+    def spectral_norm_batch_bwd(self, entries: Sequence[dict], accumulate: bool) -> Op:
+        """dW (+)= (G - (<G, W> / sigma) u_snap v_snap^T) / sigma for every entry, one gan_spectral_norm_batch_bwd."""
+        assert all(e.get("G") is not None and e.get("dW") is not None for e in entries)
+        table, total = self._sn_table(entries)
+        return self._call("gan_spectral_norm_batch_bwd", self._p(table), len(entries), total, int(accumulate), self._s())
 
     def avgpool_fwd(self, x: View, y: View) -> Op:
         return self._call("gan_avgpool_fwd", self._v(x), self._v(y), self._s())

@@ -169,7 +169,9 @@ int gan_pack_weight(const float* src, void* dst, int dtype, int Nw, int ntaps, i
 typedef struct gan_pack_desc {
   const float* src; void* dst; const int32_t* khw;
   int32_t dtype, Nw, ntaps, Cin, N_real, C_real, swap, I2, KK, layout, first_block, nblocks;
-  float* scale;                  /* dtype GAN_FP8: device float, dst = e4m3(src / *scale); written by gan_weight_scale_batch; else unused */
+  float* scale;                  /* dtype GAN_FP8: device float, dst = e4m3(src / *scale); written by gan_weight_scale_batch.  GAN_BF16 /
+                                    GAN_F32: NULL, or a device float and dst = src / *scale (spectral norm: scale = sigma, so the
+                                    copy is W_sn's, packed from weight_orig; discriminator_patchgan.py:21-23) */
 } gan_pack_desc;
 int gan_pack_weight_batch(const gan_pack_desc* descs, int n, int total_blocks, void* stream);
 /* For every descriptor with dtype GAN_FP8: *scale = max|src| / 448 over the whole master weight ((swap ? C_real : N_real) * I2 * KK
@@ -268,6 +270,29 @@ int gan_spectral_norm_fwd(const float* W, int h, int w, float* u, float* v, int 
                           float* ws, void* stream);
 int gan_spectral_norm_bwd(const float* G, const float* Wsn, const float* u, const float* v, const float* sigma, int h, int w,
                           float* dW, float* ws, void* stream);
+/* Batched spectral norm: every spectral-norm convolution of a discriminator (all scales) in a fixed number of launches, for the
+ * fused trainer.  `descs` is a DEVICE array of n descriptors; each covers gan_spectral_norm_batch_blocks(h, w) blocks, first_block =
+ * running sum of nblocks, total_blocks = their sum.
+ *   fwd (3 launches; 2 without power_iter): if power_iter, v <- normalize(W^T u), u <- normalize(W v) in place (normalize(x) =
+ *        x / max(||x||, eps)); then *sigma = u . (W v) and u_snap, v_snap <- (u, v).  W_sn is not written: the operand copies are
+ *        packed from W with gan_pack_desc.scale = sigma.  Semantics of gan_spectral_norm_fwd.
+ *   bwd (2 launches): dW (+)= (G - (<G, W> / sigma) u_snap v_snap^T) / sigma, G = dL/dW_sn as the weight-gradient kernels leave it;
+ *        accumulate lets the real and fake halves of a D-step add into one weight_orig gradient.
+ * Reductions run in a fixed order without atomics: repeated calls are bit-identical. */
+typedef struct gan_sn_desc {
+  const float* W;                /* weight_orig as an h x w row-major matrix */
+  float* u; float* v;            /* the module's weight_u [h], weight_v [w] */
+  float* sigma;                  /* [1] */
+  float* u_snap; float* v_snap;  /* [h], [w]: the (u, v) of the last forward, read by the backward */
+  const float* G;                /* bwd: dL/dW_sn [h x w] */
+  float* dW;                     /* bwd: dL/dweight_orig [h x w] */
+  float* ws;                     /* fp32 >= gan_spectral_norm_batch_ws_floats(h, w), private to the descriptor */
+  int32_t h, w, first_block, nblocks;
+} gan_sn_desc;
+int64_t gan_spectral_norm_batch_ws_floats(int h, int w);
+int gan_spectral_norm_batch_blocks(int h, int w);
+int gan_spectral_norm_batch_fwd(const gan_sn_desc* descs, int n, int total_blocks, int power_iter, float eps, void* stream);
+int gan_spectral_norm_batch_bwd(const gan_sn_desc* descs, int n, int total_blocks, int accumulate, void* stream);
 
 /* ---- DiffAugment (GAN_Variant1/training/diffaugment.py:6-60,94-106), per-sample parameters injected.
  *      prm = device fp32 [B][12]: brightness add, saturation factor, contrast factor, tx, ty,

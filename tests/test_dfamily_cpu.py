@@ -1,0 +1,264 @@
+"""The fused CutTrainer with the reference constructors' discriminator family: several scales (MultiscaleDiscriminator, num_scales)
+and spectral norm (use_spectral_norm).  CPU: the kernels are the emulator's statements (tests/emulator_dfamily.py); the golden step
+is the reference's own train_step with a 2-scale spectral-norm discriminator (tests/golden/cut_optional.npz, step_sn2.*)."""
+import os
+import socket
+
+import numpy as np
+import pytest
+import torch
+import torch.distributed as dist
+import torch.multiprocessing as mp
+
+from gan_variant_research_amd import autograd as AG, cut as C
+from oracle import cut_ref
+from tests import cases
+from tests.emulator import EmuOps
+from tests.emulator_dfamily import DFamilyEmuOps
+
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "cut_optional.npz")
+
+
+def dfamily_config(num_scales, sn, small_g=False):
+    cfg = cases.small_config()
+    cfg["diffaugment"]["enable"] = True
+    cfg["model"]["discriminator"]["num_scales"] = num_scales
+    cfg["model"]["discriminator"]["use_spectral_norm"] = sn
+    if small_g:                       # the discriminator is what these cases exercise: a narrow, shallow generator keeps them fast
+        cfg["model"]["generator"]["ngf"], cfg["model"]["generator"]["n_blocks"] = 16, 3
+    return cfg
+
+
+def _inputs(B, S):
+    g = torch.Generator().manual_seed(1234)
+    return torch.rand(B, 3, S, S, generator=g) * 2 - 1, torch.rand(B, 3, S, S, generator=g) * 2 - 1
+
+
+def fused_golden_sn2_case(device, ops, tol0, tol1, amp=False):
+    """Fused trainer, 64x64, B=2, DiffAugment on, 2 scales + spectral norm, the reference's draws injected, against step_sn2 (the tolerances
+    of test_autograd_bridge.optional_step_cases); also weight_u of scale 1's last convolution after two steps (four power iterations
+    per step on R1 steps, three otherwise, in the reference's order)."""
+    g = np.load(GOLDEN)
+    cfg = dfamily_config(2, True)
+    B, S = 2, 64
+    C.set_seed(42)
+    gen, disc = C.build_models(cfg, "cpu")
+    tr = C.CutTrainer(gen, disc, cfg, B, S, device=device, amp=amp, ops=ops)
+    photos, monets = _inputs(B, S)
+    for step in range(2):
+        torch.manual_seed(9000 + step)
+        rnd = cut_ref.sample_step_randomness(B, S, S, use_aug=True)
+        got = tr.train_step(step, photos.to(device), monets.to(device), rnd)
+        for k, v in got.items():
+            want = float(g[f"step_sn2.step{step}.{k}"])
+            atol = max(tol0 * 0.1 if step == 0 else 2e-4, 1e-3 if k == "g_adv" else 0.0)
+            np.testing.assert_allclose(v, want, rtol=tol0 if step == 0 else tol1, atol=atol, err_msg=f"step{step} {k}")
+    tr._device_sync()
+    u = disc.state_dict()["discriminators.1.model.6.weight_u"].cpu()
+    want = torch.from_numpy(g["step_sn2.u_after"])
+    err = float((u - want).abs().max() / want.abs().max())
+    assert err < 5e-3, f"weight_u after two steps: {err:.3e}"
+    return tr
+
+
+def test_fused_trainer_sn2_golden_on_emulator():
+    torch.set_num_threads(4)
+    fused_golden_sn2_case("cpu", DFamilyEmuOps(), 1e-4, 2e-3)
+
+
+def fused_vs_module_case(device, num_scales, sn, S, nsteps, make_ops, amp=False, loss_rtol=2e-3, loss_atol=2e-4, ptol=1.3e-3, uv_tol=1e-3):
+    """The fused trainer and module_step.train_step (per-layer spectral-norm kernels, autograd bridge) over `nsteps` steps from the same
+    initialisation and draws: losses, every discriminator parameter and buffer."""
+    from gan_variant_research_amd import losses as L, module_step as MS, training as T
+    cfg = dfamily_config(num_scales, sn, small_g=True)
+    B = 2
+    C.set_seed(42)
+    gen, disc = C.build_models(cfg, "cpu")
+    tr = C.CutTrainer(gen, disc, cfg, B, S, device=device, amp=amp, ops=make_ops())
+    C.set_seed(42)
+    gen2, disc2 = C.build_models(cfg, "cpu")
+    gen2, disc2 = gen2.to(device), disc2.to(device)
+    if amp:
+        from gan_variant_research_amd._lib import BF16
+        gen2.compute_dtype = disc2.compute_dtype = BF16
+    opt_G, opt_D = T.get_optimizer(gen2, cfg["optim"]["G"]), T.get_optimizer(disc2, cfg["optim"]["D"])
+    ema, ampc, aug = T.EMA(gen2, cfg["ema"]["decay"], optimizer=opt_G), T.AMPContext(False), L.DiffAugment(cfg["diffaugment"]["policy"])
+    photos, monets = _inputs(B, S)
+    photos, monets = photos.to(device), monets.to(device)
+    for step in range(nsteps):
+        torch.manual_seed(9000 + step)
+        rnd = cut_ref.sample_step_randomness(B, S, S, use_aug=True, layer_ids=cfg["patchnce"]["nce_layers"])
+        rnd = {k: (v[:len(tr.nce_hw)] if k == "nce_ids" else v) for k, v in rnd.items()}
+        a = tr.train_step(step, photos, monets, rnd)
+        rnd_dev = {k: ([t.to(device) for t in v] if k == "nce_ids" else v) for k, v in rnd.items()}
+        b = MS.train_step(step, photos, monets, gen2, disc2, opt_G, opt_D, ema, ampc, aug, cfg, torch.device(device), rnd=rnd_dev)
+        for k in a:
+            np.testing.assert_allclose(a[k], b[k], rtol=loss_rtol, atol=1e-3 if k == "g_adv" else loss_atol, err_msg=f"step {step} {k}")
+    tr._device_sync()
+    sd1, sd2 = disc.state_dict(), disc2.state_dict()
+    assert list(sd1) == list(sd2)
+    for k in sd1:
+        tol = ptol
+        if k.endswith(("weight_u", "weight_v")):
+            # u, v are power iterations on weight_orig, which Adam's sign-like first updates may move by ptol where a gradient is rounding
+            # noise: v of the one-row last layer is weight_orig / ||weight_orig|| itself
+            tol = uv_tol * float(sd2[k].abs().max()) + ptol / float(sd2[k[:-len("u")] + "orig"].norm())
+        err = float((sd1[k].float().cpu() - sd2[k].float().cpu()).abs().max())
+        assert err < tol, f"{k}: {err:.3e}"
+    return tr
+
+
+@pytest.mark.parametrize("num_scales,sn,S", [(3, False, 96), (2, True, 64)])
+def test_fused_trainer_matches_module_step_dfamily(monkeypatch, num_scales, sn, S):
+    from gan_variant_research_amd import losses as L
+    monkeypatch.setattr(AG, "_OPS_FACTORY", lambda device: EmuOps())
+    monkeypatch.setattr(L, "_PLANS", {})
+    torch.set_num_threads(4)
+    fused_vs_module_case("cpu", num_scales, sn, S, 3, DFamilyEmuOps)
+
+
+def test_default_discriminator_builds_todays_programs():
+    """One scale without spectral norm: no power iteration, no pack inside a forward, the merged real | fake pass of 2B images."""
+    cfg = dfamily_config(1, False, small_g=True)
+    C.set_seed(42)
+    gen, disc = C.build_models(cfg, "cpu")
+    tr = C.CutTrainer(gen, disc, cfg, 2, 32, device="cpu", amp=False, ops=DFamilyEmuOps())
+    assert tr.sn is None and tr.d_rf.B == 4 and len(tr.D.nets) == 1 and tr.losses.numel() == 16
+    assert len(tr.D.repack_program()) == 1
+
+
+def _resume_trainer(cfg, B, S):
+    C.set_seed(42)
+    gen, disc = C.build_models(cfg, "cpu")
+    return C.CutTrainer(gen, disc, cfg, B, S, device="cpu", amp=False, ops=DFamilyEmuOps()), disc
+
+
+def test_checkpoint_reference_keys_and_exact_resume(tmp_path):
+    torch.set_num_threads(4)
+    cfg = dfamily_config(2, True, small_g=True)
+    cfg["r1"]["every"] = 2                     # an R1 step (step 2) after the resume
+    B, S = 2, 64
+    photos, monets = _inputs(B, S)
+    rnds = []
+    for step in range(3):
+        torch.manual_seed(9000 + step)
+        rnds.append(cut_ref.sample_step_randomness(B, S, S, use_aug=True))
+    a, _ = _resume_trainer(cfg, B, S)
+    for step in range(3):
+        want = a.train_step(step, photos, monets, rnds[step])
+    b, disc_b = _resume_trainer(cfg, B, S)
+    for step in range(2):
+        b.train_step(step, photos, monets, rnds[step])
+    path = str(tmp_path / "ck" / "step_1.pt")
+    b.save_checkpoint(path, 1)
+    raw = torch.load(path, map_location="cpu", weights_only=True)
+    fresh = C.MultiscaleDiscriminator(3, 64, 3, 2, True)
+    fresh.load_state_dict(raw["discriminator"], strict=True)     # the reference's keys: weight_orig, weight_u, weight_v, bias
+    assert list(raw["discriminator"]) == list(fresh.state_dict())
+    assert torch.equal(raw["discriminator"]["discriminators.1.model.4.weight_u"], disc_b.state_dict()["discriminators.1.model.4.weight_u"])
+    assert len(raw["opt_D"]["state"]) == sum(1 for _ in fresh.parameters())
+    c, _ = _resume_trainer(cfg, B, S)
+    c.load_checkpoint(path)
+    got = c.train_step(2, photos, monets, rnds[2])
+    assert got == want
+    for k, v in a.discriminator.state_dict().items():
+        assert torch.equal(v, c.discriminator.state_dict()[k]), k
+    for k, v in a.opt_G.params.items():
+        assert torch.equal(v, c.opt_G.params[k]), k
+
+
+@pytest.mark.parametrize("drop_key", [False, True])
+def test_driver_runs_multiscale_spectral_norm(tmp_path, drop_key):
+    import yaml
+    from gan_variant_research_amd import train_cutpp as T
+    from tests.test_train_driver import SCHEMA
+    cfg = yaml.safe_load(SCHEMA)
+    if drop_key:                     # build_models keeps the reference's default: use_spectral_norm=True
+        del cfg["model"]["discriminator"]["use_spectral_norm"]
+    cfg_path = str(tmp_path / "cfg.yaml")
+    with open(cfg_path, "w") as f:
+        yaml.safe_dump(cfg, f)
+    torch.set_num_threads(4)
+    ck, lg = str(tmp_path / "ck"), str(tmp_path / "lg")
+    sets = ["image_size=64", "batch_size=2", "max_steps=2", "amp=false", f"output.checkpoint_dir={ck}", f"output.log_dir={lg}",
+            "metrics.save_checkpoint_every=1", "log_every=1", "model.generator.ngf=16", "model.generator.n_blocks=3",
+            "model.discriminator.num_scales=2"] + ([] if drop_key else ["model.discriminator.use_spectral_norm=true"])
+    r = T.main(["--config", cfg_path, "--synthetic", "--set"] + sets, ops=DFamilyEmuOps(), device="cpu")
+    assert r["step"] == 2
+    assert sorted(os.listdir(ck)) == ["ckpt_final.pt", "ckpt_step1.pt"]
+    ckpt = torch.load(os.path.join(ck, "ckpt_final.pt"), weights_only=True)
+    assert "discriminators.1.model.8.weight_orig" in ckpt["discriminator"] and "discriminators.1.model.8.weight_v" in ckpt["discriminator"]
+
+
+# ---------------------------------------------------------------------------------------------------------------- data parallel
+S_DP, BG_DP = 64, 2
+
+
+def _dp_make(B, world=1, pg=None):
+    cfg = dfamily_config(2, True, small_g=True)
+    C.set_seed(42)
+    gen, disc = C.build_models(cfg, "cpu")
+    return C.CutTrainer(gen, disc, cfg, B, S_DP, device="cpu", amp=False, ops=DFamilyEmuOps(), world_size=world, process_group=pg)
+
+
+def _dp_rnd(tr_like):
+    torch.manual_seed(4242)
+    return tr_like.sample_randomness()
+
+
+def _dp_shard(rnd, lo, hi):
+    out = {"nce_ids": rnd["nce_ids"]}
+    for k in ("aug_real", "aug_fake_d", "aug_fake_g"):
+        out[k] = {n: (v[lo:hi] if v.dim() > 0 else v) for n, v in rnd[k].items()}
+    return out
+
+
+def _dp_worker(rank, world, port, out):
+    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
+    dist.init_process_group("gloo", rank=rank, world_size=world)
+    torch.set_num_threads(2)
+    bl = BG_DP // world
+    tr = _dp_make(bl, world, None)
+    g = torch.Generator().manual_seed(1234)
+    photos = torch.rand(BG_DP, 3, S_DP, S_DP, generator=g) * 2 - 1
+    monets = torch.rand(BG_DP, 3, S_DP, S_DP, generator=g) * 2 - 1
+    rnd = _dp_rnd(_dp_make(BG_DP))
+    lo, hi = rank * bl, (rank + 1) * bl
+    losses = tr.train_step(0, photos[lo:hi], monets[lo:hi], _dp_shard(rnd, lo, hi))
+    out[rank] = {k: v.clone() for k, v in tr.discriminator.state_dict().items()}
+    out[f"flat_gd{rank}"], out[f"loss{rank}"] = tr.opt_D.flat_g.clone(), losses
+    dist.destroy_process_group()
+
+
+def test_two_rank_gloo_spectral_norm_matches_one_rank():
+    """u and v depend only on the synced weights: identical on both ranks; the summed D gradients (spectral-norm backward applied
+    before the all-reduce) reproduce the single-rank step on the whole batch."""
+    with socket.socket() as sk:
+        sk.bind(("127.0.0.1", 0))
+        port = sk.getsockname()[1]
+    mgr = mp.Manager()
+    out = mgr.dict()
+    mp.spawn(_dp_worker, args=(2, port, out), nprocs=2, join=True)
+    torch.set_num_threads(4)
+    one = _dp_make(BG_DP)
+    g = torch.Generator().manual_seed(1234)
+    photos = torch.rand(BG_DP, 3, S_DP, S_DP, generator=g) * 2 - 1
+    monets = torch.rand(BG_DP, 3, S_DP, S_DP, generator=g) * 2 - 1
+    ref_losses = one.train_step(0, photos, monets, _dp_rnd(_dp_make(BG_DP)))
+    ref = one.discriminator.state_dict()
+    r0, r1 = out[0], out[1]
+    # the last D gradient of the step (R1's, step 0), all-reduced (summed; the optimiser divides by the world size) on every rank, is
+    # the one-rank gradient of weight_orig / bias
+    summed = out["flat_gd0"]
+    assert torch.equal(summed, out["flat_gd1"])
+    assert float((summed / 2 - one.opt_D.flat_g).abs().max() / one.opt_D.flat_g.abs().max()) < 2e-4
+    for k in ("d_loss", "g_adv", "r1"):
+        np.testing.assert_allclose(0.5 * (out["loss0"][k] + out["loss1"][k]), ref_losses[k], rtol=2e-4, atol=2e-5, err_msg=k)
+    for k in ref:
+        if k.endswith(("weight_u", "weight_v")):
+            assert torch.equal(r0[k], r1[k]), k                  # power iterations on the synced weights: identical on every rank
+            tol = 1e-3 * float(ref[k].abs().max())
+        else:
+            tol = 9e-4                                           # Adam's sign-like first updates, two D updates (D-step + R1)
+        err = float((r0[k] - ref[k]).abs().max())
+        assert err < tol, f"{k}: {err:.3e}"
