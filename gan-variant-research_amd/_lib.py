@@ -38,7 +38,7 @@ class GanWgradDesc(C.Structure):
                 ("x", vp), ("x_Hp", i32), ("x_Wp", i32), ("x_y0", i32), ("x_x0", i32), ("x_sy", i32), ("x_sx", i32),
                 ("tapoff", vp), ("g", vp),
                 ("g_Hp", i32), ("g_Wp", i32), ("g_C", i32), ("g_y0", i32), ("g_x0", i32), ("g_sy", i32), ("g_sx", i32),
-                ("part", vp), ("max_tapoff", i32), ("variant", i32)]
+                ("part", vp), ("max_tapoff", i32), ("variant", i32), ("g_scale", vp)]
 
 
 class GanAdamTensor(C.Structure):

@@ -422,3 +422,36 @@ class ConvLayer:
             ba = accumulate if bias_accumulate is None else bias_accumulate
             out.append(ops.bias_grad(dy, self.cout, self.grad_b, ba, ctx.scratch("bias_ws", 256 * max(dy.C, 256))))
         return out
+
+    def wgrad8_call(self, x8: View, dy8: View, g_scale: Optional[torch.Tensor], ops=None) -> Optional[WgradCall]:
+        """The e4m3 weight-gradient call of wgrad8 (nsplit and variant set, no partial buffer yet), or None where the e4m3 range-patch kernel
+        does not qualify (gan_wgrad_patch_splits answers 0 for the GAN_FP8 descriptor).  Planning only: nothing is launched or allocated."""
+        assert not self.transposed and self.s == 1 and x8.dtype == FP8 and dy8.dtype == FP8 and x8.halo >= self.p
+        assert x8.C == cpad(self.cin) and dy8.C == cpad(self.cout) and x8.B == dy8.B and (x8.H, x8.W) == (dy8.H, dy8.W)
+        ctx, k, p = self.ctx, self.k, self.p
+        ops = ctx.ops if ops is None else ops
+        cx = x8.C
+        key = (x8.Wp, cx)
+        tapoff = self._wg_tapoff.get(key)
+        if tapoff is None:
+            tapoff = self._wg_tapoff[key] = ctx.i32([(kh * x8.Wp + kw) * cx for kh in range(k) for kw in range(k)])
+        call = WgradCall(dy8.B, dy8.H, dy8.W, cx, self.kk, dy8.C, 1, x8, x8.halo - p, x8.halo - p, 1, 1, tapoff, dy8, dy8.halo, dy8.halo, 1, 1, None,
+                         max_tapoff=((k - 1) * x8.Wp + (k - 1)) * cx, g_scale=g_scale)
+        spi = ops.wgrad_patch_splits(call)
+        if spi <= 0:
+            return None
+        call.nsplit, call.variant = dy8.B * spi, 1
+        return call
+
+    def wgrad8(self, x8: View, dy8: View, g_scale: Optional[torch.Tensor], accumulate: bool, ops=None):
+        """grad_w (+)= dL/dW on e4m3 operands: x8 = e4m3 copy of the layer input (unit scale, halo >= pad), dy8 = e4m3 copy of the output
+        gradient with the per-image scales g_scale (device float[B]; None: 1).  conv_wgrad (dtype FP8, range-patch variant) + the bf16
+        path's wgrad_reduce; no bias gradient.  Raises GanError where the e4m3 kernel does not qualify: the caller decides on the fallback."""
+        ops = self.ctx.ops if ops is None else ops
+        call = self.wgrad8_call(x8, dy8, g_scale, ops)
+        if call is None:
+            raise GanError(f"weight gradient B{dy8.B} {dy8.H}x{dy8.W} C{x8.C}->{dy8.C} k{self.k}: the e4m3 range-patch kernel does not qualify")
+        n, cx = dy8.C, x8.C
+        call.part = part = self.ctx.scratch("wgrad_part", call.nsplit * n * self.kk * cx)
+        return [ops.conv_wgrad(call),
+                ops.wgrad_reduce(part, call.nsplit, n, self.kk, cx, self.cout, self.cin, False, self.cin, self.kk, self.wg_khw, self.grad_w, accumulate)]

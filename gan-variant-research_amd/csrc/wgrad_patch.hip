@@ -218,10 +218,15 @@ __global__ __launch_bounds__(512) void wgrad_patch_kernel(WpArgs a) {
 
 }  // namespace
 
+// the e4m3 kernel of the same decomposition (wgrad_patch_fp8.hip): dtype GAN_FP8 descriptors are its
+int gan_wgrad_patch_fp8_splits(const gan_wgrad_desc* d);
+int gan_wgrad_patch_fp8_launch(const gan_wgrad_desc* d, hipStream_t s);
+
 // splits per image the range-patch weight-gradient kernel wants for this problem (0 = descriptor does not qualify).
 // The planner sizes `part` for B * spi slabs and sets nsplit = B * spi, variant = 1.
 extern "C" int gan_wgrad_patch_splits(const gan_wgrad_desc* d) {
   if (!d) return 0;
+  if (d->dtype == GAN_FP8) return gan_wgrad_patch_fp8_splits(d);
   if (d->dtype != GAN_BF16 || d->ntaps != NT || d->Cx % CB != 0 || d->N % NB != 0 || d->N != d->g_C) return 0;
   if (d->x_sy != 1 || d->x_sx != 1 || d->g_sy != 1 || d->g_sx != 1) return 0;
   // 3x3 window in row-major tap order over a map whose width is a power of two dividing the stage
@@ -248,6 +253,7 @@ extern "C" int gan_wgrad_patch_splits(const gan_wgrad_desc* d) {
 }
 
 int gan_wgrad_patch_launch(const gan_wgrad_desc* d, hipStream_t s) {
+  if (d->dtype == GAN_FP8) return gan_wgrad_patch_fp8_launch(d, s);
   const int spi_want = gan_wgrad_patch_splits(d);
   GAN_CHECK(spi_want != 0 && d->nsplit > 0 && (d->nsplit % d->B == 0 || (d->B % d->nsplit == 0 && (d->Ho * d->Wo) % KM == 0)),
             "wgrad: variant=1 but the descriptor does not qualify for the range-patch kernel");

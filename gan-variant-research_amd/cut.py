@@ -421,9 +421,12 @@ class CutTrainer:
     """
 
     def __init__(self, generator: ResNetGenerator, discriminator: MultiscaleDiscriminator, config: dict, batch_size: int, image_size: int,
-                 device="cuda", amp: Optional[bool] = None, ops=None, world_size: int = 1, process_group=None, fp8: Optional[bool] = None):
+                 device="cuda", amp: Optional[bool] = None, ops=None, world_size: int = 1, process_group=None, fp8: Optional[bool] = None,
+                 fp8_wgrad: Optional[bool] = None):
         """fp8 (default: config['mi355x']['fp8'], else False): the residual blocks' convolutions read e4m3 operand copies in the forward pass
-        and in the input gradient (BASELINE.json configs[4]); needs amp (bf16) -- see nets.GeneratorNet."""
+        and in the input gradient (BASELINE.json configs[4]); needs amp (bf16) -- see nets.GeneratorNet.
+        fp8_wgrad (default: config['mi355x']['fp8_wgrad'], else False): their weight gradients run on the same e4m3 copies in all three
+        generator passes of a step; needs fp8, whose passes write those copies."""
         self.config = config
         self.B, self.S = batch_size, image_size
         self.device = torch.device(device)
@@ -432,6 +435,10 @@ class CutTrainer:
         self.fp8 = bool((config.get("mi355x") or {}).get("fp8", False) if fp8 is None else fp8)
         if self.fp8 and not amp:
             raise ValueError("fp8 convolutions exist in the bf16 (amp) mode only: fp32 is the parity mode")
+        self.fp8_wgrad = bool((config.get("mi355x") or {}).get("fp8_wgrad", False) if fp8_wgrad is None else fp8_wgrad)
+        if self.fp8_wgrad and not self.fp8:
+            raise ValueError("fp8_wgrad needs fp8: the e4m3 weight gradient reads the e4m3 operand copies that only the fp8 forward and "
+                             "input-gradient passes write")
         self.ops = ops if ops is not None else HipOps(self.device)
         if hasattr(self.ops, "bind"):
             self.ops.bind()                 # one stream for this trainer's launches and its torch-side copies / events, from now on
@@ -473,7 +480,7 @@ class CutTrainer:
 
         B, S = self.B, self.S
         nb, ngf = generator.n_blocks, generator.ngf
-        self.G = GeneratorNet(self.ctx, self.opt_G.params, self.opt_G.grads, "cut", nb, ngf, need_input_grad=True, fp8=self.fp8)
+        self.G = GeneratorNet(self.ctx, self.opt_G.params, self.opt_G.grads, "cut", nb, ngf, need_input_grad=True, fp8=self.fp8, fp8_wgrad=self.fp8_wgrad)
         K = self.num_scales
         self.sn = None
         if self.spectral_norm:

@@ -73,14 +73,20 @@ class GeneratorNet(_Net):
     """9-block ResNet generator of both trainers (CUT: biased convs; Basic_GAN: bias-free but the last)."""
 
     def __init__(self, ctx, params, grads, style="cut", n_blocks=9, ngf=64, in_c=3, out_c=3, need_input_grad=True, reflect=True,
-                 block_act=ACT_RELU, fp8=False):
+                 block_act=ACT_RELU, fp8=False, fp8_wgrad=False):
         """reflect: `padding_type` 'reflect' (the configs' value) or 'zero'; block_act: the residual blocks' activation (ReLU in the
         configs, LeakyReLU(0.2) for activation='leaky_relu', generator_resnet_attn.py:60-66).
         fp8: the residual blocks' 3x3 convolutions (generator_resnet_attn.py:33,48 -- 88 % of the generator's FLOPs) read e4m3 copies of
         their operands in the forward pass and in the input gradient (BASELINE.json configs[4]); weight gradients, InstanceNorm, the
-        first / last layers and everything stored stay bf16 / fp32.  bf16 mode with reflect padding only."""
+        first / last layers and everything stored stay bf16 / fp32.  bf16 mode with reflect padding only.
+        fp8_wgrad (needs fp8): the same convolutions' weight gradients run on those e4m3 copies too (ConvLayer.wgrad8: the layer input's
+        copy of the forward pass and the output gradient's copy of the input gradient -- no further quantisation pass); layers whose maps
+        the e4m3 weight-gradient kernel does not take (under 128 pixels) keep the bf16 one.  GPass.wgrad8_layers tells which took which."""
         super().__init__(ctx, params, grads)
         self.fp8 = bool(fp8)
+        self.fp8_wgrad = bool(fp8_wgrad)
+        self.passes = []
+        assert not self.fp8_wgrad or self.fp8, "fp8_wgrad reads the e4m3 operand copies that only the fp8 mode writes: it needs fp8=True"
         assert not self.fp8 or (ctx.dtype == BF16 and reflect and 4 * ngf >= 128 and (4 * ngf) % 128 == 0), "fp8 blocks: bf16 mode, reflect padding, >= 128 channels"
         self.style, self.n_blocks, self.ngf, self.in_c, self.out_c = style, n_blocks, ngf, in_c, out_c
         self.reflect, self.block_act = reflect, block_act
@@ -94,7 +100,9 @@ class GeneratorNet(_Net):
         self.n_layers = 3 + n_blocks + 2  # numbered activations of get_feature_layers
 
     def new_pass(self, B, H, W, last_layer: Optional[int] = None) -> "GPass":
-        return GPass(self, B, H, W, last_layer)
+        p = GPass(self, B, H, W, last_layer)
+        self.passes.append(p)      # every pass built on this network (tests read which weight gradients took which path)
+        return p
 
 
 class GPass:
@@ -136,11 +144,12 @@ class GPass:
             self.mid8 = [v(B, H // 4, W // 4, 4 * g, 1, dtype=FP8) for _ in self.mid]
         self.img = v(B, H, W, cpad(net.out_c), 0) if self.full else None
 
-    def _fp8_grad_bufs(self, B, h, w, c):
+    def _fp8_grad_bufs(self, B, h, w, c, tag=None):
         """e4m3 copy of a residual convolution's output gradient (zero halo 2) with its per-image amax / scale: one set per network and
-        shape (producer and consumer are neighbours on the main stream)."""
+        shape (producer and consumer are neighbours on the main stream).  With e4m3 weight gradients the side stream reads the copy and
+        its scales one block late: then `tag` names one of the alternating sets (a0 / a1 / b0 / b1, as the dy_blk_* buffers)."""
         net = self.net
-        key = ("fp8g", B, h, w, c)
+        key = ("fp8g", B, h, w, c) if tag is None else ("fp8g", B, h, w, c, tag)
         bufs = net._gbufs.get(key)
         if bufs is None:
             bufs = net._gbufs[key] = (net.ctx.view(B, h, w, c, 2, dtype=FP8), net.ctx.f32(B), net.ctx.f32(B, 1.0))
@@ -239,14 +248,31 @@ class GPass:
         side = ops.side()
         readers = {}     # id(dy buffer) -> event recorded on the side stream after its last reader
 
-        def wgrad_side(conv, x, dy, bias_too):
+        def wgrad_side(conv, x, dy, bias_too, g_scale=None):
             ev = ops.new_event()
             prog.add(ops.record(ev))
             prog.add(side.wait(ev))
-            prog.add(conv.wgrad(x, dy, acc, bias_too=bias_too, ops=side))
+            if dy.dtype == FP8:      # e4m3 operands (fp8_wgrad): x is the layer input's e4m3 copy, dy the scaled copy of the output gradient
+                w8ops = conv.wgrad8(x, dy, g_scale, acc, ops=side)
+                self.wgrad8_calls.append(w8ops[0].wgrad)
+                prog.add(w8ops)
+            else:
+                prog.add(conv.wgrad(x, dy, acc, bias_too=bias_too, ops=side))
             done = ops.new_event()
             prog.add(side.record(done))
             readers[id(dy.t)] = done
+
+        # fp8_wgrad: which residual convolutions' weight gradients run on e4m3 operands -- (block, "a" | "b") -> True (e4m3 kernel) / False
+        # (bf16 kernel: the e4m3 one does not take the layer's maps)
+        self.wgrad8_layers = {}
+        self.wgrad8_calls = []      # the e4m3 weight-gradient calls of this program (runtime.WgradCall), in launch order
+
+        def use_wgrad8(k, which, conv, x8, dy8, sc8):
+            if not net.fp8_wgrad:
+                return False
+            ok = conv.wgrad8_call(x8, dy8, sc8, ops=side) is not None
+            self.wgrad8_layers[(k, which)] = ok
+            return ok
 
         def before_write(buf: View):
             ev = readers.pop(id(buf.t), None)
@@ -333,10 +359,15 @@ class GPass:
             a_parts = None
             if net.fp8:
                 # input gradients on e4m3 operands: the norm backward leaves max|dY| per image, the copy is scaled by it
-                dy8, am8, sc8 = self._fp8_grad_bufs(B, h4, w4, c4)
+                dy8, am8, sc8 = self._fp8_grad_bufs(B, h4, w4, c4, f"b{k % 2}" if net.fp8_wgrad else None)
+                w8 = use_wgrad8(k, "b", cb, self.mid8[k], dy8, sc8)
                 inbwd(rb, sb, ACT_NONE, g_cur, False, dyb, cb, amax=am8)
-                wgrad_side(cb, self.mid[k], dyb, False)
+                if not w8:
+                    wgrad_side(cb, self.mid[k], dyb, False)
+                before_write(dy8)      # fp8_wgrad: the side stream may still read this set (copy and scales) for block k + 2
                 prog.add(ops.quantize_fp8(dyb, dy8, am8, sc8))
+                if w8:                 # after the copy exists: the weight gradient reads it, not dyb
+                    wgrad_side(cb, self.mid8[k], dy8, False, g_scale=sc8)
                 prog.add(cb.dgrad8(dy8, g_mid, sc8, padded_domain=rf))
             else:
                 inbwd(rb, sb, ACT_NONE, g_cur, False, dyb, cb)
@@ -351,9 +382,16 @@ class GPass:
             before_write(dya)
             g_in_p = net.gbuf("g_blk_p", B, h4, w4, c4, 1)
             if net.fp8:
+                if net.fp8_wgrad:
+                    dy8, am8, sc8 = self._fp8_grad_bufs(B, h4, w4, c4, f"a{k % 2}")
+                w8 = use_wgrad8(k, "a", ca, self.in8[k], dy8, sc8)
                 inbwd(ra, sa, net.block_act, g_mid, rf, dya, ca, amax=am8)
-                wgrad_side(ca, self.acts[i - 1], dya, False)
+                if not w8:
+                    wgrad_side(ca, self.acts[i - 1], dya, False)
+                before_write(dy8)
                 prog.add(ops.quantize_fp8(dya, dy8, am8, sc8))
+                if w8:
+                    wgrad_side(ca, self.in8[k], dy8, False, g_scale=sc8)
                 prog.add(ca.dgrad8(dy8, g_in_p, sc8, padded_domain=rf))
             else:
                 inbwd(ra, sa, net.block_act, g_mid, rf, dya, ca, parts=a_parts)

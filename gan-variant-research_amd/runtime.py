@@ -135,6 +135,7 @@ class WgradCall:
     part: Optional[torch.Tensor]
     max_tapoff: int = 0
     variant: int = 0          # 1: range-patch kernel (nsplit = B * splits per image); 2: 7x7 window kernel (nsplit = its block count)
+    g_scale: Optional[torch.Tensor] = None   # e4m3 operands (x.dtype == FP8, variant 1): device float[B], per-image scale of g (None: 1)
 
 
 Op = Callable[[], None]
@@ -351,7 +352,8 @@ class HipOps:
         d.g_Hp, d.g_Wp, d.g_C, d.g_y0, d.g_x0, d.g_sy, d.g_sx = c.g.Hp, c.g.Wp, c.g.C, c.g_y0, c.g_x0, c.g_sy, c.g_sx
         d.part = c.part.data_ptr() if c.part is not None else None
         d.max_tapoff, d.variant = c.max_tapoff, c.variant
-        assert c.g.dtype == c.x.dtype
+        d.g_scale = c.g_scale.data_ptr() if c.g_scale is not None else None
+        assert c.g.dtype == c.x.dtype and (c.g_scale is None or (c.x.dtype == FP8 and c.g_scale.dtype == torch.float32 and c.g_scale.numel() >= c.B))
         return d
 
     def wgrad_patch_splits(self, c: WgradCall) -> int:

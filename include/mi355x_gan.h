@@ -91,7 +91,13 @@ typedef struct gan_conv_desc {
 } gan_conv_desc;
 
 /* Weight-gradient GEMM: part[s][n][t][c] = sum over the rows m of split s of
- * g[g_off(m) + n] * x[x_off(m) + tapoff[t] + c], with g_off/x_off as in gan_conv_desc.  nsplit slabs. */
+ * g[g_off(m) + n] * x[x_off(m) + tapoff[t] + c], with g_off/x_off as in gan_conv_desc.  nsplit slabs.
+ * dtype GAN_FP8 (variant 1 only; variants 0 and 2 answer with an error): x and g hold e4m3 bytes -- x with unit scale (an e4m3 copy of
+ * the layer input, halo >= 1), g the e4m3 copy of the output gradient with one dequantisation scale per image, g_scale[b] -- and
+ *   part[s][n][t][c] = g_scale[b(s)] * sum over the pixels m of split s of g8[m][n] * x8[pix(m) + tapoff[t]][c]
+ * in fp32 on v_mfma_scale_f32_16x16x128_f8f6f4; a split never crosses an image, the scale is applied when its sums are stored.  part keeps
+ * the slab layout, so gan_wgrad_reduce follows unchanged.  In fp8 mode it replaces the weight-gradient half of the backward() of the
+ * residual blocks' nn.Conv2d(256, 256, 3) under autocast (GAN_Variant1/models/generator_resnet_attn.py:33,48). */
 typedef struct gan_wgrad_desc {
   int32_t dtype;
   int32_t B, Ho, Wo;
@@ -108,6 +114,7 @@ typedef struct gan_wgrad_desc {
   int32_t max_tapoff;            /* largest value in tapoff[] (range-patch variant's span check) */
   int32_t variant;               /* 0: generic kernel, any nsplit; 1: range-patch kernel, nsplit = B * gan_wgrad_patch_splits() (or B / -that);
                                     2: 7x7 window kernel, nsplit = gan_wgrad_win7_splits() */
+  const float* g_scale;          /* dtype GAN_FP8: device float[B], per-image scale of g (NULL = 1); other dtypes: ignored */
 } gan_wgrad_desc;
 
 const char* gan_last_error(void);
@@ -148,7 +155,9 @@ int gan_conv_stats_parts(const gan_conv_desc* d);
 int gan_conv_wgrad(const gan_wgrad_desc* d, void* stream);
 /* splits per image the range-patch weight-gradient kernel wants (0: the descriptor does not qualify: bf16, 9 taps, stride 1,
  * Cx % 64 == 0, N % 128 == 0, one 128-pixel stage's window span fits LDS); pure host-side predicate for the planner.
- * A NEGATIVE value -k means k whole images per split (many small maps, e.g. 16x16 at batch 256): nsplit = B / k. */
+ * A NEGATIVE value -k means k whole images per split (many small maps, e.g. 16x16 at batch 256): nsplit = B / k.
+ * dtype GAN_FP8: the same question for the e4m3 kernel (e4m3 x and g, 9 taps, stride 1, Cx % 64 == 0, N % 128 == 0); never negative --
+ * where the bf16 answer would be, it is 0 and the planner keeps the bf16 kernel for that launch. */
 int gan_wgrad_patch_splits(const gan_wgrad_desc* d);
 /* grad[(a*I2 + b)*KK + khw[t]] (+)= sum_s part[s][n][t][c], (a,b) = swap ? (c,n) : (n,c), for n<N_real, c<C_real, khw[t]>=0 */
 /* slabs the 7x7 window weight-gradient kernels write (0: the descriptor does not qualify: bf16, 49 row-major taps, stride 1, and
