@@ -13,7 +13,7 @@ import torch.nn as nn
 
 from ._lib import BF16, F32, HALO_ZERO
 from .cut import FusedAdam, _adam_state_dict, _load_adam_state_dict
-from .nets import DiscriminatorNet, GeneratorNet
+from .nets import DiscriminatorNet, GeneratorNet, PartialSNDiscriminatorNet, SpectralNorm
 from .runtime import Ctx, HipOps, Program, View
 
 
@@ -114,14 +114,17 @@ class CycleGANTrainer:
 
     Legal saving (results unchanged): D_A(fake_A) / D_B(fake_B) are forwarded once; the generator step back-propagates through
     them without weight gradients and the discriminator steps reuse the same activations (D's weights do not change in between).
+
+    Spectral-norm discriminators (NLayerDiscriminator(spectral=True), models.py:67-101): every forward advances the power iteration of
+    net.2 / net.5 / net.8, three per discriminator and iteration as in the reference (G-step D(fake), D-step D(real), D-step
+    D(fake.detach())), so the D-step forwards the fake pass again and runs in sequence: real forward -> backward -> spectral-norm
+    backward (write) -> fake forward -> backward -> spectral-norm backward (add).  weight_u / weight_v live in device buffers that the
+    modules' buffers alias.
     """
 
     def __init__(self, G_A2B: ResnetGenerator, G_B2A: ResnetGenerator, D_A: NLayerDiscriminator, D_B: NLayerDiscriminator, cfg: dict,
                  batch_size: int, image_size: int, device="cuda", amp: Optional[bool] = None, ops=None, world_size: int = 1, process_group=None):
         self.cfg, self.B, self.S = cfg, batch_size, image_size
-        if getattr(D_A, "spectral", False) or getattr(D_B, "spectral", False):
-            raise NotImplementedError("the fused CycleGANTrainer runs Basic_GAN/configs/baseline.yaml (spectral_norm_d: false); "
-                                      "spectral-norm discriminators run through the nn.Module API (autograd.py)")
         self.device = torch.device(device)
         amp = cfg["training"].get("amp", True) if amp is None else amp
         self.dtype = BF16 if amp else F32
@@ -136,7 +139,16 @@ class CycleGANTrainer:
         gab, gba = f32(G_A2B.state_dict()), f32(G_B2A.state_dict())
         both = {**{"ab." + k: v for k, v in gab.items()}, **{"ba." + k: v for k, v in gba.items()}}   # optim_G owns both (train.py:45-48)
         self.opt_G = FusedAdam(self.ctx, list(both), [v.shape for v in both.values()], both, lr_g, betas)
-        da, db = f32(D_A.state_dict()), f32(D_B.state_dict())
+        # the optimisers hold the parameters (weight_orig under spectral norm; D.parameters() order); weight_u / weight_v: device
+        # buffers the power iterations update in place, which the modules' buffers alias (D_A.state_dict() stays live)
+        d_params = lambda D: {k: v for k, v in f32(D.state_dict()).items() if k in dict(D.named_parameters())}
+        da, db = d_params(D_A), d_params(D_B)
+        self.d_buffers = {}
+        for name, D in (("D_A", D_A), ("D_B", D_B)):
+            self.d_buffers[name] = {k: v.detach().to(self.device, torch.float32).clone().contiguous() for k, v in D.named_buffers()}
+            for k, b in D.named_buffers():
+                b.data = self.d_buffers[name][k]
+        self._d_keys = {"D_A": list(D_A.state_dict()), "D_B": list(D_B.state_dict())}
         self.opt_DA = FusedAdam(self.ctx, list(da), [v.shape for v in da.values()], da, lr_d, betas)
         self.opt_DB = FusedAdam(self.ctx, list(db), [v.shape for v in db.values()], db, lr_d, betas)
         for mod, opt, pre in ((G_A2B, self.opt_G, "ab."), (G_B2A, self.opt_G, "ba."), (D_A, self.opt_DA, ""), (D_B, self.opt_DB, "")):
@@ -146,8 +158,8 @@ class CycleGANTrainer:
         nb, ngf = G_A2B.n_blocks, G_A2B.ngf
         self.Gab = GeneratorNet(self.ctx, sub(self.opt_G.params, "ab."), sub(self.opt_G.grads, "ab."), "basic", nb, ngf)
         self.Gba = GeneratorNet(self.ctx, sub(self.opt_G.params, "ba."), sub(self.opt_G.grads, "ba."), "basic", nb, ngf)
-        self.DA = DiscriminatorNet(self.ctx, self.opt_DA.params, self.opt_DA.grads, "basic", ndf=D_A.ndf, n_layers=D_A.n_layers)
-        self.DB = DiscriminatorNet(self.ctx, self.opt_DB.params, self.opt_DB.grads, "basic", ndf=D_B.ndf, n_layers=D_B.n_layers)
+        self.DA, self.sn_A = self._d_net(D_A, self.opt_DA, self.d_buffers["D_A"])
+        self.DB, self.sn_B = self._d_net(D_B, self.opt_DB, self.d_buffers["D_B"])
         B, S = self.B, self.S
         self.real_a = torch.zeros(B, 3, S, S, dtype=torch.float32, device=self.device)
         self.real_b = torch.zeros_like(self.real_a)
@@ -156,6 +168,18 @@ class CycleGANTrainer:
         self._build()
         for net in (self.Gab, self.Gba, self.DA, self.DB):
             net.repack_program().run()
+
+    def _d_net(self, D, opt, buffers):
+        """The discriminator's engine: DiscriminatorNet, or with spectral norm the one whose net.2 / net.5 / net.8 are normalised."""
+        if not getattr(D, "spectral", False):
+            return DiscriminatorNet(self.ctx, opt.params, opt.grads, "basic", ndf=D.ndf, n_layers=D.n_layers), None
+        keys = [k[:-len(".weight_orig")] for k in opt.names if k.endswith(".weight_orig")]
+        sn = SpectralNorm(self.ctx, keys, opt.params, opt.grads, buffers)
+        return PartialSNDiscriminatorNet(self.ctx, opt.params, opt.grads, sn, "basic", ndf=D.ndf, n_layers=D.n_layers), sn
+
+    def _d_fwd(self, net, dp) -> Program:
+        """A discriminator forward: with spectral norm the power iteration and the pack of the normalised layers' copies come first."""
+        return net.fwd_program(dp) if isinstance(net, PartialSNDiscriminatorNet) else dp.fwd_program()
 
     def _slot(self, name):
         i = SLOTS[name]
@@ -178,8 +202,8 @@ class CycleGANTrainer:
         fwd.add(P["ab_b"].fwd_program(self.real_b)); fwd.add(P["ba_a"].fwd_program(self.real_a))
         self.db_fake, self.da_fake = self.DB.new_pass(B, S, S), self.DA.new_pass(B, S, S)
         self.db_real, self.da_real = self.DB.new_pass(B, S, S), self.DA.new_pass(B, S, S)
-        fwd.add(ops.view_copy(P["ab_a"].img, self.db_fake.x, HALO_ZERO)); fwd.add(self.db_fake.fwd_program())
-        fwd.add(ops.view_copy(P["ba_b"].img, self.da_fake.x, HALO_ZERO)); fwd.add(self.da_fake.fwd_program())
+        fwd.add(ops.view_copy(P["ab_a"].img, self.db_fake.x, HALO_ZERO)); fwd.add(self._d_fwd(self.DB, self.db_fake))
+        fwd.add(ops.view_copy(P["ba_b"].img, self.da_fake.x, HALO_ZERO)); fwd.add(self._d_fwd(self.DA, self.da_fake))
         self.P = P
 
         bwd = Program("G-bwd")
@@ -212,9 +236,22 @@ class CycleGANTrainer:
         self.prog_g_fwd, self.prog_g_bwd = fwd, bwd
 
         # ---- discriminator steps (train.py:99-114): real pass + the fake pass forwarded above
-        def d_step(net, real_src, p_real, p_fake, s_real, s_fake):
+        def d_step(net, real_src, p_real, p_fake, s_real, s_fake, fake_img):
             prog = Program("D-step")
             prog.add(ops.nchw_to_view(real_src, 3, p_real.x, HALO_ZERO))
+            if isinstance(net, PartialSNDiscriminatorNet):
+                # spectral norm: each forward runs its own power iteration and each backward reads the snapshots of its own forward,
+                # so real forward -> backward -> spectral-norm backward, then the fake pass forwarded again from the G-step's output
+                prog.add(net.fwd_program(p_real))
+                gl = p_real.grad_logits_view()
+                prog.add(ops.patch_loss(p_real.logits, mode, 1.0, 0.5, self._slot(s_real), gl))
+                prog.add(net.wgrad_program(p_real, gl, accumulate=False))
+                prog.add(ops.view_copy(fake_img, p_fake.x, HALO_ZERO))
+                prog.add(net.fwd_program(p_fake))
+                gl2 = p_fake.grad_logits_view()
+                prog.add(ops.patch_loss(p_fake.logits, mode, 0.0, 0.5, self._slot(s_fake), gl2))
+                prog.add(net.wgrad_program(p_fake, gl2, accumulate=True))
+                return prog
             prog.add(p_real.fwd_program())
             gl = p_real.grad_logits_view()
             prog.add(ops.patch_loss(p_real.logits, mode, 1.0, 0.5, self._slot(s_real), gl))
@@ -223,12 +260,15 @@ class CycleGANTrainer:
             prog.add(ops.patch_loss(p_fake.logits, mode, 0.0, 0.5, self._slot(s_fake), gl2))
             prog.add(p_fake.bwd_program(gl2, wgrad=True, accumulate=True))
             return prog
-        self.prog_da = d_step(self.DA, self.real_a, self.da_real, self.da_fake, "da_real", "da_fake")
-        self.prog_db = d_step(self.DB, self.real_b, self.db_real, self.db_fake, "db_real", "db_fake")
+        self.prog_da = d_step(self.DA, self.real_a, self.da_real, self.da_fake, "da_real", "da_fake", P["ba_b"].img)
+        self.prog_db = d_step(self.DB, self.real_b, self.db_real, self.db_fake, "db_real", "db_fake", P["ab_a"].img)
         # ---- updates (no clipping, no EMA in this trainer); built last: all operand copies are planned by now
         self.upd_g = Program("G-update"); self.upd_g.add(self.opt_G.step_op(None, gs)); self.upd_g.add(self.Gab.repack_program()); self.upd_g.add(self.Gba.repack_program())
         self.upd_da = Program("DA-update"); self.upd_da.add(self.opt_DA.step_op(None, gs)); self.upd_da.add(self.DA.repack_program())
         self.upd_db = Program("DB-update"); self.upd_db.add(self.opt_DB.step_op(None, gs)); self.upd_db.add(self.DB.repack_program())
+        for net in (self.DA, self.DB):
+            if isinstance(net, PartialSNDiscriminatorNet):
+                net.refresh_pack()          # the pack each forward runs covers every operand copy planned above
 
     # ---- epoch end (Basic_GAN/src/train.py:124-137): LambdaLR x 3, then the checkpoint dict
     def scheduler_step(self) -> float:
@@ -244,13 +284,19 @@ class CycleGANTrainer:
     def _module_state(self, opt, prefix=""):
         return {k[len(prefix):]: v.detach().clone() for k, v in opt.params.items() if k.startswith(prefix)}
 
+    def _d_state(self, name, opt):
+        """D_A / D_B under the module's state_dict keys and order (with spectral norm: weight_orig, weight_u, weight_v per layer)."""
+        bufs = self.d_buffers[name]
+        return {k: (opt.params[k] if k in opt.params else bufs[k]).detach().clone() for k in self._d_keys[name]}
+
     def save_checkpoint(self, path: str, epoch: int):
         """The dict of train.py:127-137, key for key: epoch, the four state_dicts under the reference's module keys, and the three
-        torch.optim.Adam state_dicts (optim_G numbers list(G_A2B.parameters()) + list(G_B2A.parameters()), train.py:45-48; the param
-        groups carry the `initial_lr` LambdaLR put there and the decayed `lr`).  torch.optim.Adam.load_state_dict accepts them."""
+        torch.optim.Adam state_dicts (optim_G numbers list(G_A2B.parameters()) + list(G_B2A.parameters()), train.py:45-48, optim_D_* the
+        discriminator's parameters; the param groups carry the `initial_lr` LambdaLR put there and the decayed `lr`).
+        torch.optim.Adam.load_state_dict accepts them."""
         ck = {"epoch": int(epoch),
               "G_A2B": self._module_state(self.opt_G, "ab."), "G_B2A": self._module_state(self.opt_G, "ba."),
-              "D_A": self._module_state(self.opt_DA), "D_B": self._module_state(self.opt_DB),
+              "D_A": self._d_state("D_A", self.opt_DA), "D_B": self._d_state("D_B", self.opt_DB),
               "optim_G": _adam_state_dict(self.opt_G, True), "optim_D_A": _adam_state_dict(self.opt_DA, True),
               "optim_D_B": _adam_state_dict(self.opt_DB, True)}
         torch.save(ck, path)
@@ -258,11 +304,13 @@ class CycleGANTrainer:
 
     def load_checkpoint(self, path: str) -> int:
         """Resumes from a checkpoint in the reference's layout (train.py:127-137; the reference has no resume code of its own: the epoch
-        counter of the three schedulers is taken from `epoch`, as LambdaLR(last_epoch=epoch) would).  Returns the epoch."""
+        counter of the three schedulers is taken from `epoch`, as LambdaLR(last_epoch=epoch) would).  Spectral norm's weight_u /
+        weight_v are restored with the weights.  Returns the epoch."""
         ck = torch.load(path, map_location="cpu", weights_only=True)
         for key, opt, pre in (("G_A2B", self.opt_G, "ab."), ("G_B2A", self.opt_G, "ba."), ("D_A", self.opt_DA, ""), ("D_B", self.opt_DB, "")):
+            bufs = self.d_buffers.get(key, {})
             for k, v in ck[key].items():
-                opt.params[pre + k].copy_(v)
+                (opt.params[pre + k] if pre + k in opt.params else bufs[k]).copy_(v)
         for key, opt in (("optim_G", self.opt_G), ("optim_D_A", self.opt_DA), ("optim_D_B", self.opt_DB)):
             _load_adam_state_dict(opt, ck[key])
         self.sched_epoch = int(ck["epoch"])

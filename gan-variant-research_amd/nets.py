@@ -451,6 +451,7 @@ class DiscriminatorNet(_Net):
             keys = [f"{prefix}{2*i}" for i in range(nconv)]
         else:
             keys = ["net.0"] + [f"net.{2+3*i}" for i in range(n_layers)] + [f"net.{2+3*n_layers}"]
+        self.keys = keys
         self.chans = [in_c, ndf] + [ndf * min(2**n, 8) for n in range(1, n_layers)] + [ndf * min(2**n_layers, 8), 1]
         self.strides = [2] * n_layers + [1, 1]
         self.convs = [self._conv(k, 4, s, 1) for k, s in zip(keys, self.strides)]
@@ -542,9 +543,11 @@ class DPass:
         return self.net.gbuf("g_logits", self.B, lg.H, lg.W, lg.C, 2)
 
     def bwd_program(self, g_logits: View, wgrad: bool = True, accumulate: bool = False, need_input_grad: bool = False,
-                    keep: Optional[list] = None, bias_grads: bool = True, bias_accumulate: Optional[bool] = None) -> Program:
+                    keep: Optional[list] = None, bias_grads: bool = True, bias_accumulate: Optional[bool] = None,
+                    write_only: Sequence[int] = ()) -> Program:
         """Backward from dL/dlogits.  keep: if a list, the per-layer output gradients (delta_i) are appended to it and
-        live in dedicated buffers (R1's second-order pass needs them).  bias_accumulate: for the bias gradients (default: accumulate)."""
+        live in dedicated buffers (R1's second-order pass needs them).  bias_accumulate: for the bias gradients (default: accumulate).
+        write_only: indices of convolutions whose weight gradient is written even when `accumulate` (spectral norm's dL/dW_sn scratch)."""
         net, ops, B = self.net, self.net.ctx.ops, self.B
         prog = Program("D.bwd")
         dy = g_logits
@@ -558,8 +561,9 @@ class DPass:
             if keep is not None:
                 keep.append(dy)
             if wgrad:
-                kw = {} if bias_accumulate is None else {"bias_accumulate": bias_accumulate}
-                prog.add(conv.wgrad(xin, dy, accumulate, bias_too=bias_grads, **kw))
+                ba = accumulate if (bias_accumulate is None and li in write_only) else bias_accumulate
+                kw = {} if ba is None else {"bias_accumulate": ba}
+                prog.add(conv.wgrad(xin, dy, accumulate and li not in write_only, bias_too=bias_grads, **kw))
             if li == 0:
                 if need_input_grad:
                     self.g_input = net.gbuf("g_dx", B, self.H, self.W, self.x.C, 0)
@@ -615,6 +619,57 @@ class SpectralNorm:
 
     def bwd_op(self, accumulate: bool):
         return self._bwd[bool(accumulate)]
+
+
+class PartialSNDiscriminatorNet:
+    """A DiscriminatorNet with spectral norm on some of its convolutions only: Basic_GAN's NLayerDiscriminator(spectral=True)
+    (Basic_GAN/src/models.py:67-101) normalises the bias-free middle convolutions net.2 / net.5 / net.8 (`sn.keys`) and leaves net.0 and
+    net.11 plain.  The spectral-norm convolutions read weight_orig packed with scale sigma and write dL/dW_sn into `sn.G`; a forward is
+    one power iteration, the pack of their operand copies, then the layers; the repack after an optimiser step covers the plain ones."""
+
+    def __init__(self, ctx: Ctx, params: Dict[str, torch.Tensor], grads: Dict[str, torch.Tensor], sn: SpectralNorm, style="basic",
+                 ndf=64, n_layers=3, in_c=3):
+        self.ctx, self.sn = ctx, sn
+        params, grads = dict(params), dict(grads)
+        for k in sn.keys:
+            params[k + ".weight"], grads[k + ".weight"] = params[k + ".weight_orig"], sn.G[k]
+        self.net = DiscriminatorNet(ctx, params, grads, style, ndf=ndf, n_layers=n_layers, in_c=in_c)
+        self.sn_layers = [i for i, k in enumerate(self.net.keys) if k in sn.keys]
+        assert len(self.sn_layers) == len(sn.keys), (self.net.keys, sn.keys)
+        for i in self.sn_layers:
+            self.net.convs[i].pack_scale = sn.sigma[self.net.keys[i]]
+        self._pack = None
+
+    def _copies(self, spectral: bool):
+        return [op.pack_args for i, c in enumerate(self.net.convs) if (i in self.sn_layers) == spectral for op in c.repack_ops()]
+
+    def repack_program(self) -> Program:
+        """Operand copies of the plain convolutions after an optimiser step: one batched launch."""
+        prog = Program("repack")
+        prog.add(self.ctx.ops.pack_weight_batch(self._copies(False)))
+        return prog
+
+    def refresh_pack(self):
+        """(Re)builds the forward's pack launch over the spectral-norm convolutions' copies planned so far; call after planning passes."""
+        self._pack = self.ctx.ops.pack_weight_batch(self._copies(True))
+
+    def new_pass(self, B, H, W) -> "DPass":
+        return self.net.new_pass(B, H, W)
+
+    def fwd_program(self, dp: "DPass") -> Program:
+        prog = Program("PSND.fwd")
+        prog.add(self.sn.fwd_op())
+        prog.add(lambda: self._pack())
+        prog.add(dp.fwd_program())
+        return prog
+
+    def wgrad_program(self, dp: "DPass", g_logits: View, accumulate: bool) -> Program:
+        """Weight gradients of pass `dp`: the plain layers' written or added, dL/dW_sn written to the scratch, then one batched
+        spectral-norm backward that writes / adds dL/dweight_orig (it reads the snapshots of dp's own forward: run it before the next)."""
+        prog = Program("PSND.bwd")
+        prog.add(dp.bwd_program(g_logits, wgrad=True, accumulate=accumulate, write_only=self.sn_layers))
+        prog.add(self.sn.bwd_op(accumulate))
+        return prog
 
 
 class MultiscaleDiscriminatorNet:
