@@ -38,7 +38,7 @@ class GanWgradDesc(C.Structure):
                 ("x", vp), ("x_Hp", i32), ("x_Wp", i32), ("x_y0", i32), ("x_x0", i32), ("x_sy", i32), ("x_sx", i32),
                 ("tapoff", vp), ("g", vp),
                 ("g_Hp", i32), ("g_Wp", i32), ("g_C", i32), ("g_y0", i32), ("g_x0", i32), ("g_sy", i32), ("g_sx", i32),
-                ("part", vp), ("max_tapoff", i32), ("variant", i32), ("g_scale", vp)]
+                ("part", vp), ("max_tapoff", i32), ("variant", i32), ("g_scale", vp), ("g_scale_pow2", i32), ("_pad", i32)]
 
 
 class GanAdamTensor(C.Structure):
@@ -89,6 +89,7 @@ PROTOTYPES = {
     "gan_pack_weight_batch": (C.c_int, [vp, C.c_int, C.c_int, vp]),
     "gan_weight_scale_batch": (C.c_int, [vp, C.c_int, vp]),
     "gan_quantize_fp8": (C.c_int, [PV, PV, vp, vp, vp]),
+    "gan_quantize_fp8_pow2": (C.c_int, [PV, PV, vp, vp, vp]),
     "gan_in_bwd_amax": (C.c_int, [PV, vp, C.c_int, PV, C.c_int, PV, vp, vp, vp, vp]),
     "gan_bias_grad": (C.c_int, [PV, C.c_int, vp, C.c_int, vp, vp]),
     "gan_in_stats": (C.c_int, [PV, f32, vp, vp, vp]),

@@ -123,11 +123,26 @@ class CycleGANTrainer:
     """
 
     def __init__(self, G_A2B: ResnetGenerator, G_B2A: ResnetGenerator, D_A: NLayerDiscriminator, D_B: NLayerDiscriminator, cfg: dict,
-                 batch_size: int, image_size: int, device="cuda", amp: Optional[bool] = None, ops=None, world_size: int = 1, process_group=None):
+                 batch_size: int, image_size: int, device="cuda", amp: Optional[bool] = None, ops=None, world_size: int = 1, process_group=None,
+                 fp8: Optional[bool] = None, fp8_wgrad: Optional[bool] = None):
+        """fp8 (default: cfg['mi355x']['fp8'], else False): the residual blocks' convolutions of both generators read e4m3 operand copies
+        in the forward pass and in the input gradient of all six generator passes; bf16 (amp) mode only.
+        fp8_wgrad (default: cfg['mi355x']['fp8_wgrad'], else False): their weight gradients run on the same e4m3 copies; needs fp8.  The
+        output gradients' copies carry power-of-two scales here (GeneratorNet.fp8_pow2_scales), so on 16x16 maps at batch >= 64 the e4m3
+        weight gradient still sums several images per split.  GPass.wgrad8_layers / wgrad8_calls of self.P[...] tell which layers took
+        the e4m3 kernel.  Checkpoints do not change: e4m3 copies are derived state."""
         self.cfg, self.B, self.S = cfg, batch_size, image_size
         self.device = torch.device(device)
         amp = cfg["training"].get("amp", True) if amp is None else amp
         self.dtype = BF16 if amp else F32
+        mi = cfg.get("mi355x") or {}
+        self.fp8 = bool(mi.get("fp8", False) if fp8 is None else fp8)
+        if self.fp8 and not amp:
+            raise ValueError("fp8 convolutions exist in the bf16 (amp) mode only: fp32 is the parity mode")
+        self.fp8_wgrad = bool(mi.get("fp8_wgrad", False) if fp8_wgrad is None else fp8_wgrad)
+        if self.fp8_wgrad and not self.fp8:
+            raise ValueError("fp8_wgrad needs fp8: the e4m3 weight gradient reads the e4m3 operand copies that only the fp8 forward and "
+                             "input-gradient passes write")
         self.ops = ops if ops is not None else HipOps(self.device)
         if hasattr(self.ops, "bind"):
             self.ops.bind()
@@ -156,8 +171,9 @@ class CycleGANTrainer:
                 p.data = opt.params[pre + k]
         sub = lambda d, pre: {k[len(pre):]: v for k, v in d.items() if k.startswith(pre)}
         nb, ngf = G_A2B.n_blocks, G_A2B.ngf
-        self.Gab = GeneratorNet(self.ctx, sub(self.opt_G.params, "ab."), sub(self.opt_G.grads, "ab."), "basic", nb, ngf)
-        self.Gba = GeneratorNet(self.ctx, sub(self.opt_G.params, "ba."), sub(self.opt_G.grads, "ba."), "basic", nb, ngf)
+        g_kw = {"fp8": True, "fp8_wgrad": self.fp8_wgrad, "fp8_pow2_scales": True} if self.fp8 else {}
+        self.Gab = GeneratorNet(self.ctx, sub(self.opt_G.params, "ab."), sub(self.opt_G.grads, "ab."), "basic", nb, ngf, **g_kw)
+        self.Gba = GeneratorNet(self.ctx, sub(self.opt_G.params, "ba."), sub(self.opt_G.grads, "ba."), "basic", nb, ngf, **g_kw)
         self.DA, self.sn_A = self._d_net(D_A, self.opt_DA, self.d_buffers["D_A"])
         self.DB, self.sn_B = self._d_net(D_B, self.opt_DB, self.d_buffers["D_B"])
         B, S = self.B, self.S

@@ -423,9 +423,11 @@ class ConvLayer:
             out.append(ops.bias_grad(dy, self.cout, self.grad_b, ba, ctx.scratch("bias_ws", 256 * max(dy.C, 256))))
         return out
 
-    def wgrad8_call(self, x8: View, dy8: View, g_scale: Optional[torch.Tensor], ops=None) -> Optional[WgradCall]:
+    def wgrad8_call(self, x8: View, dy8: View, g_scale: Optional[torch.Tensor], ops=None, pow2: bool = False) -> Optional[WgradCall]:
         """The e4m3 weight-gradient call of wgrad8 (nsplit and variant set, no partial buffer yet), or None where the e4m3 range-patch kernel
-        does not qualify (gan_wgrad_patch_splits answers 0 for the GAN_FP8 descriptor).  Planning only: nothing is launched or allocated."""
+        does not qualify (gan_wgrad_patch_splits answers 0 for the GAN_FP8 descriptor).  Planning only: nothing is launched or allocated.
+        pow2: the caller promises that every g_scale[b] is a power of two (ops.quantize_fp8_pow2 wrote them); on many small maps a split
+        then covers -spi whole images, nsplit = B // -spi, as the bf16 path plans them."""
         assert not self.transposed and self.s == 1 and x8.dtype == FP8 and dy8.dtype == FP8 and x8.halo >= self.p
         assert x8.C == cpad(self.cin) and dy8.C == cpad(self.cout) and x8.B == dy8.B and (x8.H, x8.W) == (dy8.H, dy8.W)
         ctx, k, p = self.ctx, self.k, self.p
@@ -437,18 +439,24 @@ class ConvLayer:
             tapoff = self._wg_tapoff[key] = ctx.i32([(kh * x8.Wp + kw) * cx for kh in range(k) for kw in range(k)])
         call = WgradCall(dy8.B, dy8.H, dy8.W, cx, self.kk, dy8.C, 1, x8, x8.halo - p, x8.halo - p, 1, 1, tapoff, dy8, dy8.halo, dy8.halo, 1, 1, None,
                          max_tapoff=((k - 1) * x8.Wp + (k - 1)) * cx, g_scale=g_scale)
+        if pow2:
+            call.g_scale_pow2 = True
         spi = ops.wgrad_patch_splits(call)
-        if spi <= 0:
+        if spi == 0 or (spi < 0 and not pow2):
             return None
-        call.nsplit, call.variant = dy8.B * spi, 1
+        if spi < 0:      # several whole images per split: their scales ride in the MFMA's block scale
+            assert dy8.B % -spi == 0
+            call.nsplit, call.variant = dy8.B // -spi, 1
+        else:
+            call.nsplit, call.variant = dy8.B * spi, 1
         return call
 
-    def wgrad8(self, x8: View, dy8: View, g_scale: Optional[torch.Tensor], accumulate: bool, ops=None):
+    def wgrad8(self, x8: View, dy8: View, g_scale: Optional[torch.Tensor], accumulate: bool, ops=None, pow2: bool = False):
         """grad_w (+)= dL/dW on e4m3 operands: x8 = e4m3 copy of the layer input (unit scale, halo >= pad), dy8 = e4m3 copy of the output
         gradient with the per-image scales g_scale (device float[B]; None: 1).  conv_wgrad (dtype FP8, range-patch variant) + the bf16
         path's wgrad_reduce; no bias gradient.  Raises GanError where the e4m3 kernel does not qualify: the caller decides on the fallback."""
         ops = self.ctx.ops if ops is None else ops
-        call = self.wgrad8_call(x8, dy8, g_scale, ops)
+        call = self.wgrad8_call(x8, dy8, g_scale, ops, pow2)
         if call is None:
             raise GanError(f"weight gradient B{dy8.B} {dy8.H}x{dy8.W} C{x8.C}->{dy8.C} k{self.k}: the e4m3 range-patch kernel does not qualify")
         n, cx = dy8.C, x8.C

@@ -873,6 +873,7 @@ extern "C" int gan_conv_patch_ok(const gan_conv_desc* d) {
   const int t256 = (M_img + 255) / 256 * 256, t288 = (M_img + 287) / 288 * 288;
   const int rows = t256 < t288 ? t256 : t288;
   if (d->B * ((M_img + 255) / 256) <= 128) return 1;   // few tiles: the CUs are not full either way
+  if (fp8) return 1;                                   // e4m3 operands: no generic kernel to prefer (Basic_GAN at 64x64, batch 256, fp8 mode: the 18x18 domain)
   return 4 * M_img >= 3 * rows ? 1 : 0;
 }
 

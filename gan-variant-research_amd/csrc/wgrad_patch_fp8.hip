@@ -4,7 +4,12 @@
 //
 // x8 is an e4m3 view with unit scale (GPass.in8 / mid8), g8 the e4m3 copy of the output gradient with one scale per image; both already
 // exist in fp8 mode (the forward and the input gradient read them), so this launch adds no quantisation pass.  The per-image scale is
-// applied in fp32 when a split's accumulators are stored, so a split never crosses an image (no "several images per split" mode).
+// applied in fp32 when a split's accumulators are stored, so a split never crosses an image -- unless the caller promises power-of-two
+// scales (gan_wgrad_desc.g_scale_pow2, gan_quantize_fp8_pow2): the MULTI instantiation then sums a split over several whole images, as
+// the bf16 kernel does on many small maps, with the image's scale inside the MFMA.  The exponent field of a power-of-two float IS the E8M0
+// byte of the instruction's block scale (result x 2^(byte - 127), probed with exact integer data: tools/probe/fp8_mfma_scale.hip); a stage
+// of 128 pixels is one k-step inside one image, so its g operand carries exponent_byte(g_scale[b]) in all four bytes of a wave-uniform
+// register (lane / byte layout of the scale operand irrelevant), x keeps 0x7f, and one fp32 accumulator set sums over the images.
 //
 // Same decomposition as the bf16 kernel: a block owns 128 n x 64 c x all 9 taps and walks its pixel range in stages of 128 pixels; the
 // g tile (128 pixels x 128 B) and the x window (128/Wo + 2 image rows x 64 B per pixel) are staged once per stage by LDS-DMA.  A stage is
@@ -46,6 +51,7 @@ struct Wp8Args {
   int x_Hp, x_Wp, x_y0, x_x0;
   int g_Hp, g_Wp, g_C, g_y0, g_x0;
   int NBLK, CBLK;
+  int ipb;                           // MULTI: whole images per split (spi = 1, HoWo % KM == 0)
 };
 
 __device__ __forceinline__ void glds16q(const char* gbase, uint32_t goff, char* lds) {
@@ -56,8 +62,9 @@ __device__ __forceinline__ v2i_t tr8(const char* p) {
   return __builtin_amdgcn_ds_read_tr8_b64_v2i32((__attribute__((address_space(3))) v2i_t*)p);
 }
 
-template <bool RING>
+template <bool RING, bool MULTI = false>
 __global__ __launch_bounds__(512) void wgrad_patch_fp8_kernel(Wp8Args a) {
+  static_assert(!(RING && MULTI), "the row-ring variant takes one image per split");
   extern __shared__ __attribute__((aligned(1024))) char lds[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
 
@@ -65,10 +72,11 @@ __global__ __launch_bounds__(512) void wgrad_patch_fp8_kernel(Wp8Args a) {
   int bid = (gridDim.x & 7) == 0 ? (int)(blockIdx.x & 7) * (int)(gridDim.x >> 3) + (int)(blockIdx.x >> 3) : (int)blockIdx.x;
   const int cb = bid % a.CBLK; bid /= a.CBLK;
   const int nb = bid % a.NBLK; bid /= a.NBLK;
-  const int sp = bid;                                  // split index: image b = sp / spi, sub-range sp % spi
-  const int b = sp / a.spi, sub = sp - b * a.spi;
+  const int sp = bid;                                  // split index: image b = sp / spi, sub-range sp % spi -- MULTI: ipb whole images from sp * ipb
+  const int b = MULTI ? sp * a.ipb : sp / a.spi, sub = MULTI ? 0 : sp - b * a.spi;
   const int m_begin = sub * a.per, m_end = min(a.HoWo, m_begin + a.per);
-  const int nstage = (m_end - m_begin + KM - 1) / KM;
+  const int nst_img = (m_end - m_begin + KM - 1) / KM;   // stages per image
+  const int nstage = MULTI ? nst_img * a.ipb : nst_img;  // MULTI: the stage pipeline runs across the images of the split
   const int n0 = nb * NB, c0 = cb * CB;
 
   // ---- staging roles (LDS-DMA, lane-linear images, XOR applied on the SOURCE chunk)
@@ -95,10 +103,12 @@ __global__ __launch_bounds__(512) void wgrad_patch_fp8_kernel(Wp8Args a) {
       }
     }
   };
+  const int b_first = b;
   auto stage = [&](int st, int buf) {
     char* gt = lds + buf * (RING ? GT_BYTES : STAGE_BYTES);
     char* xw = gt + GT_BYTES;
-    const int m0 = m_begin + st * KM, ho0 = m0 >> a.lgWo;
+    const int img = MULTI ? st / nst_img : 0, b = b_first + img;      // MULTI: the image of this stage
+    const int m0 = m_begin + (st - img * nst_img) * KM, ho0 = m0 >> a.lgWo;
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
       int m = m0 + gr + 64 * i;
@@ -152,7 +162,13 @@ __global__ __launch_bounds__(512) void wgrad_patch_fp8_kernel(Wp8Args a) {
     __syncthreads();   // stage st landed (LDS-DMA drained + barrier); everyone is done with the other buffer
     char* gt = lds + (st & 1) * (RING ? GT_BYTES : STAGE_BYTES);
     const char* xw = RING ? ring : gt + GT_BYTES;
-    const int m0 = m_begin + st * KM;
+    const int img = MULTI ? st / nst_img : 0;
+    const int m0 = m_begin + (st - img * nst_img) * KM;
+    // MULTI: the g operand's block scale = the exponent byte of this stage's image scale (a power of two), wave-uniform, in all four bytes
+    int gsc = 0x7f7f7f7f;
+    if constexpr (MULTI) {
+      if (a.g_scale) gsc = (int)(((__builtin_bit_cast(uint32_t, a.g_scale[b + img]) >> 23) & 0xffu) * 0x01010101u);
+    }
     uint32_t so[3] = {0u, rowb, 2u * rowb};              // byte offset of tap row dy (RING: of its slot)
     if constexpr (RING) {
       const int iy0 = (m0 >> a.lgWo) + a.x_y0;
@@ -190,12 +206,12 @@ __global__ __launch_bounds__(512) void wgrad_patch_fp8_kernel(Wp8Args a) {
       if (t + 2 < NT) x_read(t + 2);
 #pragma unroll
       for (int i = 0; i < 4; ++i)
-        acc[i][t] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(av[i], xv[t % 3], acc[i][t], 0, 0, 0, 0x7f7f7f7f, 0, 0x7f7f7f7f);
+        acc[i][t] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(av[i], xv[t % 3], acc[i][t], 0, 0, 0, MULTI ? gsc : 0x7f7f7f7f, 0, 0x7f7f7f7f);
     }
   }
 
-  // D[row = n (fg*4+e)][col = c (fr)], times the image's dequantisation scale
-  const float sc = a.g_scale ? a.g_scale[b] : 1.f;
+  // D[row = n (fg*4+e)][col = c (fr)], times the image's dequantisation scale (MULTI: already applied, image by image, in the MFMAs)
+  const float sc = (!MULTI && a.g_scale) ? a.g_scale[b] : 1.f;
   float* part = a.part + (int64_t)sp * a.N * NT * a.Cx;
 #pragma unroll
   for (int i = 0; i < 4; ++i)
@@ -211,7 +227,8 @@ __global__ __launch_bounds__(512) void wgrad_patch_fp8_kernel(Wp8Args a) {
 }  // namespace
 
 // gan_wgrad_patch_splits for GAN_FP8 descriptors: splits per image (> 0), or 0 where the e4m3 kernel does not qualify -- also where the
-// bf16 query answers negative (several whole images per split): the per-image scale forbids a split that crosses images.
+// bf16 query answers negative (several whole images per split): the per-image scale forbids a split that crosses images, unless the
+// caller promises power-of-two scales (g_scale_pow2): then the bf16 query's answer, -(images per split), for the MULTI instantiation.
 int gan_wgrad_patch_fp8_splits(const gan_wgrad_desc* d) {
   if (d->dtype != GAN_FP8 || d->ntaps != NT || d->Cx % CB != 0 || d->N % NB != 0 || d->N != d->g_C) return 0;
   if (d->x_sy != 1 || d->x_sx != 1 || d->g_sy != 1 || d->g_sx != 1) return 0;
@@ -224,7 +241,7 @@ int gan_wgrad_patch_fp8_splits(const gan_wgrad_desc* d) {
   if (HoWo < 8 * KM && d->B * blocks_per_split > 256 && HoWo % KM == 0 && nrows * pitch <= RX) {
     int ipb = d->B * blocks_per_split / 256;
     while (ipb > 1 && d->B % ipb != 0) --ipb;
-    if (ipb > 1) return 0;
+    if (ipb > 1) return d->g_scale_pow2 ? -ipb : 0;
   }
   if (HoWo < 8 * KM && d->B > 64) return 0;
   int spi = (256 + d->B * blocks_per_split - 1) / (d->B * blocks_per_split);   // ~one block per CU
@@ -235,16 +252,19 @@ int gan_wgrad_patch_fp8_splits(const gan_wgrad_desc* d) {
 }
 
 int gan_wgrad_patch_fp8_launch(const gan_wgrad_desc* d, hipStream_t s) {
-  const int spi = gan_wgrad_patch_fp8_splits(d);
-  GAN_CHECK(spi > 0, "wgrad: variant=1, dtype GAN_FP8, but the descriptor does not qualify for the e4m3 range-patch kernel");
+  const int spi_want = gan_wgrad_patch_fp8_splits(d);
+  GAN_CHECK(spi_want != 0, "wgrad: variant=1, dtype GAN_FP8, but the descriptor does not qualify for the e4m3 range-patch kernel");
+  const int spi = spi_want > 0 ? spi_want : 1, ipb = spi_want > 0 ? 1 : -spi_want;
   GAN_CHECK(d->x && d->g && d->part, "wgrad_patch_fp8: null pointer");
   GAN_CHECK(((uintptr_t)d->x % 16) == 0 && ((uintptr_t)d->g % 16) == 0, "wgrad_patch_fp8: operand pointers must be 16-byte aligned");
   // the planner's split count must be the one gan_wgrad_patch_splits answered (the kernel indexes partial slabs and images by it)
-  GAN_CHECK(d->nsplit == d->B * spi, "wgrad_patch_fp8: nsplit=%d is not what gan_wgrad_patch_splits implies (%d x %d)", d->nsplit, d->B, spi);
+  // (several images per split only under g_scale_pow2: without the promise the query never answers negative)
+  GAN_CHECK(d->nsplit > 0 && (spi_want > 0 ? d->nsplit == d->B * spi : d->nsplit * ipb == d->B),
+            "wgrad_patch_fp8: nsplit=%d is not what gan_wgrad_patch_splits implies (B=%d, answer %d)", d->nsplit, d->B, spi_want);
   Wp8Args a;
   a.x = (const char*)d->x; a.g = (const char*)d->g; a.part = d->part; a.g_scale = d->g_scale;
   a.B = d->B; a.HoWo = d->Ho * d->Wo; a.Wo = d->Wo; a.lgWo = __builtin_ctz(d->Wo);
-  a.spi = spi;
+  a.spi = spi; a.ipb = ipb;
   int per = (a.HoWo + a.spi - 1) / a.spi;
   per = (per + KM - 1) / KM * KM;
   a.per = per;
@@ -266,11 +286,15 @@ int gan_wgrad_patch_fp8_launch(const gan_wgrad_desc* d, hipStream_t s) {
   const uint64_t dev_bit = 1ull << (dev & 63);
   if (!(attr_devs.load(std::memory_order_acquire) & dev_bit)) {
     if (hipFuncSetAttribute((const void*)wgrad_patch_fp8_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES) != hipSuccess ||
-        hipFuncSetAttribute((const void*)wgrad_patch_fp8_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES_RING) != hipSuccess)
+        hipFuncSetAttribute((const void*)wgrad_patch_fp8_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES_RING) != hipSuccess ||
+        hipFuncSetAttribute((const void*)wgrad_patch_fp8_kernel<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES) != hipSuccess)
       return gan_set_error(-2, "wgrad_patch_fp8: cannot raise the dynamic LDS limit to %d bytes", LDS_BYTES);
     attr_devs.fetch_or(dev_bit, std::memory_order_release);
   }
-  if (a.nrows * a.pitch > RX) hipLaunchKernelGGL(wgrad_patch_fp8_kernel<true>, dim3(a.NBLK * a.CBLK * d->nsplit), dim3(512), LDS_BYTES_RING, s, a);
+  const bool ring = a.nrows * a.pitch > RX;
+  GAN_CHECK(!(ipb > 1 && (ring || a.HoWo % KM != 0)), "wgrad_patch_fp8: several images per split need whole 128-pixel stages and the window variant");
+  if (ipb > 1) hipLaunchKernelGGL((wgrad_patch_fp8_kernel<false, true>), dim3(a.NBLK * a.CBLK * d->nsplit), dim3(512), LDS_BYTES, s, a);
+  else if (ring) hipLaunchKernelGGL(wgrad_patch_fp8_kernel<true>, dim3(a.NBLK * a.CBLK * d->nsplit), dim3(512), LDS_BYTES_RING, s, a);
   else hipLaunchKernelGGL(wgrad_patch_fp8_kernel<false>, dim3(a.NBLK * a.CBLK * d->nsplit), dim3(512), LDS_BYTES, s, a);
   if (hipGetLastError() != hipSuccess) return gan_set_error(-2, "wgrad_patch_fp8: launch failed");
   return 0;

@@ -73,7 +73,7 @@ class GeneratorNet(_Net):
     """9-block ResNet generator of both trainers (CUT: biased convs; Basic_GAN: bias-free but the last)."""
 
     def __init__(self, ctx, params, grads, style="cut", n_blocks=9, ngf=64, in_c=3, out_c=3, need_input_grad=True, reflect=True,
-                 block_act=ACT_RELU, fp8=False, fp8_wgrad=False):
+                 block_act=ACT_RELU, fp8=False, fp8_wgrad=False, fp8_pow2_scales=False):
         """reflect: `padding_type` 'reflect' (the configs' value) or 'zero'; block_act: the residual blocks' activation (ReLU in the
         configs, LeakyReLU(0.2) for activation='leaky_relu', generator_resnet_attn.py:60-66).
         fp8: the residual blocks' 3x3 convolutions (generator_resnet_attn.py:33,48 -- 88 % of the generator's FLOPs) read e4m3 copies of
@@ -81,10 +81,15 @@ class GeneratorNet(_Net):
         first / last layers and everything stored stay bf16 / fp32.  bf16 mode with reflect padding only.
         fp8_wgrad (needs fp8): the same convolutions' weight gradients run on those e4m3 copies too (ConvLayer.wgrad8: the layer input's
         copy of the forward pass and the output gradient's copy of the input gradient -- no further quantisation pass); layers whose maps
-        the e4m3 weight-gradient kernel does not take (under 128 pixels) keep the bf16 one.  GPass.wgrad8_layers tells which took which."""
+        the e4m3 weight-gradient kernel does not take (under 128 pixels) keep the bf16 one.  GPass.wgrad8_layers tells which took which.
+        fp8_pow2_scales (needs fp8): the per-image scales of the output gradients' e4m3 copies are powers of two (ops.quantize_fp8_pow2)
+        and the e4m3 weight gradients are told so: on many small maps (16x16 at batch >= 64) a split then sums over several whole images
+        instead of falling back to the bf16 kernel.  The fused CycleGAN trainer sets it; the CUT trainer keeps the amax / 448 scales."""
         super().__init__(ctx, params, grads)
         self.fp8 = bool(fp8)
         self.fp8_wgrad = bool(fp8_wgrad)
+        self.fp8_pow2_scales = bool(fp8_pow2_scales)
+        assert not self.fp8_pow2_scales or self.fp8, "fp8_pow2_scales is about the e4m3 gradient copies of the fp8 mode: it needs fp8=True"
         self.passes = []
         assert not self.fp8_wgrad or self.fp8, "fp8_wgrad reads the e4m3 operand copies that only the fp8 mode writes: it needs fp8=True"
         assert not self.fp8 or (ctx.dtype == BF16 and reflect and 4 * ngf >= 128 and (4 * ngf) % 128 == 0), "fp8 blocks: bf16 mode, reflect padding, >= 128 channels"
@@ -247,13 +252,16 @@ class GPass:
         # it waits for the side launches that read it; the program ends with a join.
         side = ops.side()
         readers = {}     # id(dy buffer) -> event recorded on the side stream after its last reader
+        # power-of-two scales of the e4m3 gradient copies (GeneratorNet.fp8_pow2_scales): their quantiser, and the promise to the weight gradient
+        quantize_grad = ops.quantize_fp8_pow2 if net.fp8_pow2_scales else ops.quantize_fp8
+        pow2_kw = {"pow2": True} if net.fp8_pow2_scales else {}
 
         def wgrad_side(conv, x, dy, bias_too, g_scale=None):
             ev = ops.new_event()
             prog.add(ops.record(ev))
             prog.add(side.wait(ev))
             if dy.dtype == FP8:      # e4m3 operands (fp8_wgrad): x is the layer input's e4m3 copy, dy the scaled copy of the output gradient
-                w8ops = conv.wgrad8(x, dy, g_scale, acc, ops=side)
+                w8ops = conv.wgrad8(x, dy, g_scale, acc, ops=side, **pow2_kw)
                 self.wgrad8_calls.append(w8ops[0].wgrad)
                 prog.add(w8ops)
             else:
@@ -270,7 +278,7 @@ class GPass:
         def use_wgrad8(k, which, conv, x8, dy8, sc8):
             if not net.fp8_wgrad:
                 return False
-            ok = conv.wgrad8_call(x8, dy8, sc8, ops=side) is not None
+            ok = conv.wgrad8_call(x8, dy8, sc8, ops=side, **pow2_kw) is not None
             self.wgrad8_layers[(k, which)] = ok
             return ok
 
@@ -365,7 +373,7 @@ class GPass:
                 if not w8:
                     wgrad_side(cb, self.mid[k], dyb, False)
                 before_write(dy8)      # fp8_wgrad: the side stream may still read this set (copy and scales) for block k + 2
-                prog.add(ops.quantize_fp8(dyb, dy8, am8, sc8))
+                prog.add(quantize_grad(dyb, dy8, am8, sc8))
                 if w8:                 # after the copy exists: the weight gradient reads it, not dyb
                     wgrad_side(cb, self.mid8[k], dy8, False, g_scale=sc8)
                 prog.add(cb.dgrad8(dy8, g_mid, sc8, padded_domain=rf))
@@ -389,7 +397,7 @@ class GPass:
                 if not w8:
                     wgrad_side(ca, self.acts[i - 1], dya, False)
                 before_write(dy8)
-                prog.add(ops.quantize_fp8(dya, dy8, am8, sc8))
+                prog.add(quantize_grad(dya, dy8, am8, sc8))
                 if w8:
                     wgrad_side(ca, self.in8[k], dy8, False, g_scale=sc8)
                 prog.add(ca.dgrad8(dy8, g_in_p, sc8, padded_domain=rf))

@@ -136,6 +136,8 @@ class WgradCall:
     max_tapoff: int = 0
     variant: int = 0          # 1: range-patch kernel (nsplit = B * splits per image); 2: 7x7 window kernel (nsplit = its block count)
     g_scale: Optional[torch.Tensor] = None   # e4m3 operands (x.dtype == FP8, variant 1): device float[B], per-image scale of g (None: 1)
+    g_scale_pow2: Optional[bool] = None      # e4m3 operands: True promises that every g_scale[b] is a power of two (quantize_fp8_pow2); a
+                                             # split may then cover several whole images (nsplit = B // -wgrad_patch_splits)
 
 
 Op = Callable[[], None]
@@ -353,6 +355,7 @@ class HipOps:
         d.part = c.part.data_ptr() if c.part is not None else None
         d.max_tapoff, d.variant = c.max_tapoff, c.variant
         d.g_scale = c.g_scale.data_ptr() if c.g_scale is not None else None
+        d.g_scale_pow2 = 1 if c.g_scale_pow2 else 0
         assert c.g.dtype == c.x.dtype and (c.g_scale is None or (c.x.dtype == FP8 and c.g_scale.dtype == torch.float32 and c.g_scale.numel() >= c.B))
         return d
 
@@ -505,6 +508,13 @@ class HipOps:
         """e4m3 copy of a whole buffer (halo included): unit scale, or per-image scale amax[b] / 448 written to scale_out[b]."""
         assert dst.dtype == FP8 and (src.B, src.Hp, src.Wp, src.C, src.halo) == (dst.B, dst.Hp, dst.Wp, dst.C, dst.halo)
         return self._call("gan_quantize_fp8", self._v(src), self._v(dst), self._p(amax), self._p(scale_out), self._s())
+
+    def quantize_fp8_pow2(self, src: View, dst: View, amax, scale_out) -> Op:
+        """quantize_fp8 with the per-image scale rounded up to a power of two, 2^ceil(log2(amax[b] / 448)): what WgradCall.g_scale_pow2
+        promises (the scale's exponent byte is the MFMA's block scale)."""
+        assert dst.dtype == FP8 and (src.B, src.Hp, src.Wp, src.C, src.halo) == (dst.B, dst.Hp, dst.Wp, dst.C, dst.halo)
+        assert amax is not None and scale_out is not None and amax.numel() >= src.B and scale_out.numel() >= src.B
+        return self._call("gan_quantize_fp8_pow2", self._v(src), self._v(dst), self._p(amax), self._p(scale_out), self._s())
 
     def fold_add(self, a: Optional[View], b: View, fold, out: View) -> Op:
         return self._call("gan_fold_add", self._v(a), self._v(b), int(fold), self._v(out), self._s())

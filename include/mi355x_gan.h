@@ -96,7 +96,9 @@ typedef struct gan_conv_desc {
  * the layer input, halo >= 1), g the e4m3 copy of the output gradient with one dequantisation scale per image, g_scale[b] -- and
  *   part[s][n][t][c] = g_scale[b(s)] * sum over the pixels m of split s of g8[m][n] * x8[pix(m) + tapoff[t]][c]
  * in fp32 on v_mfma_scale_f32_16x16x128_f8f6f4; a split never crosses an image, the scale is applied when its sums are stored.  part keeps
- * the slab layout, so gan_wgrad_reduce follows unchanged.  In fp8 mode it replaces the weight-gradient half of the backward() of the
+ * the slab layout, so gan_wgrad_reduce follows unchanged.  With g_scale_pow2 (every g_scale[b] a power of two: gan_quantize_fp8_pow2) a
+ * split may cover k whole images, part[s] = sum over the images b of split s of g_scale[b] * (image b's sum): the scale's exponent byte
+ * is the E8M0 block scale of the MFMA's g operand, one 128-pixel k-step never leaves an image.  In fp8 mode it replaces the weight-gradient half of the backward() of the
  * residual blocks' nn.Conv2d(256, 256, 3) under autocast (GAN_Variant1/models/generator_resnet_attn.py:33,48). */
 typedef struct gan_wgrad_desc {
   int32_t dtype;
@@ -115,6 +117,9 @@ typedef struct gan_wgrad_desc {
   int32_t variant;               /* 0: generic kernel, any nsplit; 1: range-patch kernel, nsplit = B * gan_wgrad_patch_splits() (or B / -that);
                                     2: 7x7 window kernel, nsplit = gan_wgrad_win7_splits() */
   const float* g_scale;          /* dtype GAN_FP8: device float[B], per-image scale of g (NULL = 1); other dtypes: ignored */
+  int32_t g_scale_pow2;          /* dtype GAN_FP8, variant 1: the caller promises that every g_scale[b] is a normal power of two (0: no
+                                    promise, one image per split); then nsplit may be B / k as gan_wgrad_patch_splits answers */
+  int32_t _pad;
 } gan_wgrad_desc;
 
 const char* gan_last_error(void);
@@ -156,8 +161,9 @@ int gan_conv_wgrad(const gan_wgrad_desc* d, void* stream);
 /* splits per image the range-patch weight-gradient kernel wants (0: the descriptor does not qualify: bf16, 9 taps, stride 1,
  * Cx % 64 == 0, N % 128 == 0, one 128-pixel stage's window span fits LDS); pure host-side predicate for the planner.
  * A NEGATIVE value -k means k whole images per split (many small maps, e.g. 16x16 at batch 256): nsplit = B / k.
- * dtype GAN_FP8: the same question for the e4m3 kernel (e4m3 x and g, 9 taps, stride 1, Cx % 64 == 0, N % 128 == 0); never negative --
- * where the bf16 answer would be, it is 0 and the planner keeps the bf16 kernel for that launch. */
+ * dtype GAN_FP8: the same question for the e4m3 kernel (e4m3 x and g, 9 taps, stride 1, Cx % 64 == 0, N % 128 == 0); without
+ * g_scale_pow2 never negative -- where the bf16 answer would be, it is 0 and the planner keeps the bf16 kernel for that launch; with
+ * g_scale_pow2 the bf16 query's negative answer for the same geometry. */
 int gan_wgrad_patch_splits(const gan_wgrad_desc* d);
 /* grad[(a*I2 + b)*KK + khw[t]] (+)= sum_s part[s][n][t][c], (a,b) = swap ? (c,n) : (n,c), for n<N_real, c<C_real, khw[t]>=0 */
 /* slabs the 7x7 window weight-gradient kernels write (0: the descriptor does not qualify: bf16, 49 row-major taps, stride 1, and
@@ -192,6 +198,13 @@ int gan_weight_scale_batch(const gan_pack_desc* descs, int n, void* stream);
  * (unit scale: InstanceNorm outputs are O(1)).  amax != NULL: device float[B] holding max|src| per image (gan_in_bwd_amax); then
  * scale_out[b] = amax[b] / 448 (1 if zero) and dst = e4m3(src / scale_out[b]).  Values are clamped to +-448 before conversion. */
 int gan_quantize_fp8(const gan_view* src, const gan_view* dst, const float* amax, float* scale_out, void* stream);
+/* gan_quantize_fp8 with power-of-two scales (amax and scale_out required): scale_out[b] = 2^ceil(log2(amax[b] / 448)), computed on the bit
+ * pattern of amax[b] (biased exponent e, mantissa field m: e - 8, plus 1 if m > 0x600000 i.e. 1.m > 1.75; clamped to 1 .. 254 so the
+ * scale is a normal float), 1 for amax[b] == 0; dst = e4m3(src / scale_out[b]), clamped to +-448 first.  amax / 448 <= scale < 2 amax / 448:
+ * at most one of e4m3's bits of range is given up, and the scale's exponent byte is an E8M0 block scale (gan_wgrad_desc.g_scale_pow2).
+ * The e4m3 copies of the residual blocks' output gradients in the fused CycleGAN trainer's fp8 mode: the operand copies that
+ * torch.autocast would make for the backward() of Basic_GAN/src/models.py:12,16 (nn.Conv2d(dim, dim, 3) of ResnetBlock), were it e4m3. */
+int gan_quantize_fp8_pow2(const gan_view* src, const gan_view* dst, const float* amax, float* scale_out, void* stream);
 /* bias gradient: grad[n] (+)= sum over logical pixels of g[...,n], n < N_real (column sums of dY) */
 int gan_bias_grad(const gan_view* g, int N_real, float* grad, int accumulate, float* ws, void* stream);
 
