@@ -30,8 +30,10 @@ __device__ __forceinline__ float bf2f(bf16_t v) { return __builtin_bit_cast(floa
 __device__ __forceinline__ bf16_t f2bf(float f) { return __builtin_bit_cast(bf16_t, (__bf16)f); }
 
 // OCP e4m3 (GAN_FP8): v_cvt_pk_fp8_f32 rounds to nearest even and turns out-of-range values into NaN, so operands are clamped to +-448
+// (+-inf included).  fminf(fmaxf(v, -448), 448) alone (one v_med3_f32) turns a NaN into -448 -- the operand copy of a poisoned buffer
+// would be finite -- so a NaN is passed around the clamp (one compare and one select more) and becomes an e4m3 NaN byte.
 __device__ __forceinline__ uint32_t f2e4m3x4(float a, float b, float c, float d) {
-  auto cl = [](float v) { return fminf(fmaxf(v, -448.f), 448.f); };
+  auto cl = [](float v) { return v != v ? v : fminf(fmaxf(v, -448.f), 448.f); };
   uint32_t r = __builtin_amdgcn_cvt_pk_fp8_f32(cl(a), cl(b), 0u, false);
   return __builtin_amdgcn_cvt_pk_fp8_f32(cl(c), cl(d), r, true);
 }

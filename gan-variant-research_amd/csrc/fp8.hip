@@ -4,7 +4,7 @@
 // activation / output-gradient and weight operands on v_mfma_scale_f32_16x16x128_f8f6f4 (conv_patch.hip); everything else --
 // results, InstanceNorm, master weights, optimiser -- keeps its precision.  This file makes the copies:
 //   gan_quantize_fp8        activation / gradient buffer -> e4m3 buffer of the same geometry (halo included), unit scale or a
-//                           per-image scale from max|x| (gan_in_bwd_amax);
+//                           per-image scale from max|x| (gan_in_bwd_amax), never below 2^-126;
 //   gan_quantize_fp8_pow2   the same with the per-image scale rounded up to a power of two: its exponent byte is then an E8M0 block scale
 //                           of the scaled MFMA (wgrad_patch_fp8.hip sums a split over several images with it);
 //   gan_weight_scale_batch  per-tensor weight scale max|W| / 448 for gan_pack_weight(_batch) with dtype GAN_FP8.
@@ -13,6 +13,11 @@
 
 namespace {
 
+// smallest scale gan_quantize_fp8 (per image) and gan_weight_scale_batch (per tensor) write: amax / 448 below it is subnormal (or flushed) and its reciprocal overflows -- the
+// copy of a merely negligible image would be 0 * inf = NaN.  2^-126 is what pow2_scale's exponent clamp gives, and its reciprocal is exact.
+constexpr float MIN_SCALE = 0x1p-126f;
+// The scales are true quotients, amax / 448.f: a product with the rounded reciprocal of 448 is up to 1.4 ulp away from amax / 448.
+
 // src chunk pair (2 x 16 B of bf16 = 16 elements) -> one 16-byte e4m3 chunk
 __global__ __launch_bounds__(256) void quantize_bf16_kernel(const u32x4_t* __restrict__ src, u32x4_t* __restrict__ dst, int64_t nchunk16, int64_t per_image16,
                                                            const float* __restrict__ amax, float* __restrict__ scale_out) {
@@ -20,7 +25,7 @@ __global__ __launch_bounds__(256) void quantize_bf16_kernel(const u32x4_t* __res
     float inv = 1.f;
     if (amax) {
       const int b = (int)(i / per_image16);
-      const float am = amax[b], sc = am > 0.f ? am * (1.f / 448.f) : 1.f;
+      const float am = amax[b], sc = am > 0.f ? fmaxf(am / 448.f, MIN_SCALE) : 1.f;
       inv = 1.f / sc;
       if (i == (int64_t)b * per_image16) scale_out[b] = sc;
     }
@@ -43,7 +48,7 @@ __global__ __launch_bounds__(256) void quantize_f32_kernel(const f32x4_t* __rest
     float inv = 1.f;
     if (amax) {
       const int b = (int)(i / per_image16);
-      const float am = amax[b], sc = am > 0.f ? am * (1.f / 448.f) : 1.f;
+      const float am = amax[b], sc = am > 0.f ? fmaxf(am / 448.f, MIN_SCALE) : 1.f;
       inv = 1.f / sc;
       if (i == (int64_t)b * per_image16) scale_out[b] = sc;
     }
@@ -95,7 +100,7 @@ __global__ __launch_bounds__(256) void quantize_pow2_kernel(const u32x4_t* __res
   }
 }
 
-// one block per pack descriptor: *scale = max|W| / 448
+// one block per pack descriptor: *scale = max|W| / 448, never below 2^-126
 __global__ __launch_bounds__(1024) void weight_scale_kernel(const gan_pack_desc* __restrict__ descs) {
   const gan_pack_desc D = descs[blockIdx.x];
   if (D.dtype != GAN_FP8 || !D.scale) return;
@@ -109,7 +114,7 @@ __global__ __launch_bounds__(1024) void weight_scale_kernel(const gan_pack_desc*
   __syncthreads();
   if (threadIdx.x == 0) {
     for (int w = 1; w < 16; ++w) m = fmaxf(m, sh[w]);
-    *D.scale = m > 0.f ? m * (1.f / 448.f) : 1.f;
+    *D.scale = m > 0.f ? fmaxf(m / 448.f, MIN_SCALE) : 1.f;      // the same floor as the per-image scales: 1 / *scale stays finite
   }
 }
 

@@ -465,8 +465,10 @@ __global__ __launch_bounds__(NTHR, 6) void in_bwd_apply_kernel(DView x, const fl
         float xa, xb, ga, gb;
         Pairs<T>::get(xr[u], j, xa, xb);
         Pairs<T>::get(gr[u], j, ga, gb);
-        ga = act_mask<ACT>(ga, xa, ca[0]) * ca[1] + (xa * ca[2] + ca[3]);
-        gb = act_mask<ACT>(gb, xb, cb[0]) * cb[1] + (xb * cb[2] + cb[3]);
+        // explicit fmas: left to the compiler's contraction, the AMAX instantiation got separate multiplies and adds where the plain one
+        // got fmas, and its dx differed from gan_in_bwd_bias_deferred's in the last bit
+        ga = fmaf(act_mask<ACT>(ga, xa, ca[0]), ca[1], fmaf(xa, ca[2], ca[3]));
+        gb = fmaf(act_mask<ACT>(gb, xb, cb[0]), cb[1], fmaf(xb, cb[2], cb[3]));
         if (AMAX && ((live >> u) & 1)) mx = fmaxf(mx, fmaxf(fabsf(ga), fabsf(gb)));
         Pairs<T>::set(gr[u], j, ga, gb);
       }

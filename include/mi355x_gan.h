@@ -21,7 +21,11 @@ extern "C" {
 
 /* GAN_FP8: OCP e4m3 ("e4m3fn": no infinities, max 448), one byte per element.  Only operand COPIES of the bottleneck convolutions are
  * fp8 (BASELINE.json configs[4]): gan_quantize_fp8 writes activations / output gradients, gan_pack_weight the weights; every result,
- * statistic and master weight stays bf16 / fp32.  An fp8 view has C % 16 == 0. */
+ * statistic and master weight stays bf16 / fp32.  An fp8 view has C % 16 == 0.
+ * Every producer of e4m3 bytes (gan_quantize_fp8, gan_quantize_fp8_pow2, the y8 copy of gan_in_apply_parts_fp8, gan_pack_weight_batch
+ * with dtype GAN_FP8) converts the same way: the value, divided by its scale, is clamped to +-448 (+-inf included), then rounded to
+ * nearest, ties to even, the sign of zero kept; a NaN element becomes an e4m3 NaN byte (0x7F / 0xFF), never a finite one, so the operand
+ * copy of a poisoned buffer is poisoned too. */
 enum { GAN_F32 = 0, GAN_BF16 = 1, GAN_FP8 = 2 };
 enum { GAN_ACT_NONE = 0, GAN_ACT_RELU = 1, GAN_ACT_LRELU = 2, GAN_ACT_TANH = 3 };
 /* GAN_HALO_REPLICATE (nn.ReplicationPad2d, generator_resnet_attn.py:26-27,45-46: an option the shipped configs do not use): accepted by
@@ -190,13 +194,17 @@ typedef struct gan_pack_desc {
 } gan_pack_desc;
 int gan_pack_weight_batch(const gan_pack_desc* descs, int n, int total_blocks, void* stream);
 /* For every descriptor with dtype GAN_FP8: *scale = max|src| / 448 over the whole master weight ((swap ? C_real : N_real) * I2 * KK
- * floats), 1 if the weight is all zero -- the per-tensor dequantisation scale of the e4m3 operand copy.  One launch for the batch
+ * floats), 1 if the weight is all zero, never below 2^-126 (as gan_quantize_fp8's scales: the reciprocal stays finite) -- the per-tensor
+ * dequantisation scale of the e4m3 operand copy.  One launch for the batch
  * (same DEVICE descriptor array as gan_pack_weight_batch, which it precedes). */
 int gan_weight_scale_batch(const gan_pack_desc* descs, int n, void* stream);
 /* e4m3 operand copy of an activation / gradient buffer: dst (GAN_FP8) has exactly src's (GAN_BF16 / GAN_F32) geometry (B, Hp, Wp, C,
  * halo) and the WHOLE allocation is converted, halo included (the producer already materialised it).  amax == NULL: dst = e4m3(src)
  * (unit scale: InstanceNorm outputs are O(1)).  amax != NULL: device float[B] holding max|src| per image (gan_in_bwd_amax); then
- * scale_out[b] = amax[b] / 448 (1 if zero) and dst = e4m3(src / scale_out[b]).  Values are clamped to +-448 before conversion. */
+ * scale_out[b] = amax[b] / 448 (1 if zero) and dst = e4m3(src / scale_out[b]).  Values are clamped to +-448 before conversion.
+ * The scale is never below 2^-126: for 0 < amax[b] < 448 * 2^-126 the quotient would be subnormal and its reciprocal infinite, so it is
+ * clamped to 2^-126 (what gan_quantize_fp8_pow2's exponent clamp gives) and the image's bytes are finite, small ones.  Only amax[0 .. B)
+ * and scale_out[0 .. B) are read / written.  A NaN INSIDE amax is outside this contract. */
 int gan_quantize_fp8(const gan_view* src, const gan_view* dst, const float* amax, float* scale_out, void* stream);
 /* gan_quantize_fp8 with power-of-two scales (amax and scale_out required): scale_out[b] = 2^ceil(log2(amax[b] / 448)), computed on the bit
  * pattern of amax[b] (biased exponent e, mantissa field m: e - 8, plus 1 if m > 0x600000 i.e. 1.m > 1.75; clamped to 1 .. 254 so the
@@ -260,7 +268,11 @@ int gan_in_bwd_bias_deferred(const gan_view* x, const float* stats, int act, con
                              const gan_view* dx, float* ws, float* bias_part, void* stream);
 int gan_bias_finalize_batch(const gan_bias_part_desc* descs, int n, int total_blocks, void* stream);
 /* gan_in_bwd_bias_deferred (bias_part may be NULL: no bias gradient) that also leaves max|dx| per image in amax[B] (device floats,
- * combined with atomic max on the bit patterns -- order-independent, hence deterministic): the scale of dx's e4m3 copy */
+ * combined with atomic max on the bit patterns -- order-independent, hence deterministic): the scale of dx's e4m3 copy.
+ * amax[b] is the maximum over the INTERIOR of image b (the halo of dx is neither written nor read) of the fp32 values BEFORE the store
+ * rounds them to dx's dtype: for GAN_F32 it is exactly max|dx[b]|, for GAN_BF16 it may differ from the maximum of the stored dx by one bf16
+ * rounding (2^-8 relative).  Every call overwrites amax[0 .. B) (the reset is part of the op); dx and bias_part are bit for bit what
+ * gan_in_bwd_bias_deferred / gan_in_bwd write.  What amax holds when dx contains a NaN is not specified. */
 int gan_in_bwd_amax(const gan_view* x, const float* stats, int act, const gan_view* gy, int fold, const gan_view* dx, float* ws,
                     float* bias_part, float* amax, void* stream);
 int gan_fold_add(const gan_view* a, const gan_view* b, int fold, const gan_view* out, void* stream);

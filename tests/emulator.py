@@ -65,7 +65,7 @@ def _store(view, vals, padded_coords=False):
 
 
 def _e4m3(v):
-    """fp32 -> OCP e4m3 (round to nearest even, clamped to +-448) -> fp32: what an e4m3 byte holds."""
+    """fp32 -> OCP e4m3 (round to nearest even, clamped to +-448, NaN stays NaN) -> fp32: what an e4m3 byte holds."""
     return v.float().clamp(-448.0, 448.0).to(torch.float8_e4m3fn).float()
 
 
@@ -168,8 +168,9 @@ class EmuOps:
             a()
             b()
             if y8 is not None:        # the kernel converts its fp32 values, not the rounded bf16 ones
-                b32()
-                y8.padded().copy_(y32.padded().clamp(-448.0, 448.0).to(torch.float8_e4m3fn).view(torch.uint8))
+                b32()            # ... and writes y8 where it writes y: the padded extent with a reflect halo, else the interior (NaN stays NaN)
+                part = (lambda v: v.padded()) if halo_mode == HALO_REFLECT else (lambda v: v.nhwc())
+                part(y8).copy_(part(y32).clamp(-448.0, 448.0).to(torch.float8_e4m3fn).view(torch.uint8))
         return op
 
     def in_stats_from_parts(self, parts, nparts, B, Cc, HW, eps, stats):
@@ -314,7 +315,7 @@ class EmuOps:
         def op():
             if dtype == 2:      # e4m3 copy: per-tensor scale max|W| / 448 (statement of gan_weight_scale_batch + the fp8 pack)
                 am = float(src.abs().max())
-                scale.fill_(am / 448.0 if am > 0 else 1.0)
+                scale.fill_(max(am / 448.0, 2.0 ** -126) if am > 0 else 1.0)      # the floor of gan_quantize_fp8's scales
             out = torch.zeros(Nw, ntaps, Cin)
             s = src.reshape(-1).float()
             n_idx = torch.arange(N_real)[:, None]
@@ -376,20 +377,25 @@ class EmuOps:
                 _store(y, v)
         return op
 
+    @staticmethod
+    def _in_bwd_value(x, stats, act, gy, fold, g2):
+        """(B,H,W,C) fp32: the InstanceNorm backward before it is rounded to dx's dtype"""
+        st = stats.view(x.B, 1, 1, x.C, 2)
+        xh = (x.nhwc().float() - st[..., 0]) * st[..., 1]
+        g = _fold(gy, fold)
+        if g2 is not None:
+            g = g + g2.nhwc().float()
+        if act == ACT_RELU:
+            g = g * (xh > 0)
+        elif act == ACT_LRELU:
+            g = torch.where(xh > 0, g, 0.2 * g)
+        m1 = g.mean((1, 2), keepdim=True)
+        m2 = (g * xh).mean((1, 2), keepdim=True)
+        return st[..., 1] * (g - m1 - xh * m2)
+
     def in_bwd(self, x, stats, act, gy, fold, g2, dx, ws):
         def op():
-            st = stats.view(x.B, 1, 1, x.C, 2)
-            xh = (x.nhwc().float() - st[..., 0]) * st[..., 1]
-            g = _fold(gy, fold)
-            if g2 is not None:
-                g = g + g2.nhwc().float()
-            if act == ACT_RELU:
-                g = g * (xh > 0)
-            elif act == ACT_LRELU:
-                g = torch.where(xh > 0, g, 0.2 * g)
-            m1 = g.mean((1, 2), keepdim=True)
-            m2 = (g * xh).mean((1, 2), keepdim=True)
-            _store(dx, st[..., 1] * (g - m1 - xh * m2))
+            _store(dx, self._in_bwd_value(x, stats, act, gy, fold, g2))
         return op
 
     def in_bwd_bias(self, x, stats, act, gy, fold, g2, dx, ws, bias_grad, bias_n, accumulate):
@@ -443,19 +449,24 @@ class EmuOps:
         return op
 
     def in_bwd_amax(self, x, stats, act, gy, fold, dx, ws, bias_part, amax):
-        """Statement of gan_in_bwd_amax: gan_in_bwd_bias_deferred plus max|dx| per image."""
+        """Statement of gan_in_bwd_amax: gan_in_bwd_bias_deferred plus max|dx| per image over the interior, overwritten by every call.
+        The maximum is taken of the fp32 values BEFORE the store rounds them to dx's dtype (in bf16 it may differ from the maximum of
+        the stored dx by one bf16 rounding, 2^-8 relative)."""
         inner = self.in_bwd_bias_deferred(x, stats, act, gy, fold, None, dx, ws, bias_part) if bias_part is not None else self.in_bwd(x, stats, act, gy, fold, None, dx, ws)
 
         def op():
             inner()
-            amax[:x.B].copy_(dx.nhwc().float().abs().amax((1, 2, 3)))
+            amax[:x.B].copy_(self._in_bwd_value(x, stats, act, gy, fold, None).abs().amax((1, 2, 3)))
         return op
 
     def quantize_fp8(self, src, dst, amax=None, scale_out=None):
+        """Statement of gan_quantize_fp8.  The per-image scale amax / 448 is never below 2^-126 (a normal float whose reciprocal is
+        finite), 1 for amax == 0; +-inf and everything beyond +-448 become +-448, a NaN becomes an e4m3 NaN byte (torch's cast agrees:
+        tests/test_fp8_producers_cpu.py compares it with tests/e4m3_ref.py)."""
         def op():
             v = src.padded().float()
             if amax is not None:
-                sc = torch.where(amax[:src.B] > 0, amax[:src.B] / 448.0, torch.ones_like(amax[:src.B]))
+                sc = torch.where(amax[:src.B] > 0, (amax[:src.B] / 448.0).clamp_min(2.0 ** -126), torch.ones_like(amax[:src.B]))
                 scale_out[:src.B].copy_(sc)
                 v = v / sc.view(src.B, 1, 1, 1)
             dst.padded().copy_(v.clamp(-448.0, 448.0).to(torch.float8_e4m3fn).view(torch.uint8))
