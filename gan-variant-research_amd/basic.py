@@ -13,7 +13,7 @@ import torch.nn as nn
 
 from ._lib import BF16, F32, HALO_ZERO
 from .cut import FusedAdam, _adam_state_dict, _load_adam_state_dict
-from .nets import DiscriminatorNet, GeneratorNet, PartialSNDiscriminatorNet, SpectralNorm
+from .nets import DiscriminatorNet, GeneratorNet, PartialSNDiscriminatorNet, SpectralNorm, fp8_switches
 from .runtime import Ctx, HipOps, Program, View
 
 
@@ -135,14 +135,7 @@ class CycleGANTrainer:
         self.device = torch.device(device)
         amp = cfg["training"].get("amp", True) if amp is None else amp
         self.dtype = BF16 if amp else F32
-        mi = cfg.get("mi355x") or {}
-        self.fp8 = bool(mi.get("fp8", False) if fp8 is None else fp8)
-        if self.fp8 and not amp:
-            raise ValueError("fp8 convolutions exist in the bf16 (amp) mode only: fp32 is the parity mode")
-        self.fp8_wgrad = bool(mi.get("fp8_wgrad", False) if fp8_wgrad is None else fp8_wgrad)
-        if self.fp8_wgrad and not self.fp8:
-            raise ValueError("fp8_wgrad needs fp8: the e4m3 weight gradient reads the e4m3 operand copies that only the fp8 forward and "
-                             "input-gradient passes write")
+        self.fp8, self.fp8_wgrad = fp8_switches(cfg.get("mi355x"), amp, fp8, fp8_wgrad)
         self.ops = ops if ops is not None else HipOps(self.device)
         if hasattr(self.ops, "bind"):
             self.ops.bind()

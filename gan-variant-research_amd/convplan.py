@@ -14,7 +14,7 @@ from typing import List, Optional, Tuple
 import torch
 
 from ._lib import ACT_NONE, BF16, F32, FP8, GanError
-from .runtime import ConvCall, Ctx, View, WgradCall, cpad
+from .runtime import IN_WS_CHUNKS, ConvCall, Ctx, View, WgradCall, cpad
 
 
 def _nw(n_real: int) -> int:
@@ -23,6 +23,18 @@ def _nw(n_real: int) -> int:
     if n_real <= 64:
         return 64
     return (n_real + 127) // 128 * 128
+
+
+def _patch_split(B: int, spi: int, grouped_ok: bool = True) -> Optional[Tuple[int, int]]:
+    """(nsplit, variant) of a weight gradient on the range-patch kernel from gan_wgrad_patch_splits' answer: spi > 0 is splits per image;
+    spi < 0 is -spi whole images per split (many small maps), honoured only when `grouped_ok` -- always for bf16 operands, for e4m3
+    operands only under the power-of-two promise (the images' scales then ride in the MFMA's block scale).  None: not that kernel."""
+    if spi > 0:
+        return B * spi, 1
+    if spi < 0 and grouped_ok:
+        assert B % -spi == 0
+        return B // -spi, 1
+    return None
 
 
 class _Pack:
@@ -63,14 +75,18 @@ class _Pack:
             self.scale8 = torch.ones(1, dtype=torch.float32, device=self.ctx.device)
         return self._wf8
 
+    def _patch_tiles(self, c: ConvCall):
+        """Tile of a call the range-patch kernel takes (c.w / c.w_frag set): pixels, then output channels per tile."""
+        c.tile_rows = self.ctx.ops.conv_patch_tile_rows(c)
+        c.tile_cols = self.ctx.ops.conv_patch_tile_cols(c)
+
     def finalize8(self, c: ConvCall) -> ConvCall:
         """fp8 operands (c.x is an e4m3 view): the range-patch kernel or nothing -- there is no other fp8 convolution."""
         assert c.x.dtype == FP8
         c.w, c.w_frag, c.w_scale = self.wf8, True, self.scale8
         if not self.ctx.ops.conv_patch_ok(c):
             raise GanError(f"fp8 convolution: B{c.B} {c.Ho}x{c.Wo} Cin{c.Cin} taps{c.ntaps} does not qualify for the range-patch kernel")
-        c.tile_rows = self.ctx.ops.conv_patch_tile_rows(c)
-        c.tile_cols = self.ctx.ops.conv_patch_tile_cols(c)
+        self._patch_tiles(c)
         return c
 
     def pack_ops(self, master: torch.Tensor, scale: Optional[torch.Tensor] = None):
@@ -91,8 +107,7 @@ class _Pack:
         c.w = None
         if self.ctx.ops.conv_patch_ok(c):
             c.w, c.w_frag = self.wf, True
-            c.tile_rows = self.ctx.ops.conv_patch_tile_rows(c)
-            c.tile_cols = self.ctx.ops.conv_patch_tile_cols(c)
+            self._patch_tiles(c)
         else:
             c.w, c.w_frag = self.w, False
             # the 64 -> 3 channel 7x7 layers: the window kernel reads the same row-major weight copy
@@ -187,7 +202,7 @@ class ConvLayer:
         if bias is not None and cpad(self.cout) != self.cout:
             self.bias_k = torch.zeros(_nw(self.cout), dtype=torch.float32, device=ctx.device)
         self.wg_khw = ctx.i32([t[2] for t in alltaps])
-        self._wg_tapoff = {}
+        self._wg_tapoffs = {}
         self._pairs = {}
         self.bias_pair = None     # [bias | bias] for paired phases (allocated with the first paired plan)
         self.pack_scale = None    # spectral norm: device sigma; the operand copies hold weight / sigma (nets.SpectralNorm)
@@ -223,61 +238,47 @@ class ConvLayer:
         return out
 
     # ------------------------------------------------------------------ forward
+    def _fwd_call(self, x: View, y: View, act: int, mask: Optional[View], bias: Optional[torch.Tensor], in_scale: Optional[torch.Tensor] = None) -> ConvCall:
+        """The planned forward call of a regular (non-transposed) convolution; e4m3 operands when `x` is an e4m3 view."""
+        s, p, pk = self.s, self.p, self.fwd_pack
+        assert (y.H, y.W) == ((x.H + 2 * p - self.k) // s + 1, (x.W + 2 * p - self.k) // s + 1) and x.halo >= p, (x.H, x.W, y.H, y.W, x.halo, p)
+        finalize = pk.finalize8 if x.dtype == FP8 else pk.finalize
+        return finalize(ConvCall(x.B, y.H, y.W, pk.cred, pk.ntaps, pk.nw, min(pk.nw, y.C), x, x.halo - p, x.halo - p, s, s, pk.tapoff(x.Wp), None,
+                                 bias, y, y.halo, y.halo, 1, 1, act, mask, mask.halo if mask else 0, mask.halo if mask else 0,
+                                 pk.max_tapoff(x.Wp), in_scale=in_scale))
+
+    def _fuse_stats(self, call: ConvCall, stats_ws: Optional[torch.Tensor]):
+        """Lets the epilogue of the forward `call` write the InstanceNorm partials of its output into stats_ws if the launch can;
+        self.stats_parts = their count per image (0: not fused).  Range-patch and 7x7 window launches can; an e4m3 call is always
+        fragment-major (range-patch), so the condition needs no case of its own."""
+        self.stats_parts = 0
+        if stats_ws is not None and (call.w_frag or call.win7 is not None) and call.Nst == call.out.C:
+            n = self.ctx.ops.conv_stats_parts(call)
+            if 0 < n and call.B * n * call.out.C * 2 <= stats_ws.numel():
+                call.stats, self.stats_parts = stats_ws, n
+
     def fwd(self, x: View, y: View, act: int = ACT_NONE, mask: Optional[View] = None, use_bias: bool = True,
             stats_ws: Optional[torch.Tensor] = None):
         """Forward launches.  stats_ws: if given and the launch can, its epilogue also writes the InstanceNorm partials of `y`
         there; self.stats_parts then holds their count per image (0: not fused, the caller runs in_stats)."""
         assert x.C == cpad(self.cin) and y.C == cpad(self.cout) and x.B == y.B, (x.C, self.cin, y.C, self.cout)
-        ops = self.ctx.ops
         self.stats_parts = 0
+        bias = self.bias_k if use_bias else None
         if not self.transposed:
-            k, s, p = self.k, self.s, self.p
-            ho, wo = (x.H + 2 * p - k) // s + 1, (x.W + 2 * p - k) // s + 1
-            assert (ho, wo) == (y.H, y.W) and x.halo >= p, (ho, wo, y.H, y.W, x.halo, p)
-            pk = self.fwd_pack
-            call = pk.finalize(ConvCall(x.B, ho, wo, pk.cred, pk.ntaps, pk.nw, min(pk.nw, y.C), x, x.halo - p, x.halo - p, s, s,
-                                        pk.tapoff(x.Wp), None, self.bias_k if use_bias else None, y, y.halo, y.halo, 1, 1, act, mask,
-                                        mask.halo if mask else 0, mask.halo if mask else 0, pk.max_tapoff(x.Wp)))
-            if stats_ws is not None and (call.w_frag or call.win7 is not None) and call.Nst == y.C:
-                n = ops.conv_stats_parts(call)
-                if 0 < n and x.B * n * y.C * 2 <= stats_ws.numel():
-                    call.stats, self.stats_parts = stats_ws, n
+            call = self._fwd_call(x, y, act, mask, bias)
+            self._fuse_stats(call, stats_ws)
             self.last_call = call          # the planned forward call (tests read the tile the planner chose)
-            return [ops.conv_igemm(call)]
+            return [self.ctx.ops.conv_igemm(call)]
         assert (y.H, y.W) == (2 * x.H, 2 * x.W)
-        return self._phased(self.fwd_packs, x, y, act, self.bias_k if use_bias else None, mask)
+        return self._phased(self.fwd_packs, x, y, act, bias, mask)
 
     def fwd8(self, x8: View, y: View, act: int = ACT_NONE, stats_ws: Optional[torch.Tensor] = None, in_scale: Optional[torch.Tensor] = None):
         """Forward on e4m3 operands (x8 = gan_quantize_fp8 copy of the input, unit scale unless in_scale; the weight copy is this
         layer's fp8 pack); the result `y` is bf16.  Stride-1 convolutions on the range-patch kernel (the residual 3x3 256->256 layers)."""
         assert not self.transposed and self.s == 1 and x8.dtype == FP8 and y.dtype == BF16 and x8.C == cpad(self.cin) and y.C == cpad(self.cout)
-        ops, k, p = self.ctx.ops, self.k, self.p
-        assert (y.H, y.W) == (x8.H + 2 * p - k + 1, x8.W + 2 * p - k + 1) and x8.halo >= p
-        pk = self.fwd_pack
-        call = pk.finalize8(ConvCall(x8.B, y.H, y.W, pk.cred, pk.ntaps, pk.nw, min(pk.nw, y.C), x8, x8.halo - p, x8.halo - p, 1, 1, pk.tapoff(x8.Wp), None,
-                                     self.bias_k, y, y.halo, y.halo, 1, 1, act, None, 0, 0, pk.max_tapoff(x8.Wp), in_scale=in_scale))
-        self.stats_parts = 0
-        if stats_ws is not None and call.Nst == y.C:
-            n = ops.conv_stats_parts(call)
-            if 0 < n and x8.B * n * y.C * 2 <= stats_ws.numel():
-                call.stats, self.stats_parts = stats_ws, n
-        return [ops.conv_igemm(call)]
-
-    def dgrad8(self, dy8: View, dx: View, in_scale: torch.Tensor, padded_domain: bool = False):
-        """Input gradient on e4m3 operands: dy8 = per-image-scaled e4m3 copy of dY (zero halo), in_scale its scales; dx is bf16."""
-        assert not self.transposed and self.s == 1 and dy8.dtype == FP8 and dx.dtype == BF16
-        ops, k, p = self.ctx.ops, self.k, self.p
-        pk = self.dgrad_packs[0]
-        if padded_domain:
-            assert dx.halo == p and dy8.halo >= k - 1
-            gh, gw, oy, iy = dx.Hp, dx.Wp, 0, dy8.halo - (k - 1)
-        else:
-            assert dy8.halo >= k - 1 - p
-            gh, gw, oy, iy = dx.H, dx.W, dx.halo, dy8.halo - (k - 1) + p
-        call = pk.finalize8(ConvCall(dy8.B, gh, gw, pk.cred, pk.ntaps, pk.nw, min(pk.nw, dx.C), dy8, iy, iy, 1, 1, pk.tapoff(dy8.Wp), None, None, dx,
-                                     oy, oy, 1, 1, ACT_NONE, None, 0, 0, pk.max_tapoff(dy8.Wp), in_scale=in_scale))
-        call.alg_pixels = dy8.H * dy8.W
-        return [ops.conv_igemm(call)]
+        call = self._fwd_call(x8, y, act, None, self.bias_k, in_scale)
+        self._fuse_stats(call, stats_ws)
+        return [self.ctx.ops.conv_igemm(call)]
 
     def _pair_packs(self, packs):
         """Lazily built _PairPack per phase row (see there); None when the layer does not qualify."""
@@ -319,13 +320,36 @@ class ConvLayer:
         return out
 
     # ------------------------------------------------------------------ input gradient
+    def _dgrad_call(self, dy: View, dx: View, padded_domain: bool, mask: Optional[View] = None, in_scale: Optional[torch.Tensor] = None) -> ConvCall:
+        """The planned input-gradient call of a stride-1 convolution: flipped taps over the zero-haloed dy, on the input's own domain or on
+        its padded one (the gradient on the halo too); e4m3 operands when `dy` is an e4m3 view (in_scale: its per-image scales)."""
+        k, p, pk = self.k, self.p, self.dgrad_packs[0]
+        if padded_domain:
+            assert dx.halo == p and dy.halo >= k - 1 and mask is None
+            gh, gw, oy, iy = dx.Hp, dx.Wp, 0, dy.halo - (k - 1)
+        else:
+            assert dy.halo >= k - 1 - p
+            gh, gw, oy, iy = dx.H, dx.W, dx.halo, dy.halo - (k - 1) + p
+        assert gh == dy.H + k - 1 - (0 if padded_domain else 2 * p), (gh, dy.H, k, p)
+        finalize = pk.finalize8 if dy.dtype == FP8 else pk.finalize
+        call = finalize(ConvCall(dy.B, gh, gw, pk.cred, pk.ntaps, pk.nw, min(pk.nw, dx.C), dy, iy, iy, 1, 1, pk.tapoff(dy.Wp), None, None, dx,
+                                 oy, oy, 1, 1, ACT_NONE, mask, mask.halo if mask else 0, mask.halo if mask else 0, pk.max_tapoff(dy.Wp),
+                                 in_scale=in_scale))
+        call.alg_pixels = dy.H * dy.W      # the reference op's M is the forward output (dy) pixel count, not the (padded) input domain
+        return call
+
+    def dgrad8(self, dy8: View, dx: View, in_scale: torch.Tensor, padded_domain: bool = False):
+        """Input gradient on e4m3 operands: dy8 = per-image-scaled e4m3 copy of dY (zero halo), in_scale its scales; dx is bf16."""
+        assert not self.transposed and self.s == 1 and dy8.dtype == FP8 and dx.dtype == BF16
+        return [self.ctx.ops.conv_igemm(self._dgrad_call(dy8, dx, padded_domain, in_scale=in_scale))]
+
     def dgrad(self, dy: View, dx: View, mask: Optional[View] = None, padded_domain: bool = False, chain: Optional[dict] = None):
         """dx <- dL/d(input).  padded_domain: also produce the gradient on the input's (reflect) halo; the consumer folds it.
         chain (stride-1 layers on the padded domain, bf16) = {"operand": y, "ws": parts}: the launch's epilogue also leaves the two sums of
         the InstanceNorm backward behind a ReLU whose saved output is y (reflect halo p) -- gan_conv_desc.stats_mode 1; self.chain_parts =
         partials per image written to ws.  Raises GanError if the launch cannot carry it (ask can_chain first)."""
         assert dy.C == cpad(self.cout) and dx.C == cpad(self.cin) and dy.B == dx.B
-        ops, k, p = self.ctx.ops, self.k, self.p
+        ops, p = self.ctx.ops, self.p
         self.chain_parts = 0
         assert chain is None or (self.s == 1 and not self.transposed and padded_domain and mask is None)
         if self.transposed:  # regular strided conv over dy
@@ -335,17 +359,7 @@ class ConvLayer:
                                             pk.tapoff(dy.Wp), None, None, dx, dx.halo, dx.halo, 1, 1, ACT_NONE, mask,
                                             mask.halo if mask else 0, mask.halo if mask else 0, pk.max_tapoff(dy.Wp))))]
         if self.s == 1:
-            pk = self.dgrad_packs[0]
-            if padded_domain:
-                assert dx.halo == p and dy.halo >= k - 1 and mask is None
-                gh, gw, oy, iy = dx.Hp, dx.Wp, 0, dy.halo - (k - 1)
-            else:
-                assert dy.halo >= k - 1 - p
-                gh, gw, oy, iy = dx.H, dx.W, dx.halo, dy.halo - (k - 1) + p
-            assert gh == dy.H + k - 1 - (0 if padded_domain else 2 * p), (gh, dy.H, k, p)
-            call = pk.finalize(ConvCall(dy.B, gh, gw, pk.cred, pk.ntaps, pk.nw, min(pk.nw, dx.C), dy, iy, iy, 1, 1, pk.tapoff(dy.Wp), None,
-                                        None, dx, oy, oy, 1, 1, ACT_NONE, mask, mask.halo if mask else 0, mask.halo if mask else 0, pk.max_tapoff(dy.Wp)))
-            call.alg_pixels = dy.H * dy.W      # the reference op's M is the forward output (dy) pixel count, not the (padded) input domain
+            call = self._dgrad_call(dy, dx, padded_domain, mask)
             if chain is not None:
                 opd = chain["operand"]
                 assert opd.C == dx.C and opd.B == dx.B and (opd.H, opd.W) == (dx.H, dx.W) and opd.halo == p
@@ -353,7 +367,7 @@ class ConvLayer:
                 call.stats, call.stats_mode = chain["ws"], 1
                 n = ops.conv_stats_parts(call) if call.w_frag else 0
                 if n <= 0 or dy.B * n * dx.C * 2 > chain["ws"].numel():
-                    raise GanError(f"input gradient B{dy.B} {gh}x{gw} C{dx.C}: the launch cannot carry the backward chain (ask can_chain first)")
+                    raise GanError(f"input gradient B{dy.B} {call.Ho}x{call.Wo} C{dx.C}: the launch cannot carry the backward chain (ask can_chain first)")
                 self.chain_parts = n
             return [ops.conv_igemm(call)]
         assert not padded_domain and (dx.H, dx.W) == (2 * dy.H, 2 * dy.W)
@@ -365,7 +379,7 @@ class ConvLayer:
         if self.transposed or self.s != 1 or self.ctx.dtype != BF16 or dx.halo != self.p or dy.halo < self.k - 1:
             return False
         try:      # planning only: dx stands in for the operand (same geometry), nothing is launched
-            self.dgrad(dy, dx, padded_domain=True, chain={"operand": dx, "ws": self.ctx.scratch("bwd_parts_a", dx.B * 96 * dx.C * 2)})
+            self.dgrad(dy, dx, padded_domain=True, chain={"operand": dx, "ws": self.ctx.scratch("bwd_parts_a", dx.B * IN_WS_CHUNKS * dx.C * 2)})
         except GanError:
             return False
         return self.chain_parts > 0
@@ -378,46 +392,46 @@ class ConvLayer:
             ns -= 1
         return ns
 
+    def _wg_tapoff(self, xo: View) -> torch.Tensor:
+        key = (xo.Wp, xo.C)
+        t = self._wg_tapoffs.get(key)
+        if t is None:
+            t = self._wg_tapoffs[key] = self.ctx.i32([(kh * xo.Wp + kw) * xo.C for kh in range(self.k) for kw in range(self.k)])
+        return t
+
+    def _wgrad_call(self, xo: View, g: View, stride: int, g_scale: Optional[torch.Tensor] = None) -> WgradCall:
+        """The weight-gradient call over the rows of `g` against the taps of `xo` (nsplit, variant and partial buffer not set yet)."""
+        k, p = self.k, self.p
+        return WgradCall(g.B, g.H, g.W, xo.C, self.kk, g.C, 1, xo, xo.halo - p, xo.halo - p, stride, stride, self._wg_tapoff(xo), g, g.halo, g.halo,
+                         1, 1, None, max_tapoff=((k - 1) * xo.Wp + (k - 1)) * xo.C, g_scale=g_scale)
+
+    def _wgrad_launches(self, call: WgradCall, ops, accumulate: bool):
+        """Scratch partials for the planned `call`, then its launch and the reduction of the partials into grad_w."""
+        n_real, c_real = (self.cin, self.cout) if self.transposed else (self.cout, self.cin)
+        call.part = part = self.ctx.scratch("wgrad_part", call.nsplit * call.N * self.kk * call.Cx)
+        return [ops.conv_wgrad(call),
+                ops.wgrad_reduce(part, call.nsplit, call.N, self.kk, call.Cx, n_real, c_real, False, c_real, self.kk, self.wg_khw, self.grad_w, accumulate)]
+
     def wgrad(self, x: View, dy: View, accumulate: bool, bias_too: bool = True, ops=None, bias_accumulate: Optional[bool] = None):
         """grad_w (+)= dL/dW from the layer input `x` and the output gradient `dy`.  ops: op layer to build the launches on
         (default: the context's; the backward programs pass the second-stream layer).  bias_accumulate: for grad_b (default: accumulate)."""
-        ctx, k, p = self.ctx, self.k, self.p
+        ctx = self.ctx
         ops = ctx.ops if ops is None else ops
-        epc = 4 if ctx.dtype == F32 else 8
-        if not self.transposed:
-            g, xo, stride = dy, x, self.s
-            assert x.halo >= p
-            n_real, c_real, i2 = self.cout, self.cin, self.cin
-        else:  # roles swap: rows run over the layer input, the "x operand" is dy
-            g, xo, stride = x, dy, 2
-            assert dy.halo >= p
-            n_real, c_real, i2 = self.cin, self.cout, self.cout
-        n, cx = g.C, xo.C
-        ktot = self.kk * cx
-        m = g.B * g.H * g.W
-        jt, ntl = 16 * epc, (16 if n <= 16 else (128 if ctx.dtype == BF16 else 64))
-        key = (xo.Wp, cx)
-        tapoff = self._wg_tapoff.get(key)
-        if tapoff is None:
-            tapoff = ctx.i32([(kh * xo.Wp + kw) * cx for kh in range(k) for kw in range(k)])
-            self._wg_tapoff[key] = tapoff
-        call = WgradCall(g.B, g.H, g.W, cx, self.kk, n, 1, xo, xo.halo - p, xo.halo - p, stride, stride, tapoff, g, g.halo, g.halo, 1, 1, None,
-                         max_tapoff=((k - 1) * xo.Wp + (k - 1)) * cx)
+        # transposed: roles swap -- rows run over the layer input, the "x operand" is dy
+        g, xo, stride = (x, dy, 2) if self.transposed else (dy, x, self.s)
+        assert xo.halo >= self.p
+        call = self._wgrad_call(xo, g, stride)
         spi = ops.wgrad_patch_splits(call)
         w7 = ops.wgrad_win7_splits(call) if spi == 0 else 0
-        if spi > 0:      # range-patch kernel: spi splits per image
-            call.nsplit, call.variant = g.B * spi, 1
-        elif spi < 0:    # ... or, on many small maps, -spi whole images per split
-            assert g.B % -spi == 0
-            call.nsplit, call.variant = g.B // -spi, 1
-        elif w7 > 0:     # the 64 -> 3 channel 7x7 layer: one slab per persistent block
+        split = _patch_split(g.B, spi)
+        if split is not None:      # range-patch kernel
+            call.nsplit, call.variant = split
+        elif w7 > 0:               # the 64 -> 3 channel 7x7 layer: one slab per persistent block
             call.nsplit, call.variant = w7, 2
         else:
-            call.nsplit = self._nsplit(m, -(-ktot // jt), -(-n // ntl), n <= 16)
-        ns = call.nsplit
-        call.part = part = ctx.scratch("wgrad_part", ns * n * ktot)
-        out = [ops.conv_wgrad(call),
-               ops.wgrad_reduce(part, ns, n, self.kk, cx, n_real, c_real, False, i2, self.kk, self.wg_khw, self.grad_w, accumulate)]
+            jt, ntl = 16 * (4 if ctx.dtype == F32 else 8), (16 if g.C <= 16 else (128 if ctx.dtype == BF16 else 64))
+            call.nsplit = self._nsplit(g.B * g.H * g.W, -(-self.kk * xo.C // jt), -(-g.C // ntl), g.C <= 16)
+        out = self._wgrad_launches(call, ops, accumulate)
         if bias_too and self.grad_b is not None:
             ba = accumulate if bias_accumulate is None else bias_accumulate
             out.append(ops.bias_grad(dy, self.cout, self.grad_b, ba, ctx.scratch("bias_ws", 256 * max(dy.C, 256))))
@@ -430,25 +444,14 @@ class ConvLayer:
         then covers -spi whole images, nsplit = B // -spi, as the bf16 path plans them."""
         assert not self.transposed and self.s == 1 and x8.dtype == FP8 and dy8.dtype == FP8 and x8.halo >= self.p
         assert x8.C == cpad(self.cin) and dy8.C == cpad(self.cout) and x8.B == dy8.B and (x8.H, x8.W) == (dy8.H, dy8.W)
-        ctx, k, p = self.ctx, self.k, self.p
-        ops = ctx.ops if ops is None else ops
-        cx = x8.C
-        key = (x8.Wp, cx)
-        tapoff = self._wg_tapoff.get(key)
-        if tapoff is None:
-            tapoff = self._wg_tapoff[key] = ctx.i32([(kh * x8.Wp + kw) * cx for kh in range(k) for kw in range(k)])
-        call = WgradCall(dy8.B, dy8.H, dy8.W, cx, self.kk, dy8.C, 1, x8, x8.halo - p, x8.halo - p, 1, 1, tapoff, dy8, dy8.halo, dy8.halo, 1, 1, None,
-                         max_tapoff=((k - 1) * x8.Wp + (k - 1)) * cx, g_scale=g_scale)
+        ops = self.ctx.ops if ops is None else ops
+        call = self._wgrad_call(x8, dy8, 1, g_scale)
         if pow2:
             call.g_scale_pow2 = True
-        spi = ops.wgrad_patch_splits(call)
-        if spi == 0 or (spi < 0 and not pow2):
+        split = _patch_split(dy8.B, ops.wgrad_patch_splits(call), grouped_ok=pow2)
+        if split is None:
             return None
-        if spi < 0:      # several whole images per split: their scales ride in the MFMA's block scale
-            assert dy8.B % -spi == 0
-            call.nsplit, call.variant = dy8.B // -spi, 1
-        else:
-            call.nsplit, call.variant = dy8.B * spi, 1
+        call.nsplit, call.variant = split
         return call
 
     def wgrad8(self, x8: View, dy8: View, g_scale: Optional[torch.Tensor], accumulate: bool, ops=None, pow2: bool = False):
@@ -459,7 +462,4 @@ class ConvLayer:
         call = self.wgrad8_call(x8, dy8, g_scale, ops, pow2)
         if call is None:
             raise GanError(f"weight gradient B{dy8.B} {dy8.H}x{dy8.W} C{x8.C}->{dy8.C} k{self.k}: the e4m3 range-patch kernel does not qualify")
-        n, cx = dy8.C, x8.C
-        call.part = part = self.ctx.scratch("wgrad_part", call.nsplit * n * self.kk * cx)
-        return [ops.conv_wgrad(call),
-                ops.wgrad_reduce(part, call.nsplit, n, self.kk, cx, self.cout, self.cin, False, self.cin, self.kk, self.wg_khw, self.grad_w, accumulate)]
+        return self._wgrad_launches(call, ops, accumulate)

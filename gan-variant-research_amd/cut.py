@@ -20,7 +20,7 @@ import torch
 import torch.nn as nn
 
 from ._lib import ACT_NONE, BF16, F32, HALO_NONE, HALO_ZERO
-from .nets import GeneratorNet, MultiscaleDiscriminatorNet, SpectralNorm
+from .nets import GeneratorNet, MultiscaleDiscriminatorNet, SpectralNorm, fp8_switches
 from .runtime import ADAM_CHUNK, Ctx, HipOps, Program, View, cpad
 
 NCE_LAYERS_DEFAULT = (0, 4, 8, 12, 16)
@@ -432,13 +432,7 @@ class CutTrainer:
         self.device = torch.device(device)
         amp = config.get("amp", True) if amp is None else amp
         self.amp = AMPContext(amp)
-        self.fp8 = bool((config.get("mi355x") or {}).get("fp8", False) if fp8 is None else fp8)
-        if self.fp8 and not amp:
-            raise ValueError("fp8 convolutions exist in the bf16 (amp) mode only: fp32 is the parity mode")
-        self.fp8_wgrad = bool((config.get("mi355x") or {}).get("fp8_wgrad", False) if fp8_wgrad is None else fp8_wgrad)
-        if self.fp8_wgrad and not self.fp8:
-            raise ValueError("fp8_wgrad needs fp8: the e4m3 weight gradient reads the e4m3 operand copies that only the fp8 forward and "
-                             "input-gradient passes write")
+        self.fp8, self.fp8_wgrad = fp8_switches(config.get("mi355x"), amp, fp8, fp8_wgrad)
         self.ops = ops if ops is not None else HipOps(self.device)
         if hasattr(self.ops, "bind"):
             self.ops.bind()                 # one stream for this trainer's launches and its torch-side copies / events, from now on

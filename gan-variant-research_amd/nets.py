@@ -69,6 +69,20 @@ class _Net:
         return self.ctx.scratch("in_ws", B * IN_WS_CHUNKS * C * 2 + B * C * 2 + (B * 1024 + 32) * C)
 
 
+def fp8_switches(mi_cfg: Optional[dict], amp: bool, fp8: Optional[bool], fp8_wgrad: Optional[bool]):
+    """(fp8, fp8_wgrad) of a fused trainer: the keyword where given, else the config's 'mi355x' section, else False.  fp8 needs amp and
+    fp8_wgrad needs fp8 (GeneratorNet has what they mean): ValueError otherwise."""
+    mi = mi_cfg or {}
+    fp8 = bool(mi.get("fp8", False) if fp8 is None else fp8)
+    if fp8 and not amp:
+        raise ValueError("fp8 convolutions exist in the bf16 (amp) mode only: fp32 is the parity mode")
+    fp8_wgrad = bool(mi.get("fp8_wgrad", False) if fp8_wgrad is None else fp8_wgrad)
+    if fp8_wgrad and not fp8:
+        raise ValueError("fp8_wgrad needs fp8: the e4m3 weight gradient reads the e4m3 operand copies that only the fp8 forward and "
+                         "input-gradient passes write")
+    return fp8, fp8_wgrad
+
+
 class GeneratorNet(_Net):
     """9-block ResNet generator of both trainers (CUT: biased convs; Basic_GAN: bias-free but the last)."""
 
@@ -180,18 +194,17 @@ class GPass:
             out = self.acts[i] if out is None else out
             halo = self.halo_mode(i) if out is self.acts[i] else net.pad_mode
             ws = net.in_ws(self.B, raw.C)
-            if conv is not None and conv.stats_parts:     # the convolution's epilogue already wrote per-tile (sum, sum of squares)
-                if conv.stats_parts <= 16:          # few tiles: the apply pass adds them up itself (no statistics launch at all)
-                    prog.add(ops.in_apply_parts(raw, ws, conv.stats_parts, IN_EPS, stats, act, residual, out, halo, out8))
-                    return
-                prog.add(ops.in_stats_from_parts(ws, conv.stats_parts, self.B, raw.C, raw.H * raw.W, IN_EPS, stats))
-            else:
+            parts = conv.stats_parts if conv is not None else 0     # per-tile (sum, sum of squares) the convolution's epilogue already wrote
+            if 0 < parts <= 16:      # few tiles: the apply pass adds them up itself (no statistics launch at all)
+                prog.add(ops.in_apply_parts(raw, ws, parts, IN_EPS, stats, act, residual, out, halo, out8))
+            elif parts > 16:
+                prog.add(ops.in_stats_from_parts(ws, parts, self.B, raw.C, raw.H * raw.W, IN_EPS, stats))
+                prog.add(ops.in_apply(raw, stats, act, residual, out, halo))
+                if out8 is not None:
+                    prog.add(ops.quantize_fp8(out, out8))
+            else:                    # no fused partials: a partial pass of its own
                 prog.add(ops.in_partial(raw, ws))
                 prog.add(ops.in_apply_parts(raw, ws, ops.in_partial_count(raw), IN_EPS, stats, act, residual, out, halo, out8))
-                return
-            prog.add(ops.in_apply(raw, stats, act, residual, out, halo))
-            if out8 is not None:
-                prog.add(ops.quantize_fp8(out, out8))
 
         prog.add(net.c_init.fwd(self.x0, self.raw[0], stats_ws=net.in_ws(self.B, self.raw[0].C)))
         norm(0, self.raw[0], self.stats[0], ACT_RELU, conv=net.c_init)
@@ -204,20 +217,15 @@ class GPass:
             i = 3 + k
             if i > self.last:
                 return prog
-            ca, cb = net.c_blk[k]
-            ra, rb = self.raw[i]
-            sa, sb = self.stats[i]
-            if net.fp8:      # the e4m3 operand copies come out of the InstanceNorm passes that produce the bf16 tensors
-                prog.add(ca.fwd8(self.in8[k], ra, stats_ws=net.in_ws(self.B, ra.C)))
-                norm(i, ra, sa, net.block_act, out=self.mid[k], conv=ca, out8=self.mid8[k])
-                prog.add(cb.fwd8(self.mid8[k], rb, stats_ws=net.in_ws(self.B, rb.C)))
-                nxt8 = self.in8[k + 1] if (k + 1 < nb and i + 1 <= self.last) else None
-                norm(i, rb, sb, ACT_NONE, residual=self.acts[i - 1], conv=cb, out8=nxt8)
-                continue
-            prog.add(ca.fwd(self.acts[i - 1], ra, stats_ws=net.in_ws(self.B, ra.C)))
-            norm(i, ra, sa, net.block_act, out=self.mid[k], conv=ca)
-            prog.add(cb.fwd(self.mid[k], rb, stats_ws=net.in_ws(self.B, rb.C)))
-            norm(i, rb, sb, ACT_NONE, residual=self.acts[i - 1], conv=cb)
+            (ca, cb), (ra, rb), (sa, sb) = net.c_blk[k], self.raw[i], self.stats[i]
+            # fp8: the convolutions read the e4m3 operand copies, which come out of the InstanceNorm passes that produce the bf16 tensors
+            f8 = net.fp8
+            conv_fwd = lambda conv, x, y: (conv.fwd8 if f8 else conv.fwd)(x, y, stats_ws=net.in_ws(self.B, y.C))
+            prog.add(conv_fwd(ca, self.in8[k] if f8 else self.acts[i - 1], ra))
+            norm(i, ra, sa, net.block_act, out=self.mid[k], conv=ca, out8=self.mid8[k] if f8 else None)
+            prog.add(conv_fwd(cb, self.mid8[k] if f8 else self.mid[k], rb))
+            nxt8 = self.in8[k + 1] if (f8 and k + 1 < nb and i + 1 <= self.last) else None
+            norm(i, rb, sb, ACT_NONE, residual=self.acts[i - 1], conv=cb, out8=nxt8)
         for j in range(2):
             i = 3 + nb + j
             if i > self.last:
@@ -353,59 +361,47 @@ class GPass:
             prog.add(net.c_up[j].dgrad(dy, g_cur))
             g_fold = False
             i -= 1
+        def block_conv_bwd(k, which, conv, raw, stats, act, gy, fold, chain=False, parts=None):
+            """Backward of convolution `which` ("a": first, "b": second) of residual block k behind its InstanceNorm: the norm's backward of
+            gy into the convolution's output gradient dy, the weight gradient on the side stream, the input gradient dx on the (padded)
+            domain.  parts: see inbwd.  chain: dx's epilogue also sums for the ReLU'd norm in front of the convolution, whose saved output
+            (the convolution's input) carries the reflect halo.  -> (dx, `parts` for that norm's backward or None)."""
+            x = self.mid[k] if which == "b" else self.acts[2 + k]
+            dy = net.gbuf(f"dy_blk_{which}{k % 2}", B, raw.H, raw.W, raw.C, 2)   # two sets, alternating: the side stream reads them one block late
+            before_write(dy)
+            dx = net.gbuf("g_blk_p", B, raw.H, raw.W, raw.C, 1)
+            x8 = dy8 = am8 = sc8 = chained = None
+            if net.fp8:
+                # input gradients on e4m3 operands: the norm backward leaves max|dY| per image, the copy is scaled by it.  With fp8_wgrad the
+                # side stream reads the copy and its scales one block late as well: then the sets alternate like the dy buffers
+                x8 = (self.mid8 if which == "b" else self.in8)[k]
+                dy8, am8, sc8 = self._fp8_grad_bufs(B, raw.H, raw.W, raw.C, f"{which}{k % 2}" if net.fp8_wgrad else None)
+            w8 = use_wgrad8(k, which, conv, x8, dy8, sc8)
+            inbwd(raw, stats, act, gy, fold, dy, conv, amax=am8, parts=parts)
+            if not w8:                 # the bf16 weight gradient reads dy: it goes before the quantiser
+                wgrad_side(conv, x, dy, False)
+            if net.fp8:
+                before_write(dy8)      # fp8_wgrad: the side stream may still read this set (copy and scales) for block k + 2
+                prog.add(quantize_grad(dy, dy8, am8, sc8))
+                if w8:                 # after the copy exists: the e4m3 weight gradient reads it, not dy
+                    wgrad_side(conv, x8, dy8, False, g_scale=sc8)
+                prog.add(conv.dgrad8(dy8, dx, sc8, padded_domain=rf))
+            elif chain:
+                pa = ctx.scratch("bwd_parts_a", B * IN_WS_CHUNKS * raw.C * 2)
+                prog.add(conv.dgrad(dy, dx, padded_domain=True, chain={"operand": x, "ws": pa}))
+                chained = (pa, conv.chain_parts, 1)
+            else:
+                prog.add(conv.dgrad(dy, dx, padded_domain=rf))
+            return dx, chained
+
         # ---- residual blocks
         while i >= 3:
             k = i - 3
             hook(i, g_cur)
-            ca, cb = net.c_blk[k]
-            ra, rb = self.raw[i]
-            sa, sb = self.stats[i]
-            c4, h4, w4 = ra.C, ra.H, ra.W
-            dyb = net.gbuf(f"dy_blk_b{k % 2}", B, h4, w4, c4, 2)   # two sets, alternating: the side stream reads them one block late
-            before_write(dyb)
-            g_mid = net.gbuf("g_blk_p", B, h4, w4, c4, 1)
-            a_parts = None
-            if net.fp8:
-                # input gradients on e4m3 operands: the norm backward leaves max|dY| per image, the copy is scaled by it
-                dy8, am8, sc8 = self._fp8_grad_bufs(B, h4, w4, c4, f"b{k % 2}" if net.fp8_wgrad else None)
-                w8 = use_wgrad8(k, "b", cb, self.mid8[k], dy8, sc8)
-                inbwd(rb, sb, ACT_NONE, g_cur, False, dyb, cb, amax=am8)
-                if not w8:
-                    wgrad_side(cb, self.mid[k], dyb, False)
-                before_write(dy8)      # fp8_wgrad: the side stream may still read this set (copy and scales) for block k + 2
-                prog.add(quantize_grad(dyb, dy8, am8, sc8))
-                if w8:                 # after the copy exists: the weight gradient reads it, not dyb
-                    wgrad_side(cb, self.mid8[k], dy8, False, g_scale=sc8)
-                prog.add(cb.dgrad8(dy8, g_mid, sc8, padded_domain=rf))
-            else:
-                inbwd(rb, sb, ACT_NONE, g_cur, False, dyb, cb)
-                wgrad_side(cb, self.mid[k], dyb, False)
-                if use_chain:      # the epilogue also sums for the ReLU'd norm, whose saved output mid[k] carries the reflect halo
-                    pa = ctx.scratch("bwd_parts_a", B * IN_WS_CHUNKS * c4 * 2)
-                    prog.add(cb.dgrad(dyb, g_mid, padded_domain=True, chain={"operand": self.mid[k], "ws": pa}))
-                    a_parts = (pa, cb.chain_parts, 1)
-                else:
-                    prog.add(cb.dgrad(dyb, g_mid, padded_domain=rf))
-            dya = net.gbuf(f"dy_blk_a{k % 2}", B, h4, w4, c4, 2)
-            before_write(dya)
-            g_in_p = net.gbuf("g_blk_p", B, h4, w4, c4, 1)
-            if net.fp8:
-                if net.fp8_wgrad:
-                    dy8, am8, sc8 = self._fp8_grad_bufs(B, h4, w4, c4, f"a{k % 2}")
-                w8 = use_wgrad8(k, "a", ca, self.in8[k], dy8, sc8)
-                inbwd(ra, sa, net.block_act, g_mid, rf, dya, ca, amax=am8)
-                if not w8:
-                    wgrad_side(ca, self.acts[i - 1], dya, False)
-                before_write(dy8)
-                prog.add(quantize_grad(dya, dy8, am8, sc8))
-                if w8:
-                    wgrad_side(ca, self.in8[k], dy8, False, g_scale=sc8)
-                prog.add(ca.dgrad8(dy8, g_in_p, sc8, padded_domain=rf))
-            else:
-                inbwd(ra, sa, net.block_act, g_mid, rf, dya, ca, parts=a_parts)
-                wgrad_side(ca, self.acts[i - 1], dya, False)
-                prog.add(ca.dgrad(dya, g_in_p, padded_domain=rf))
-            g_next = net.gbuf(f"g_res{k % 2}", B, h4, w4, c4, 0)
+            (ca, cb), (ra, rb), (sa, sb) = net.c_blk[k], self.raw[i], self.stats[i]
+            g_mid, a_parts = block_conv_bwd(k, "b", cb, rb, sb, ACT_NONE, g_cur, False, chain=use_chain)
+            g_in_p, _ = block_conv_bwd(k, "a", ca, ra, sa, net.block_act, g_mid, rf, parts=a_parts)
+            g_next = net.gbuf(f"g_res{k % 2}", B, ra.H, ra.W, ra.C, 0)
             prog.add(ops.fold_add(g_cur, g_in_p, rf, g_next))
             g_cur = g_next
             if bucket is not None and k == bucket[0]:

@@ -28,7 +28,7 @@ import torch.nn as nn
 from . import autograd as AG
 from ._lib import ACT_NONE, ACT_RELU, ACT_LRELU, ACT_TANH, BF16, F32, HALO_NONE, HALO_REFLECT, HALO_REPLICATE, HALO_ZERO
 from .convplan import ConvLayer
-from .runtime import Program, View, cpad
+from .runtime import IN_WS_CHUNKS, Program, View, cpad
 
 PAD_ZERO, PAD_REFLECT = 0, 1
 _COMPUTE_DTYPE = [F32]
@@ -200,7 +200,7 @@ class _NormPlan:
         self.y_out, self.dx_out, self.stats = f32(shape), f32(shape), f32(B * cpad(C) * 2)
         xv, yv, rv = ctx.view(B, H, W, cpad(C), 0), ctx.view(B, H, W, cpad(C), 0), (ctx.view(B, H, W, cpad(C), 0) if has_res else None)
         gv, dxv = ctx.view(B, H, W, cpad(C), 0), ctx.view(B, H, W, cpad(C), 0)
-        ws = f32(B * 96 * cpad(C) * 2 + B * cpad(C) * 2 + 64)
+        ws = f32(B * IN_WS_CHUNKS * cpad(C) * 2 + B * cpad(C) * 2 + 64)
         self.fwd = Program("instance_norm_fwd")
         self.fwd.add(ops.nchw_to_view(self.x_in, C, xv, HALO_NONE))
         if has_res:
