@@ -686,7 +686,7 @@ int check_lanes(const gan_view* v, const char* what) {
   if (v->C % epc != 0 || cl > NTHR || (cl & (cl - 1)) != 0) return gan_set_error(-1, "%s: C=%d unsupported (C/%d must be a power of two <= 256)", what, v->C, epc);
   return 0;
 }
-// row-chunks per image for the statistics passes: ~2048 16-byte loads per block, at most MAXCH (workspace bound)
+// row-chunks per image for the statistics passes: WORK_PER_BLOCK 16-byte loads per block, at most MAXCH (workspace bound)
 constexpr int WORK_PER_BLOCK = 4096;   // 16-byte loads per block and operand
 // partials per image for the passes whose consumer sums them itself (<= MAXPARTS): as many as keep ~2 blocks per CU busy
 int nparts_for(int B, int HW, int cl) {
@@ -859,7 +859,7 @@ static int in_bwd_impl(const gan_view* x, const float* stats, int act, const gan
   GAN_CHECK(stats && ws, "in_bwd: null pointer");
   GAN_CHECK(act == GAN_ACT_NONE || act == GAN_ACT_RELU || act == GAN_ACT_LRELU, "in_bwd: unsupported activation %d", act);
   GAN_CHECK(x->C <= NTHR * 8 / 4, "in_bwd: C=%d > %d", x->C, NTHR * 8 / 4);
-  // two launches: partial sums (sum g, sum g*xhat) per (image, chunk), then the apply pass, whose blocks add the <= 16 chunks up themselves
+  // two launches: partial sums (sum g', sum g'*x against the RAW x) per (image, chunk), then the apply pass, whose blocks add the <= 16 chunks up themselves
   const int HW = x->H * x->W, nch = nparts_for(x->B, HW, lanes_of(x)), BC = x->B * x->C;
   float* ws2 = ws + (int64_t)x->B * MAXCH * x->C * 2;
   DView vx = to_dview(x), vg = to_dview(gy), v2 = g2 ? to_dview(g2) : null_dview(), vd = to_dview(dx);

@@ -428,6 +428,11 @@ class HipOps:
     def in_stats(self, x: View, eps, stats, ws) -> Op:
         return self._call("gan_in_stats", self._v(x), C.c_float(eps), self._p(stats), self._p(ws), self._s())
 
+    def in_finalize(self, stats, BC, HW, eps) -> Op:
+        """stats: fp32 [BC][2] whole-image (sum, sum of squares), turned into (mean, rstd) in place."""
+        assert stats.dtype == torch.float32 and stats.numel() >= BC * 2
+        return self._call("gan_in_finalize", self._p(stats), BC, HW, C.c_float(eps), self._s())
+
     @staticmethod
     def _hbm(op: Op, x: View, ntensors: int) -> Op:
         """Algorithmic HBM bytes of an HBM-bound launch (every operand tensor read or written once), for bench.py."""

@@ -218,7 +218,29 @@ int gan_bias_grad(const gan_view* g, int N_real, float* grad, int accumulate, fl
 
 /* ---- InstanceNorm2d (+ReLU/LeakyReLU, + residual add, + halo fill): replaces nn.InstanceNorm2d, nn.ReLU,
  *      nn.ReflectionPad2d and the residual add (generator_resnet_attn.py:25,43,56,64,71,111,114-115,126-127,150-151,158;
- *      Basic_GAN/src/models.py:10-18,30-31,38-39,52-53,91-92,99-100).  stats = fp32 [B][C][2] (mean, rstd). */
+ *      Basic_GAN/src/models.py:10-18,30-31,38-39,52-53,91-92,99-100).  stats = fp32 [B][C][2] (mean, rstd).
+ *
+ * Conditioning of the statistics (every producer: gan_in_stats, gan_in_partial + gan_in_stats_from_parts / gan_in_apply_parts, the
+ * convolution epilogue's partials, gan_in_finalize).  The biased variance is evaluated as E[x^2] - mean^2: sum and sum of squares are
+ * accumulated in fp32 per lane and chunk, combined in fp64, var is clamped at 0 and rstd = 1 / sqrt(var + eps).  With
+ *     dS = 4 sqrt(HW) 2^-24 sum|x|,   dQ = 4 sqrt(HW) 2^-24 sum x^2
+ * the results satisfy   |mean - mean_exact| <= dS / HW + 2^-24 |mean|,
+ *                       |var - var_exact|   <= tol_var = dQ / HW + 2 |mean| dS / HW + (dS / HW)^2,
+ *                       rstd in [ (var_exact + tol_var + eps)^-1/2, (max(var_exact - tol_var, 0) + eps)^-1/2 ] widened by 2^-23 relative,
+ * which for tol_var << var + eps is 1/2 rstd^3 tol_var.  The relative error of the variance therefore grows with
+ * kappa = (mean^2 + var) / var: about 1e-5 on centred data, 1e-3 at |mean| / sigma = 100, and no digits are left around
+ * |mean| / sigma = 1000 (has the measured figures).  torch's float32 instance_norm subtracts the mean before squaring
+ * and is better conditioned (1e-7 on all of these); callers whose activations carry a mean far above their spread must centre them first.
+ * With H * W = 1, var is the fp32 rounding error of x^2 (0 where x^2 is exact in fp32), mean is x and y is exactly 0 (+ residual).
+ *
+ * What each entry point writes.  stats: floats [0, B*C*2).  gan_in_stats' ws: floats [0, B*nchunks*C*2), nchunks <= 96.  gan_in_partial:
+ * parts [0, B*gan_in_partial_count(x)*C*2).  gan_in_apply / gan_in_apply_parts: the interior of y, and with GAN_HALO_REFLECT also the
+ * y0 / x0 halo pixels around it (each a bit copy of the value at its reflect pre-image); every other halo_mode (NONE, ZERO, REPLICATE)
+ * leaves the halo as it is -- a zero halo is the caller's, zeroed once at allocation.  gan_in_bwd*, gan_fold_add, gan_pad_fold,
+ * gan_act_bwd: the interior of dx / out only.  Bias: bias_grad[0, bias_n), bias_part [0, gan_in_bwd_bias_parts(x)*C) (row 0 of each image
+ * holds the closed-form value, the other rows 0), gan_bias_finalize_batch: grad[0, N_real) of each descriptor.
+ * Widths: C a multiple of 8 (both dtypes) with C/8 (bf16) or C/4 (fp32) a power of two <= 256; gan_in_apply_parts C <= 1024; the
+ * backward entry points C <= 512.  Every entry point is deterministic: a repeated call gives the same bits. */
 int gan_in_stats(const gan_view* x, float eps, float* stats, float* ws, void* stream);
 /* (mean, rstd) from the per-tile partials a convolution epilogue wrote to gan_conv_desc.stats (parts = [B][nparts][C][2]) */
 int gan_in_stats_from_parts(const float* parts, int nparts, int B, int C, int HW, float eps, float* stats, void* stream);

@@ -181,6 +181,15 @@ class EmuOps:
             stats[:B * Cc * 2].view(B, Cc, 2).copy_(torch.stack([mean, 1.0 / torch.sqrt(var + eps)], -1).float())
         return op
 
+    def in_finalize(self, stats, BC, HW, eps):
+        """Statement of gan_in_finalize: whole-image (sum, sum of squares) -> (mean, rstd) in place."""
+        def op():
+            p = stats[:BC * 2].view(BC, 2).double()
+            mean = p[:, 0] / HW
+            var = (p[:, 1] / HW - mean * mean).clamp_min(0)
+            stats[:BC * 2].view(BC, 2).copy_(torch.stack([mean, 1.0 / torch.sqrt(var + eps)], -1).float())
+        return op
+
     @staticmethod
     def _unfrag(wf, Nw, K, sub=1):
         """fragment-major [Nw/16][K/32][fg 4][fr 16][8] (x `sub` values per slot: 2 for fp8) -> row-major [Nw][K * sub]"""
@@ -403,7 +412,7 @@ class EmuOps:
 
         def op():
             inner()
-            s = dx.nhwc().float().sum((0, 1, 2))[:bias_n]
+            s = dx.nhwc().float().sum((1, 2)).sum(0)[:bias_n]       # the per-image rows of in_bwd_bias_deferred, then their sum
             bias_grad.copy_(bias_grad + s if accumulate else s)
         return op
 

@@ -18,6 +18,7 @@ import torch
 from gan_variant_research_amd import BF16, F32, FP8
 from tests import e4m3_ref as R
 from tests.emulator import EmuOps, _reflect
+from tests.norm_ref64 import bwd_ref64, fold64, norm_ref64      # noqa: F401  (the float64 statements live in tests/norm_ref64.py)
 
 REL = 2.0 ** -22
 CAP = 1e-3
@@ -275,20 +276,6 @@ def _fill_view(v, gen, scale=1.0, shift=0.0, off_ties=False):
     v.t.copy_(t.to(v.t.device))
 
 
-def norm_ref64(x, act, residual):
-    """float64 InstanceNorm of the interior: mean and variance from float64 sums of x, activation, residual"""
-    v = x.nhwc().double()
-    HW = x.H * x.W
-    mean = v.sum((1, 2), keepdim=True) / HW
-    var = ((v * v).sum((1, 2), keepdim=True) / HW - mean * mean).clamp_min(0)
-    out = (v - mean) / torch.sqrt(var + EPS64)
-    if act == 1:
-        out = torch.relu(out)
-    if residual is not None:
-        out = out + residual.nhwc().double()
-    return out, mean, 1.0 / torch.sqrt(var + EPS64)
-
-
 def apply_case(ctx, dtype, shape, act, res, mode, nan_at=None):
     B, H, W, C, halo = shape
     gen = torch.Generator().manual_seed(17 + 2 * act + res)
@@ -371,29 +358,6 @@ def check_apply(res, ref, what, delta=None):
 DX_FILL = 1e6
 BWD_COMBOS = [(act, bias) for act in (1, 0) for bias in (True, False)]
 BWD_TOL = {F32: 1e-4, BF16: 1e-1}        # 5 x test_instance_norm_twins' (rtol = atol) for dx
-
-
-def fold64(g, fold):
-    full = g.padded().double()
-    p, H, W = g.halo, g.H, g.W
-    if not fold:
-        return full[:, p:p + H, p:p + W].clone()
-    ys, xs = _reflect(torch.arange(-p, H + p), H).to(full.device), _reflect(torch.arange(-p, W + p), W).to(full.device)
-    tmp = torch.zeros(g.B, H, g.Wp, g.C, dtype=torch.float64, device=full.device)
-    tmp.index_add_(1, ys, full)
-    out = torch.zeros(g.B, H, W, g.C, dtype=torch.float64, device=full.device)
-    out.index_add_(2, xs, tmp)
-    return out
-
-
-def bwd_ref64(x, act, gy, fold):
-    _, mean, rstd = norm_ref64(x, 0, None)
-    xh = (x.nhwc().double() - mean) * rstd
-    g = fold64(gy, fold)
-    if act == 1:
-        g = g * (xh > 0)
-    m1, m2 = g.mean((1, 2), keepdim=True), (g * xh).mean((1, 2), keepdim=True)
-    return rstd * (g - m1 - xh * m2)
 
 
 def bwd_case(ctx, dtype, shape, act, bias):
