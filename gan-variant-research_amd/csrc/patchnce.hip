@@ -10,7 +10,11 @@
 // permuted identically on both sides so every lane reads 16 contiguous bytes); shapes the MFMA tiling does not cover
 // (C not a multiple of 64, P not a multiple of 16) take the scalar-FMA kernels below.
 //
-// Workspace (floats): Sn[B][P][C] | Tn[B][P][C] | tnorm[B][P] | lse[B][P] | rowloss[B][P] | flag[B] | dX[B][P][C]
+// The workspace layout (Sn | Tn | tnorm | lse | rowloss | flag | dX) is stated in include/mi355x_gan.h beside the entry points.
+//
+// Non-finite data: an Inf or NaN in a sampled row makes logits NaN (Inf / Inf in the normalisation); nce_clamp passes a NaN on, so
+// the row losses it touches, the image's mean and hence its flag see it.  A flag-0 image adds nothing to the loss, its rows of dX are
+// written as zeros and the scatter leaves its part of gtgt alone (never 0 * x: Sn and Tn of such an image hold NaN themselves).
 #include <stdlib.h>
 #include "common.h"
 
@@ -29,13 +33,13 @@ __host__ __device__ inline NceWs carve(float* ws, int B, int P, int C) {
 
 // one wave per (b, patch): gather the C-vector, L2-normalise (x / max(|x|, eps))
 template <typename T>
-__global__ __launch_bounds__(256) void nce_gather_kernel(DView src, DView tgt, int has_src, const int32_t* __restrict__ ids, int P, int C,
+__global__ __launch_bounds__(256) void nce_gather_kernel(DView src, DView tgt, const int32_t* __restrict__ ids, int P, int C,
                                                         NceWs w) {
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
   if (row >= tgt.B * P) return;
   const int b = row / P, i = row - b * P;
   const int id = ids[i], y = id / tgt.W, x = id - y * tgt.W;
-  for (int which = has_src ? 0 : 1; which < 2; ++which) {
+  for (int which = 0; which < 2; ++which) {
     const DView& v = which ? tgt : src;
     const T* p = reinterpret_cast<const T*>(v.ptr) + v.pix(b, y, x);
     float vals[8];  // C <= 512
@@ -52,6 +56,15 @@ __global__ __launch_bounds__(256) void nce_gather_kernel(DView src, DView tgt, i
 }
 
 constexpr int TI = 16;  // target rows per block
+
+// clamp(x, -50, 50) as torch.clamp states it: a NaN stays a NaN (fminf / fmaxf alone return the other operand, i.e. -50)
+__device__ __forceinline__ float nce_clamp(float x) { return x != x ? x : fminf(fmaxf(x, -50.f), 50.f); }
+
+// the rows i0 .. i0+15 of dX of an image whose loss was not finite: exactly zero
+__device__ __forceinline__ void nce_zero_rows(float* __restrict__ dX_b, int i0, int P, int C) {
+  const int n = min(TI, P - i0) * C;
+  for (int k = threadIdx.x; k < n; k += 256) dX_b[(int64_t)i0 * C + k] = 0.f;
+}
 
 // computes, for rows i0..i0+15 of image b, the clamped logits against every source patch j (thread j).
 // lg[r] = logit(i0+r, j), raw[r] = the unclamped value.  S is streamed through LDS in 32-channel slabs.
@@ -83,7 +96,7 @@ __device__ __forceinline__ void nce_logits(const float* __restrict__ Sn_b, const
 #pragma unroll
   for (int r = 0; r < TI; ++r) {
     raw[r] = acc[r] * inv_t;
-    lg[r] = fminf(fmaxf(raw[r], -50.f), 50.f);
+    lg[r] = nce_clamp(raw[r]);
   }
 }
 
@@ -142,7 +155,9 @@ __global__ __launch_bounds__(256) void nce_finalize_kernel(int B, int P, float w
   }
   if (threadIdx.x == 0) {
     tot /= (float)B;
-    if (!isfinite(tot)) tot = 0.f;  // :106-108
+    // :106-108.  Every term added above is finite and at most 100 + log 256, so short of fp32 overflow of their sum (B > 1e36) this
+    // branch cannot be taken; it is kept as the statement of the reference's last check.
+    if (!isfinite(tot)) tot = 0.f;
     *loss += weight * tot;
   }
 }
@@ -156,6 +171,7 @@ __global__ __launch_bounds__(256) void nce_bwd_kernel(int B, int P, int C, float
   __shared__ float red[16];
   const int b = blockIdx.y, i0 = blockIdx.x * TI, j = threadIdx.x;
   const float* Sn_b = w.Sn + (int64_t)b * P * C;
+  if (w.flag[b] == 0.f) { nce_zero_rows(w.dX + (int64_t)b * P * C, i0, P, C); return; }   // block-uniform
   float lg[TI], raw[TI];
   nce_logits(Sn_b, w.Tn + (int64_t)b * P * C, i0, P, C, inv_t, tsh, ssh, lg, raw);
   const float scale = weight * w.flag[b] * inv_t / ((float)P * (float)B);
@@ -267,7 +283,7 @@ __global__ __launch_bounds__(256) void nce_fwd_mfma_kernel(int P, int C, float i
     const bool ok = 64 * wave + 16 * t + fr < P;
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-      lg[t][r] = ok ? fminf(fmaxf(acc[t][r] * inv_t, -50.f), 50.f) : -1e30f;
+      lg[t][r] = ok ? nce_clamp(acc[t][r] * inv_t) : -1e30f;
       mx[r] = fmaxf(mx[r], lg[t][r]);
     }
   }
@@ -303,6 +319,7 @@ __global__ __launch_bounds__(256) void nce_bwd_mfma_kernel(int B, int P, int C, 
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, fr = lane & 15, fg = lane >> 4;
   const float* Sn_b = w.Sn + (int64_t)b * P * C;
   const float* Tn_b = w.Tn + (int64_t)b * P * C;
+  if (w.flag[b] == 0.f) { nce_zero_rows(w.dX + (int64_t)b * P * C, i0, P, C); return; }   // block-uniform
   for (int k = threadIdx.x; k < TI * C; k += 256) {
     const int r = k / C, c = k - r * C;
     tsh[k] = (i0 + r < P) ? Tn_b[(int64_t)(i0 + r) * C + c] : 0.f;
@@ -319,7 +336,7 @@ __global__ __launch_bounds__(256) void nce_bwd_mfma_kernel(int B, int P, int C, 
       const float raw = acc[t][r] * inv_t;
       float d = 0.f;
       if (i < P && j < P) {
-        d = expf(fminf(fmaxf(raw, -50.f), 50.f) - w.lse[(int64_t)b * P + i]) - (j == i ? 1.f : 0.f);
+        d = expf(nce_clamp(raw) - w.lse[(int64_t)b * P + i]) - (j == i ? 1.f : 0.f);
         if (raw < -50.f || raw > 50.f) d = 0.f;   // clamp passes no gradient outside [-50, 50]
         d *= scale;
       }
@@ -393,6 +410,7 @@ __global__ __launch_bounds__(256) void nce_scatter_kernel(DView gt, const int32_
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
   if (row >= gt.B * P) return;
   const int b = row / P, i = row - b * P;
+  if (w.flag[b] == 0.f) return;   // wave-uniform: a non-finite image passes no gradient, its part of gt keeps its bits
   const int id = ids[i];
   // positions holding the same id, found 64 at a time (P <= 256): the first one is the leader and adds all of them, in
   // ascending order of position
@@ -445,7 +463,7 @@ extern "C" int gan_patchnce_fwd(const gan_view* src, const gan_view* tgt, const 
   NceWs w = carve(ws, B, P, C);
   hipStream_t s = (hipStream_t)stream;
   DView vs = to_dview(src), vt = to_dview(tgt);
-  GAN_DISPATCH_DTYPE(tgt->dtype, hipLaunchKernelGGL((nce_gather_kernel<T>), dim3((B * P + 3) / 4), dim3(256), 0, s, vs, vt, 1, ids, P, C, w);)
+  GAN_DISPATCH_DTYPE(tgt->dtype, hipLaunchKernelGGL((nce_gather_kernel<T>), dim3((B * P + 3) / 4), dim3(256), 0, s, vs, vt, ids, P, C, w);)
   const size_t shm = (size_t)(TI * C + 256 * 33) * sizeof(float);
   if (nce_mfma_ok(P, C)) hipLaunchKernelGGL(nce_fwd_mfma_kernel, dim3((P + TI - 1) / TI, B), dim3(256), 0, s, P, C, 1.f / temperature, w);
   else hipLaunchKernelGGL(nce_fwd_kernel, dim3((P + TI - 1) / TI, B), dim3(256), shm, s, P, C, 1.f / temperature, w);

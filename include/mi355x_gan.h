@@ -394,8 +394,23 @@ int gan_r1_reduce(const gan_view* g, int C, float scale, float* loss, const gan_
 
 /* ---- PatchNCE (GAN_Variant1/losses/patchnce_cut.py:42-110) for one feature layer.
  *      ids: device int32 [P] positions in [0,H*W).  ws: fp32 workspace >= gan_patchnce_ws_floats(B,P,C).
- *      fwd: *loss += weight * mean_b CE (non-finite per-image losses count as 0).  bwd: grad rows of tgt
- *      (scaled by weight) are ADDED into `gtgt` (duplicates in ids accumulate). */
+ *      fwd: *loss += weight * mean_b CE.  bwd: grad rows of tgt (scaled by weight) are ADDED into `gtgt`
+ *      (duplicates in ids accumulate); channels >= C and halos of `gtgt` are never written.
+ *      Non-finite data: an image whose mean CE is not finite (an Inf or NaN in one of its sampled rows; the
+ *      clamp to +-50 passes a NaN on, as torch.clamp does) counts as the constant 0: it adds nothing to the
+ *      loss, its flag is 0, its rows of dX are exactly 0 and its part of `gtgt` keeps its bits.  The other
+ *      images are unaffected; values outside the sampled rows are never read.
+ *      Range: the row norm sqrt(sum_c x^2) is evaluated in fp32, so sampled rows must have ||x|| < 1.8e19
+ *      (sum x^2 below FLT_MAX; beyond it the norm is Inf and the row normalises to zeros).  Rows below
+ *      about 1e-19, whose squares underflow, fall to the eps branch x / 1e-6 like every row of norm
+ *      <= 1e-6, in agreement with the reference.
+ *      Workspace layout (floats, in this order; tests read it):
+ *        Sn[B][P][C] | Tn[B][P][C]   normalised source / target rows, x / max(||x||, 1e-6)
+ *        tnorm[B][P]                 max(||target row||, 1e-6)
+ *        lse[B][P] | rowloss[B][P]   log-sum-exp of the clamped logits of row i; lse - logit(i, i)
+ *        flag[(B+3)/4*4]             1 where the image's mean CE is finite, else 0 (entries >= B unused)
+ *        dX[B][P][C]                 gradient rows before the scatter (written by bwd)
+ *      followed by 64 unused floats: gan_patchnce_ws_floats = 3 B P C + 3 B P + (B+3)/4*4 + 64. */
 int64_t gan_patchnce_ws_floats(int B, int P, int C);
 int gan_patchnce_fwd(const gan_view* src, const gan_view* tgt, const int32_t* ids, int P, int C, float temperature,
                      float weight, float* loss, float* ws, void* stream);

@@ -713,15 +713,16 @@ class EmuOps:
             B_, P_ = logits.shape[:2]
             per = torch.nn.functional.cross_entropy(logits.reshape(B_ * P_, P_), torch.arange(P_).repeat(B_), reduction="none").reshape(B_, P_).mean(1)
             dlog = (torch.softmax(logits, dim=2) - torch.eye(P_).unsqueeze(0)) / (B_ * P_)
-            dlog = dlog * ((raw > -50) & (raw < 50)) * torch.isfinite(per).view(B_, 1, 1)
+            dlog = dlog * ((raw > -50) & (raw < 50))
+            ok = torch.isfinite(per)        # an image whose loss is not finite passes no gradient: its part of gtgt keeps its bits (never 0 * NaN)
             dtn = torch.bmm(dlog, sn) / temperature
             g = weight * (dtn - tn * (dtn * tn).sum(2, keepdim=True)) / nt
             g = torch.where(t.norm(dim=2, keepdim=True) > 1e-6, g, weight * dtn / 1e-6)
             buf = gtgt.nhwc()
-            acc = buf.float()
+            acc = buf.float().clone()       # (.float() of an fp32 buffer is the buffer itself)
             for i in range(ids.numel()):
                 acc[:, ys[i], xs[i], :Cc] += g[:, i]
-            buf.copy_(acc.to(buf.dtype))
+            buf[ok] = acc.to(buf.dtype)[ok]
         return op
 
     # ------------------------------------------------------------------ optimiser
