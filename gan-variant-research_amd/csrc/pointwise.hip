@@ -145,8 +145,9 @@ __global__ __launch_bounds__(1024) void patch_loss_kernel(DView x, int mode, flo
     const int w = i % x.W, h = (i / x.W) % x.H, b = i / (x.W * x.H);
     const float v = ld1<T>(xp + x.pix(b, h, w));
     float f, d;
-    if (mode == 0) { f = fmaxf(1.f - v, 0.f); d = v < 1.f ? -1.f : 0.f; }
-    else if (mode == 1) { f = fmaxf(1.f + v, 0.f); d = v > -1.f ? 1.f : 0.f; }
+    // relu that passes a NaN on, as torch.relu does (fmaxf returns its non-NaN operand: a NaN logit would add 0 to the hinge loss)
+    if (mode == 0) { const float h = 1.f - v; f = h > 0.f || h != h ? h : 0.f; d = v < 1.f ? -1.f : 0.f; }
+    else if (mode == 1) { const float h = 1.f + v; f = h > 0.f || h != h ? h : 0.f; d = v > -1.f ? 1.f : 0.f; }
     else if (mode == 2) { f = -v; d = -1.f; }
     else if (mode == 3) { f = (v - target) * (v - target); d = 2.f * (v - target); }
     else { f = fmaxf(v, 0.f) - v * target + log1pf(expf(-fabsf(v))); d = 1.f / (1.f + expf(-v)) - target; }

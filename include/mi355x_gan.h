@@ -308,10 +308,14 @@ int gan_act_bwd(const gan_view* y, int act, const gan_view* g, int fold, const g
 int gan_nchw_to_view(const float* src, int C, const gan_view* dst, int halo_mode, void* stream);
 int gan_view_to_nchw(const gan_view* src, int C, float* dst, void* stream);
 int gan_view_copy(const gan_view* src, const gan_view* dst, int halo_mode, void* stream);   /* interior copy + halo fill */
+/* The three are exact: every value is rounded once to the destination type (a NaN stays a NaN in exactly the copies that read it).
+ * gan_nchw_to_view writes 0 to channels C .. dst->C of every pixel it writes; GAN_HALO_NONE writes the interior only, GAN_HALO_REFLECT
+ * (both calls; needs y0 < H and x0 < W) and GAN_HALO_REPLICATE (gan_nchw_to_view) the padded extent of y0 / x0 pixels as well. */
 
 /* ---- AvgPool2d(kernel 3, stride 2, padding 1, count_include_pad=False): the downsampling between the scales of
  *      MultiscaleDiscriminator (GAN_Variant1/models/discriminator_patchgan.py:100, 110-112; get_intermediate_features :125-127).
- *      y is ((H-1)/2+1) x ((W-1)/2+1); only interiors are written (zero halos stay zero).  bwd: gx (+)= pool^T gy. */
+ *      y is ((H-1)/2+1) x ((W-1)/2+1); only interiors are written (zero halos stay zero).  bwd: gx (+)= pool^T gy.
+ *      A NaN reaches exactly the outputs whose window reads it; the halo of x is never read. */
 int gan_avgpool_fwd(const gan_view* x, const gan_view* y, void* stream);
 int gan_avgpool_bwd(const gan_view* gy, const gan_view* gx, int accumulate, void* stream);
 
@@ -352,7 +356,16 @@ int gan_spectral_norm_batch_bwd(const gan_sn_desc* descs, int n, int total_block
 
 /* ---- DiffAugment (GAN_Variant1/training/diffaugment.py:6-60,94-106), per-sample parameters injected.
  *      prm = device fp32 [B][12]: brightness add, saturation factor, contrast factor, tx, ty,
- *      cut_lo_h, cut_hi_h, cut_lo_w, cut_hi_w (inclusive; lo>hi = no cutout), 3 spare.  C = real channels (3). */
+ *      cut_lo_h, cut_hi_h, cut_lo_w, cut_hi_w (inclusive; lo>hi = no cutout), 3 spare.  C = real channels (1..4; the views have C = 8).
+ *      y[b][h][w] = 0 where (h, w) is cut or (h + tx, w + ty) lies outside the image, else the value of x[b][h + tx][w + ty] after
+ *      brightness, saturation about the pixel's channel mean and contrast about the image's mean over (c, h, w); channels C..7 of
+ *      every interior pixel of the output are written as 0, halos are not written.  ws: fp32, [0 .. B) is written (fwd: the images'
+ *      sums over the real channels; bwd: the sums of gy over the pixels that took a value), nothing past it.
+ *      Accuracy: the contrast line (s - mu) * con + mu carries the fp32 image mean: its error is about 4 sqrt(C H W) 2^-24 |mean|
+ *      whatever the spread of the image, so relative to the spread it grows with |mean| / spread.
+ *      Non-finite data: a NaN in a real channel of a pixel reaches, through the image mean, every output pixel of that image that
+ *      takes a value (bwd: a NaN in a gy pixel that took a value reaches all of gx of that image); pixels that take no value stay
+ *      exactly 0, other images are unaffected, and pad channels, halos and (bwd) cut or shifted-out pixels of gy are never read. */
 int gan_diffaug_fwd(const gan_view* x, int C, const float* prm, const gan_view* y, float* ws, void* stream);
 int gan_diffaug_bwd(const gan_view* gy, int C, const float* prm, const gan_view* gx, float* ws, void* stream);
 
@@ -385,7 +398,16 @@ int gan_input_pipeline(const gan_input_job* jobs_dev, const gan_input_job* jobs_
 /* ---- losses.  Every loss writes its value to *loss (device fp32, overwritten) and the gradient wrt its input.
  *      hinge: adv_hinge.py:6-62 (mode 0: mean relu(1-x), 1: mean relu(1+x), 2: -mean x), scaled by `scale`;
  *      lsgan/bce: Basic_GAN/src/losses.py:5-22 (mode 3: mse vs target, 4: bce-with-logits vs target in {0,1});
- *      l1: identity_l1.py:18-20 and Basic_GAN/src/losses.py:24-30 (target given as NCHW fp32). */
+ *      l1: identity_l1.py:18-20 and Basic_GAN/src/losses.py:24-30 (target given as NCHW fp32).
+ *      gan_patch_loss reads channel 0 of the logits: *loss = scale * mean f, grad = scale / n * f' in channel 0 and 0 in channels 1..7
+ *      (grad->C must be 8); the hinge derivative at the kink (x == 1 for mode 0, x == -1 for mode 1) is 0, as relu' is in torch.
+ *      gan_l1_loss: sign(0) = 0.  The gradient views' halos are never written; channels C..7 of their interior pixels are written as 0.
+ *      ws of gan_l1_loss and gan_r1_reduce: fp32, [0 .. 512) is written, nothing past it.  Repeated calls repeat their bits.
+ *      Non-finite data: one NaN in an element that is read (channel 0 of a logit; a real channel of x, target_nchw or g) makes *loss
+ *      NaN in every mode of gan_patch_loss, in gan_l1_loss and in gan_r1_reduce; one +-Inf makes it what the formula gives in IEEE
+ *      arithmetic -- not finite, except for a hinge on its flat side (relu(1 - Inf) = 0).  Pad channels and halos are never read: a NaN
+ *      or Inf there changes nothing.  The gradient of a NaN or Inf element itself (0 or NaN) is unspecified; the gradients of
+ *      the other elements are unaffected. */
 int gan_patch_loss(const gan_view* logits, int mode, float target, float scale, float* loss, const gan_view* grad, void* stream);
 int gan_l1_loss(const gan_view* x, int C, const float* target_nchw, float scale, const float* dev_grad_scale, float* loss,
                 const gan_view* grad, float* ws, void* stream);   /* grad additionally * (*dev_grad_scale) if non-NULL */

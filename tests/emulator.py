@@ -605,7 +605,7 @@ class EmuOps:
             col = (s - mu) * con + mu
             bb = torch.arange(B).view(B, 1, 1).expand(B, H, W)
             out = torch.zeros(B, H, W, y.C)
-            out[..., :Cr] = col[bb, sh, sw] * valid.unsqueeze(-1)
+            out[..., :Cr] = torch.where(valid.unsqueeze(-1), col[bb, sh, sw], torch.zeros(()))      # a pixel that takes no value is 0, not 0 * NaN
             _store(y, out)
         return op
 
@@ -613,7 +613,7 @@ class EmuOps:
         def op():
             B, H, W = gx.B, gx.H, gx.W
             p, sh, sw, valid = self._aug_masks(prm, B, H, W)
-            g = gy.nhwc().float()[..., :Cr] * valid.unsqueeze(-1)
+            g = torch.where(valid.unsqueeze(-1), gy.nhwc().float()[..., :Cr], torch.zeros(()))      # a gradient that is not read is 0, not 0 * NaN
             gsum = g.sum((1, 2, 3), keepdim=True)
             # scatter back to source coordinates (a pure shift: each source pixel is read at most once)
             gs = torch.zeros(B, H, W, Cr)
