@@ -14,6 +14,7 @@ LIB_PATH = os.path.join(HERE, "libmi355x_gan.so")
 F32, BF16, FP8 = 0, 1, 2     # FP8: OCP e4m3 operand copies of the bottleneck convolutions (BASELINE.json configs[4])
 ACT_NONE, ACT_RELU, ACT_LRELU, ACT_TANH = 0, 1, 2, 3
 HALO_NONE, HALO_ZERO, HALO_REFLECT, HALO_REPLICATE = 0, 1, 2, 3
+RESIZE_BILINEAR, RESIZE_BICUBIC = 2, 3      # Pillow's filter ids (Image.BILINEAR, Image.BICUBIC)
 
 vp, i32, i64, f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_float
 
@@ -107,6 +108,7 @@ PROTOTYPES = {
     "gan_nchw_to_view": (C.c_int, [vp, C.c_int, PV, C.c_int, vp]),
     "gan_view_to_nchw": (C.c_int, [PV, C.c_int, vp, vp]),
     "gan_view_copy": (C.c_int, [PV, PV, C.c_int, vp]),
+    "gan_view_to_u8_hwc": (C.c_int, [PV, C.c_int, vp, vp]),
     "gan_avgpool_fwd": (C.c_int, [PV, PV, vp]),
     "gan_in_bwd_bias_parts": (C.c_int, [PV]),
     "gan_in_bwd_bias_deferred": (C.c_int, [PV, vp, C.c_int, PV, C.c_int, PV, PV, vp, vp, vp]),
@@ -115,6 +117,9 @@ PROTOTYPES = {
     "gan_resize_ksize": (C.c_int, [C.c_int, C.c_int]),
     "gan_resize_coeffs": (C.c_int, [C.c_int, C.c_int, vp, vp, C.c_int]),
     "gan_input_pipeline": (C.c_int, [vp, vp, C.c_int, vp, C.c_int, vp, C.c_int, vp, vp, vp, vp]),
+    "gan_resize_ksize_filter": (C.c_int, [C.c_int, C.c_int, C.c_int]),
+    "gan_resize_coeffs_filter": (C.c_int, [C.c_int, C.c_int, C.c_int, vp, vp, C.c_int]),
+    "gan_input_pipeline_filter": (C.c_int, [vp, vp, C.c_int, vp, C.c_int, C.c_int, vp, C.c_int, vp, vp, vp, vp]),
     "gan_spectral_norm_ws_floats": (C.c_int64, [C.c_int, C.c_int]),
     "gan_spectral_norm_fwd": (C.c_int, [vp, C.c_int, C.c_int, vp, vp, C.c_int, C.c_float, vp, vp, vp, vp]),
     "gan_spectral_norm_bwd": (C.c_int, [vp, vp, vp, vp, vp, C.c_int, C.c_int, vp, vp, vp]),

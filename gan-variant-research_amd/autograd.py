@@ -114,7 +114,8 @@ class _Bridge:
             if s.reclaim():
                 s.busy = True
                 return s
-        s = make()
+        with torch.inference_mode(False), torch.no_grad():      # a slot outlives its first caller: planned under inference_mode its
+            s = make()                                          # buffers would refuse the next caller's copy_ outside it
         s.busy = True
         slots.append(s)
         self._repack = None            # planning a new pass may have allocated operand copies: rebuild the repack program
@@ -165,19 +166,23 @@ class _GenBridge(_Bridge):
         s.xin = torch.zeros(B, net.in_c, H, W, dtype=torch.float32, device=self.device)
         s.fwd = s.gp.fwd_program(s.xin)
         s.out = None
+        s.n_pass = len(s.fwd)             # the launches of the pass itself; what follows converts the image for the caller
         if s.gp.full:
             s.out = torch.zeros(B, net.out_c, H, W, dtype=torch.float32, device=self.device)
             s.fwd.add(ops.view_to_nchw(s.gp.img, net.out_c, s.out))
             s.g_out = torch.zeros_like(s.out)
             s.g_img = ctx.view(B, H, W, s.gp.img.C, 0)
         s.feat_out, s.feat_gin, s.feat_gview = {}, {}, {}
+        s.u8_out = None                   # forward_u8: (uint8 (B, H, W, out_c) tensor, prebuilt epilogue), once per slot
         s.last = last
         s.gx = torch.zeros_like(s.xin)
         return s
 
-    def forward(self, x: torch.Tensor, feat_ids: Optional[Tuple[int, ...]], keep: bool):
+    def forward(self, x: torch.Tensor, feat_ids: Optional[Tuple[int, ...]], keep: bool, u8: bool = False):
+        """u8 (full forward-only passes): the image leaves as packed (B, H, W, out_c) uint8 through the fused epilogue
+        (ops.view_to_u8_hwc) instead of as a clone of the fp32 NCHW tensor."""
         B, C, H, W = x.shape
-        assert C == self.net.in_c
+        assert C == self.net.in_c and not (u8 and (keep or feat_ids is not None))
         last = None if feat_ids is None else max(feat_ids)
         # Forward-only calls of a module with `use_graph = True` replay the pass as ONE hipGraph launch: at small batch the ~110
         # launches of a generator pass cost more host time than GPU time.  Ops bake the stream that is current when they are built,
@@ -204,9 +209,20 @@ class _GenBridge(_Bridge):
                     with torch.cuda.graph(s.graph, stream=s.gstream):
                         s.fwd.run()
                 s.graph.replay()
+            elif u8:
+                for op in s.fwd.ops[:s.n_pass]:      # the fp32 NCHW conversion is not needed (a captured graph keeps it: one graph per slot)
+                    op()
             else:
                 s.fwd.run()
-            if feat_ids is None:
+            if u8:
+                if s.u8_out is None:             # built here, not in the slot: the epilogue runs eagerly on the caller's stream after a replay
+                    with torch.inference_mode(False):      # the slot outlives an inference_mode caller: keep its tensor an ordinary one
+                        t = torch.zeros(B, H, W, self.net.out_c, dtype=torch.uint8, device=self.device)
+                    s.u8_out = (t, self.ctx.ops.view_to_u8_hwc(s.gp.img, self.net.out_c, t))
+                t, op = s.u8_out
+                op()
+                outs = (t.clone(),)
+            elif feat_ids is None:
                 outs = (s.out.clone(),)
             else:
                 outs = []
@@ -490,6 +506,14 @@ def generator_forward(module, x: torch.Tensor, style: str, feat_ids: Optional[Se
     keep = torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in b.plist))
     outs = _GenFn.apply(b, ids, keep, x.float().contiguous(), *b.plist)
     return outs[0] if ids is None else list(outs)
+
+
+def generator_forward_u8(module, x: torch.Tensor, style: str) -> torch.Tensor:
+    """Forward-only G(x) whose image leaves as packed (B, H, W, out_c) uint8 (inference.to_uint8 of G(x), HWC); no autograd node."""
+    b = _bridge_of(module, lambda dev, dt: _GenBridge(module, dev, dt, style))
+    with torch.no_grad():
+        _, outs = b.forward(x.detach().float().contiguous(), None, False, u8=True)
+    return outs[0]
 
 
 def discriminator_forward(module, x: torch.Tensor, style: str, prefix, ndf: int, n_layers: int):

@@ -9,6 +9,8 @@
 // Pillow 12.2 operation by operation (oracle/input_ref.py is the numpy restatement, pinned against Pillow itself), so floating-point
 // contraction is off for this file and every rounding is the one the C code performs.
 // All kernels are HBM-/latency-bound byte work: one pixel per lane, one image per blockIdx.y.
+// The same file holds the other end of inference: view_to_u8_hwc_kernel turns the generator's last activation into the packed uint8
+// HWC image PIL encodes (four pixels per lane), held to torch's float32 operation order for the same reason.
 #include "common.h"
 #include <cmath>
 
@@ -163,9 +165,66 @@ __global__ __launch_bounds__(256) void input_finish_kernel(const gan_input_job* 
 #pragma unroll
   for (int k = 0; k < 3; ++k) o[(int64_t)k * S * S] = __fdiv_rn(__fsub_rn(__fdiv_rn((float)c[k], 255.f), 0.5f), 0.5f);
 }
+
+// ---- output epilogue: view interior -> packed [B][H][W][C] uint8, the reference's _to_uint8 (generate_folder.py:183-185) fused with the
+// NCHW -> HWC turn PIL needs.  Each lane takes a run of four pixels of one row: four 16-byte loads issued back to back (a whole bf16
+// pixel of 8 channels, or the first four fp32 channels; C <= 4, so nothing past them is needed), then PACKED (C == 3, W % 4 == 0, dst
+// four-byte aligned: every run starts on a dword) twelve bytes as three dword stores, otherwise byte stores with a row tail.
+__device__ __forceinline__ uint32_t unit_to_u8(float v) {
+  if (!(v >= -1.f)) v = -1.f;            // clamp(-1, 1); a NaN takes this branch and becomes byte 0
+  if (v > 1.f) v = 1.f;
+  return (uint32_t)rintf(__fmul_rn(__fadd_rn(__fmul_rn(v, 0.5f), 0.5f), 255.f));      // rintf: half to even, as torch.round
+}
+
+template <typename T, bool PACKED>
+__global__ __launch_bounds__(256) void view_to_u8_hwc_kernel(DView src, int C, uint8_t* __restrict__ dst) {
+  const int gw = (src.W + 3) >> 2;
+  const int64_t total = (int64_t)src.B * src.H * gw;
+  const T* sp = reinterpret_cast<const T*>(src.ptr);
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+    const int g = (int)(i % gw);
+    const int64_t r = i / gw;
+    const int y = (int)(r % src.H), b = (int)(r / src.H);
+    const int x = 4 * g;
+    const int n = PACKED ? 4 : min(4, src.W - x);
+    const T* p = sp + src.pix(b, y, x);
+    Raw<T> raw[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) raw[k] = ldraw<T>(p + (int64_t)(k < n ? k : 0) * src.C);     // a tail lane re-reads its first pixel: no load past the row
+    uint32_t q[4][4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      float v[Chunk<T>::N];
+      cvtraw<T>(raw[k], v);
+#pragma unroll
+      for (int c = 0; c < 4; ++c) q[k][c] = unit_to_u8(v[c]);
+    }
+    uint8_t* o = dst + (((int64_t)b * src.H + y) * src.W + x) * C;
+    if (PACKED) {
+      uint32_t* o4 = reinterpret_cast<uint32_t*>(o);
+      o4[0] = q[0][0] | (q[0][1] << 8) | (q[0][2] << 16) | (q[1][0] << 24);
+      o4[1] = q[1][1] | (q[1][2] << 8) | (q[2][0] << 16) | (q[2][1] << 24);
+      o4[2] = q[2][2] | (q[3][0] << 8) | (q[3][1] << 16) | (q[3][2] << 24);
+    } else {
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+#pragma unroll
+        for (int c = 0; c < 4; ++c)
+          if (k < n && c < C) o[k * C + c] = (uint8_t)q[k][c];
+      }
+    }
+  }
+}
 }  // namespace
 
-// ---- host: Pillow's bicubic taps (Resample.c precompute_coeffs + normalize_coeffs_8bpc), double arithmetic, no GPU involved
+// ---- host: Pillow's taps (Resample.c precompute_coeffs + normalize_coeffs_8bpc), double arithmetic, no GPU involved.  The filter ids
+// are Pillow's (Image.BILINEAR = 2, Image.BICUBIC = 3); each filter is its Resample.c function and support.
+static double bilinear_filter(double x) {
+  if (x < 0.0) x = -x;
+  if (x < 1.0) return 1.0 - x;
+  return 0.0;
+}
+
 static double bicubic_filter(double x) {
   const double a = -0.5;
   if (x < 0.0) x = -x;
@@ -174,21 +233,32 @@ static double bicubic_filter(double x) {
   return 0.0;
 }
 
-extern "C" int gan_resize_ksize(int in_size, int out_size) {
+struct ResizeFilter { double (*fn)(double); double support; };
+static bool resize_filter(int filter, ResizeFilter* f) {
+  if (filter == GAN_RESIZE_BILINEAR) { f->fn = bilinear_filter; f->support = 1.0; return true; }
+  if (filter == GAN_RESIZE_BICUBIC) { f->fn = bicubic_filter; f->support = 2.0; return true; }
+  return false;
+}
+
+extern "C" int gan_resize_ksize_filter(int in_size, int out_size, int filter) {
+  ResizeFilter f;
+  if (!resize_filter(filter, &f)) return gan_set_error(-1, "resize_ksize: unknown filter %d (BILINEAR = 2, BICUBIC = 3)", filter);
   if (in_size <= 0 || out_size <= 0) return gan_set_error(-1, "resize_ksize: sizes must be positive (%d -> %d)", in_size, out_size);
   double filterscale = (double)in_size / out_size;
   if (filterscale < 1.0) filterscale = 1.0;
-  return (int)ceil(2.0 * filterscale) * 2 + 1;
+  return (int)ceil(f.support * filterscale) * 2 + 1;
 }
 
-extern "C" int gan_resize_coeffs(int in_size, int out_size, int32_t* bounds, int32_t* kk, int ksize) {
+extern "C" int gan_resize_coeffs_filter(int in_size, int out_size, int filter, int32_t* bounds, int32_t* kk, int ksize) {
+  ResizeFilter f;
+  GAN_CHECK(resize_filter(filter, &f), "resize_coeffs: unknown filter %d (BILINEAR = 2, BICUBIC = 3)", filter);
   GAN_CHECK(in_size > 0 && out_size > 0 && bounds && kk, "resize_coeffs: bad arguments (%d -> %d)", in_size, out_size);
-  GAN_CHECK(ksize == gan_resize_ksize(in_size, out_size), "resize_coeffs: ksize must be gan_resize_ksize(in, out) = %d, got %d",
-            gan_resize_ksize(in_size, out_size), ksize);
+  GAN_CHECK(ksize == gan_resize_ksize_filter(in_size, out_size, filter), "resize_coeffs: ksize must be gan_resize_ksize(in, out) = %d, got %d",
+            gan_resize_ksize_filter(in_size, out_size, filter), ksize);
   const double in0 = 0.0, in1 = (double)in_size;
   double scale = (in1 - in0) / out_size, filterscale = scale;
   if (filterscale < 1.0) filterscale = 1.0;
-  const double support = 2.0 * filterscale, ss = 1.0 / filterscale;
+  const double support = f.support * filterscale, ss = 1.0 / filterscale;
   double w[1024];
   GAN_CHECK(ksize <= 1024, "resize_coeffs: downscale factor too large (ksize %d)", ksize);
   for (int xx = 0; xx < out_size; ++xx) {
@@ -199,7 +269,7 @@ extern "C" int gan_resize_coeffs(int in_size, int out_size, int32_t* bounds, int
     if (xmax > in_size) xmax = in_size;
     xmax -= xmin;
     double ww = 0.0;
-    for (int x = 0; x < xmax; ++x) { w[x] = bicubic_filter((x + xmin - center + 0.5) * ss); ww += w[x]; }
+    for (int x = 0; x < xmax; ++x) { w[x] = f.fn((x + xmin - center + 0.5) * ss); ww += w[x]; }
     int32_t* k = kk + (int64_t)xx * ksize;
     for (int x = 0; x < ksize; ++x) {
       if (x >= xmax) { k[x] = 0; continue; }
@@ -211,8 +281,15 @@ extern "C" int gan_resize_coeffs(int in_size, int out_size, int32_t* bounds, int
   return 0;
 }
 
-extern "C" int gan_input_pipeline(const gan_input_job* jobs_dev, const gan_input_job* jobs_host, int B, const int32_t* tables_dev, int S,
-                                  uint8_t* tmp, int tmp_rows, uint8_t* img, int32_t* mean_ws, float* out, void* stream) {
+extern "C" int gan_resize_ksize(int in_size, int out_size) { return gan_resize_ksize_filter(in_size, out_size, GAN_RESIZE_BICUBIC); }
+
+extern "C" int gan_resize_coeffs(int in_size, int out_size, int32_t* bounds, int32_t* kk, int ksize) {
+  return gan_resize_coeffs_filter(in_size, out_size, GAN_RESIZE_BICUBIC, bounds, kk, ksize);
+}
+
+extern "C" int gan_input_pipeline_filter(const gan_input_job* jobs_dev, const gan_input_job* jobs_host, int B, const int32_t* tables_dev, int S,
+                                         int filter, uint8_t* tmp, int tmp_rows, uint8_t* img, int32_t* mean_ws, float* out, void* stream) {
+  GAN_CHECK(filter == GAN_RESIZE_BILINEAR || filter == GAN_RESIZE_BICUBIC, "input_pipeline: unknown filter %d (BILINEAR = 2, BICUBIC = 3)", filter);
   GAN_CHECK(jobs_dev && jobs_host && tables_dev && tmp && img && mean_ws && out && B > 0 && S > 0, "input_pipeline: null pointer or empty batch");
   int max_rows = 0;
   bool slot_used[4] = {false, false, false, false}, slot_mean[4] = {false, false, false, false};
@@ -222,7 +299,7 @@ extern "C" int gan_input_pipeline(const gan_input_job* jobs_dev, const gan_input
               "input_pipeline: image %d: crop box (%d,%d,%d,%d) outside a row of %d bytes", b, j.crop_y, j.crop_x, j.crop_h, j.crop_w, j.src_stride);
     GAN_CHECK(j.win_y >= 0 && j.win_x >= 0 && j.win_y + S <= j.res_h && j.win_x + S <= j.res_w,
               "input_pipeline: image %d: %dx%d window at (%d,%d) outside the %dx%d resized image", b, S, S, j.win_y, j.win_x, j.res_h, j.res_w);
-    GAN_CHECK(j.hksize == gan_resize_ksize(j.crop_w, j.res_w) && j.vksize == gan_resize_ksize(j.crop_h, j.res_h),
+    GAN_CHECK(j.hksize == gan_resize_ksize_filter(j.crop_w, j.res_w, filter) && j.vksize == gan_resize_ksize_filter(j.crop_h, j.res_h, filter),
               "input_pipeline: image %d: tap counts do not match its sizes", b);
     GAN_CHECK(j.crop_h <= tmp_rows, "input_pipeline: image %d: %d source rows > tmp_rows %d", b, j.crop_h, tmp_rows);
     if (j.crop_h > max_rows) max_rows = j.crop_h;
@@ -242,6 +319,26 @@ extern "C" int gan_input_pipeline(const gan_input_job* jobs_dev, const gan_input
     hipLaunchKernelGGL(input_jitter_kernel, dim3(gp, B), dim3(256), 0, s, jobs_dev, img, S, slot, mean_ws);
   }
   hipLaunchKernelGGL(input_finish_kernel, dim3(gp, B), dim3(256), 0, s, jobs_dev, img, S, out);
+  GAN_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int gan_input_pipeline(const gan_input_job* jobs_dev, const gan_input_job* jobs_host, int B, const int32_t* tables_dev, int S,
+                                  uint8_t* tmp, int tmp_rows, uint8_t* img, int32_t* mean_ws, float* out, void* stream) {
+  return gan_input_pipeline_filter(jobs_dev, jobs_host, B, tables_dev, S, GAN_RESIZE_BICUBIC, tmp, tmp_rows, img, mean_ws, out, stream);
+}
+
+extern "C" int gan_view_to_u8_hwc(const gan_view* src, int C, uint8_t* dst, void* stream) {
+  if (gan_check_view(src, "view_to_u8_hwc.src")) return -1;
+  GAN_CHECK(src->dtype == GAN_F32 || src->dtype == GAN_BF16, "view_to_u8_hwc: the view must be fp32 or bf16 (dtype %d)", src->dtype);
+  GAN_CHECK(dst && C >= 1 && C <= 4 && C <= src->C, "view_to_u8_hwc: bad C=%d (1 .. 4 channels)", C);
+  const int64_t total = (int64_t)src->B * src->H * ((src->W + 3) / 4);
+  const int grid = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
+  const bool packed = C == 3 && src->W % 4 == 0 && (uintptr_t)dst % 4 == 0;
+  DView sv = to_dview(src);
+  GAN_DISPATCH_DTYPE(src->dtype,
+    if (packed) hipLaunchKernelGGL((view_to_u8_hwc_kernel<T, true>), dim3(grid), dim3(256), 0, (hipStream_t)stream, sv, C, dst);
+    else hipLaunchKernelGGL((view_to_u8_hwc_kernel<T, false>), dim3(grid), dim3(256), 0, (hipStream_t)stream, sv, C, dst);)
   GAN_LAUNCH_CHECK();
   return 0;
 }

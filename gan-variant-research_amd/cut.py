@@ -148,6 +148,14 @@ class ResNetGenerator(nn.Module):
         from . import autograd as AG
         return AG.generator_forward(self, x, "cut")
 
+    def forward_u8(self, x):
+        """Forward-only: (B,3,H,W) fp32 in [-1,1] -> (B,H,W,3) uint8 on the device, clamp(-1,1)*0.5+0.5, *255, round (generate_folder.py:
+        183-185) fused with the HWC turn into one kernel after the last layer.  Bit-identical to that chain applied to forward(x)."""
+        if self._layerwise:
+            raise NotImplementedError("forward_u8 needs the module-granular engine (instance norm, reflect | zero padding, two down-samplings)")
+        from . import autograd as AG
+        return AG.generator_forward_u8(self, x, "cut")
+
     def get_feature_layers(self, x, layer_ids=None):
         """generator_resnet_attn.py:190-235: numbered activations; ids beyond the last one are silently ignored there too."""
         if self._layerwise:

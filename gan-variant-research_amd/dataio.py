@@ -25,6 +25,7 @@ from . import _lib
 from ._lib import GanError, GanInputJob
 
 BRIGHTNESS, CONTRAST, SATURATION, HUE = 0, 1, 2, 3
+BILINEAR, BICUBIC = _lib.RESIZE_BILINEAR, _lib.RESIZE_BICUBIC      # Pillow's ids; the training transforms use BICUBIC, inference BILINEAR
 
 
 # ------------------------------------------------------------------------------------------------ jobs (host side, per image)
@@ -63,6 +64,12 @@ def eval_job(h: int, w: int, image_size: int = 256) -> Dict:
     return _job(h, w, (0, 0, h, w), (image_size, image_size), (0, 0, image_size, image_size))
 
 
+def infer_job(h: int, w: int, image_size: int = 256) -> Dict:
+    """generate_folder.py:175-180: the whole image resized to S x S, no flip, no jitter -- eval_job's geometry; the reference resizes
+    with BILINEAR there, which is the pipeline's `filter`, not the job's."""
+    return eval_job(h, w, image_size)
+
+
 def _resize_smaller_edge(h: int, w: int, size: int) -> Tuple[int, int]:
     """torchvision Resize(int): the smaller edge becomes `size`, the other int(size * long / short)."""
     if w <= h:
@@ -90,33 +97,37 @@ def basic_job(h: int, w: int, load_size: int = 286, crop_size: int = 256, train:
 # ------------------------------------------------------------------------------------------------ the device pipeline
 class InputPipeline:
     """Batched transform on one GPU.  `run(images, jobs)`: images = uint8 (H, W, 3) device tensors (one per job, any sizes), jobs from
-    the `*_job` functions (all with an S x S window) -> (B, 3, S, S) fp32 in [-1, 1].  Tap tables are cached per (source, target) size;
-    jobs and tables travel in one pinned block and one asynchronous copy per batch."""
+    the `*_job` functions (all with an S x S window) -> (B, 3, S, S) fp32 in [-1, 1].  `filter` is Pillow's resampling filter of every
+    resize the pipeline makes (BICUBIC or BILINEAR).  Tap tables are cached per (source, target, filter); jobs and tables travel in one
+    pinned block and one asynchronous copy per batch.  `max_rows` sizes the buffer between the two resize passes; a batch with a
+    taller image grows it."""
 
-    def __init__(self, image_size: int, device, max_batch: int = 64, max_rows: int = 1024):
-        self.S, self.device = int(image_size), torch.device(device)
+    def __init__(self, image_size: int, device, max_batch: int = 64, max_rows: int = 1024, filter: int = BICUBIC):
+        self.S, self.device, self.filter = int(image_size), torch.device(device), int(filter)
         if self.device.type != "cuda":
             raise GanError("the input pipeline runs on the GPU (there is no CPU fallback)")
+        if self.filter not in (BILINEAR, BICUBIC):
+            raise GanError(f"input pipeline: unknown filter {filter} (BILINEAR = {BILINEAR}, BICUBIC = {BICUBIC})")
         self.lib = _lib.load()
         self.max_batch, self.max_rows = max_batch, max_rows
         S = self.S
         self._tmp = torch.zeros(max_batch * max_rows * S * 4, dtype=torch.uint8, device=self.device)
         self._img = torch.zeros(max_batch * S * S * 4, dtype=torch.uint8, device=self.device)
         self._mean = torch.zeros(max_batch, dtype=torch.int32, device=self.device)
-        self._taps: Dict[Tuple[int, int], Tuple[np.ndarray, np.ndarray, int]] = {}
+        self._taps: Dict[Tuple[int, int, int], Tuple[np.ndarray, np.ndarray, int]] = {}
         self._block_bytes = 0
         self._host = self._dev = None
 
     def taps(self, in_size: int, out_size: int):
-        """(bounds [out][2], taps [out][ksize], ksize) of Pillow's bicubic resize in_size -> out_size, from the library."""
-        key = (in_size, out_size)
+        """(bounds [out][2], taps [out][ksize], ksize) of Pillow's resize in_size -> out_size with the pipeline's filter, from the library."""
+        key = (in_size, out_size, self.filter)
         t = self._taps.get(key)
         if t is None:
-            k = self.lib.gan_resize_ksize(in_size, out_size)
+            k = self.lib.gan_resize_ksize_filter(in_size, out_size, self.filter)
             if k < 0:
                 raise GanError(self.lib.gan_last_error().decode())
             bounds, kk = np.zeros((out_size, 2), np.int32), np.zeros((out_size, k), np.int32)
-            _lib.check(self.lib.gan_resize_coeffs(in_size, out_size, bounds.ctypes.data, kk.ctypes.data, k), "gan_resize_coeffs")
+            _lib.check(self.lib.gan_resize_coeffs_filter(in_size, out_size, self.filter, bounds.ctypes.data, kk.ctypes.data, k), "gan_resize_coeffs_filter")
             t = self._taps[key] = (bounds, kk, k)
         return t
 
@@ -135,8 +146,9 @@ class InputPipeline:
             if jb["window"][2:] != (S, S):
                 raise GanError(f"input pipeline: job {b} has a {jb['window'][2:]} window, the pipeline produces {S}x{S}")
             cy, cx, ch, cw = jb["crop"]
-            if ch > self.max_rows:
-                raise GanError(f"input pipeline: image {b} needs {ch} source rows, max_rows is {self.max_rows}")
+            if ch > self.max_rows:      # photo folders are not uniform: grow (queued launches keep the old buffer, freed in stream order)
+                self.max_rows = -(-ch // 256) * 256
+                self._tmp = torch.zeros(self.max_batch * self.max_rows * S * 4, dtype=torch.uint8, device=self.device)
             js = structs[b]
             js.src, js.src_stride = im.data_ptr(), im.stride(0)
             js.crop_y, js.crop_x, js.crop_h, js.crop_w = cy, cx, ch, cw
@@ -182,9 +194,10 @@ class InputPipeline:
         if out is None:
             out = torch.empty(B, 3, S, S, dtype=torch.float32, device=self.device)
         assert out.shape == (B, 3, S, S) and out.dtype == torch.float32 and out.is_contiguous() and out.device == self.device
-        rc = self.lib.gan_input_pipeline(self._dev.data_ptr(), hv.ctypes.data, B, self._dev.data_ptr() + jbytes, S, self._tmp.data_ptr(), self.max_rows,
-                                         self._img.data_ptr(), self._mean.data_ptr(), out.data_ptr(), ts.cuda_stream)
-        _lib.check(rc, "gan_input_pipeline")
+        rc = self.lib.gan_input_pipeline_filter(self._dev.data_ptr(), hv.ctypes.data, B, self._dev.data_ptr() + jbytes, S, self.filter,
+                                                self._tmp.data_ptr(), self.max_rows, self._img.data_ptr(), self._mean.data_ptr(), out.data_ptr(),
+                                                ts.cuda_stream)
+        _lib.check(rc, "gan_input_pipeline_filter")
         return out
 
 

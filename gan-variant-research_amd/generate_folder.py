@@ -1,0 +1,59 @@
+"""Inference driver with the reference's command line (GAN_Variant1/generate_folder.py:255-292):
+
+    python -m gan_variant_research_amd.generate_folder --ckpt CKPT --photos DIR --out DIR [--batch 16] [--size 256] [--device cuda|cpu] [--limit N]
+
+Same flags, defaults and messages; the checkpoint is chosen as the reference chooses it (EMA shadow first, inference.pick_state_dict);
+the output tree mirrors the input tree as JPEGs (quality 95, 4:4:4).  What differs is what runs underneath: the generator is the HIP
+engine, and on the GPU the resize, the normalisation and the uint8 conversion run there as well (inference.stylize_images).
+Build-only flags: --ngf / --n-blocks (the reference reads the architecture from its own module), --fp32 (bf16 operands stand in for the
+reference's autocast by default), --graph (one hipGraph replay per batch shape), --host-io (resize and convert with PIL / torch on the host).
+"""
+from __future__ import annotations
+
+import argparse
+
+import torch
+
+from . import inference as I
+
+
+def parse_args(argv=None) -> argparse.Namespace:
+    """generate_folder.py:255-264, plus the build-only flags."""
+    ap = argparse.ArgumentParser(description="Stylize a folder of photos with a trained CUT++ generator (MI355X-native).")
+    ap.add_argument("--ckpt", required=True, help="Path to ckpt_final.pt or ckpt_stepXXXX.pt")
+    ap.add_argument("--photos", required=True, help="Path to source photos folder (e.g., Kaggle photo_jpg)")
+    ap.add_argument("--out", required=True, help="Output folder for generated JPGs")
+    ap.add_argument("--batch", type=int, default=16, help="Batch size for inference")
+    ap.add_argument("--size", type=int, default=256, help="Output resolution (and input resize)")
+    ap.add_argument("--device", default="cuda", choices=["cuda", "cpu"], help="Device")
+    ap.add_argument("--limit", type=int, default=None, help="Optionally limit number of images for quick tests")
+    ap.add_argument("--ngf", type=int, default=64, help="generator width of the checkpoint (build-only flag)")
+    ap.add_argument("--n-blocks", type=int, default=9, help="residual blocks of the checkpoint (build-only flag)")
+    ap.add_argument("--fp32", action="store_true", help="fp32 operands instead of bf16 (build-only flag)")
+    ap.add_argument("--graph", action="store_true", help="replay the generator pass as one hipGraph per batch shape (build-only flag)")
+    ap.add_argument("--host-io", action="store_true", help="resize / normalise / convert on the host instead of the device (build-only flag)")
+    return ap.parse_args(argv)
+
+
+def main(argv=None) -> int:
+    args = parse_args(argv)
+    if args.device == "cuda" and not torch.cuda.is_available():
+        print("[WARN] CUDA not available. Falling back to CPU.")
+        args.device = "cpu"
+
+    print(f"Loading generator from: {args.ckpt}")
+    G = I.load_generator(args.ckpt, device=args.device, ngf=args.ngf, n_blocks=args.n_blocks, bf16=not args.fp32, use_graph=args.graph)
+    n_params = sum(p.numel() for p in G.parameters())
+    print(f"Generator parameters: {n_params:,}")
+
+    print(f"Stylizing from '{args.photos}' -> '{args.out}' "
+          f"(size={args.size}, batch={args.batch}, device={args.device})")
+    # the device input pipeline and the uint8 epilogue are HIP kernels: they run exactly when the generator runs on the HIP library
+    n = I.stylize_folder(G, src_dir=args.photos, out_dir=args.out, device=args.device, img_size=args.size, batch=args.batch, limit=args.limit,
+                         device_io=args.device == "cuda" and not args.host_io)
+    print("Done.")
+    return n
+
+
+if __name__ == "__main__":
+    main()

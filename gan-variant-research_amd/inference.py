@@ -2,13 +2,16 @@
 
 `load_generator` takes the reference's checkpoints (or this package's: same layout) and prefers the EMA weights exactly as
 generate_folder.py:125-170 does; `stylize` is the tensor-level body of `stylize_folder` (:207-252): G(x) then
-clamp -> *0.5 + 0.5 -> *255 -> round -> uint8 (:183-185).  Decoding / resizing / JPEG encoding of files is the input pipeline
-(torchvision + PIL in the reference) and stays outside this package; `stylize_folder` is provided for PIL-readable folders.
+clamp -> *0.5 + 0.5 -> *255 -> round -> uint8 (:183-185).  `stylize_hwc` is the same with the conversion and the HWC turn PIL needs
+fused into one kernel after the generator's last layer (gan_view_to_u8_hwc), `stylize_images` puts the device input pipeline with
+Pillow's BILINEAR taps (:175-180) in front of it.  JPEG / PNG decoding and JPEG encoding stay in PIL on the host; `stylize_folder`
+walks a PIL-readable folder, with the resize and both conversions on the host (the default) or on the device (`device_io=True`).
+The command line is generate_folder.py next to this file.
 """
 from __future__ import annotations
 
 from pathlib import Path
-from typing import Dict, Iterable, Optional
+from typing import Dict, Iterable, Optional, Sequence
 
 import torch
 
@@ -67,8 +70,32 @@ def stylize(G: ResNetGenerator, x: torch.Tensor) -> torch.Tensor:
 
 
 @torch.inference_mode()
-def stylize_folder(G, src_dir: str, out_dir: str, device: str = "cuda", img_size: int = 256, batch: int = 16, limit: Optional[int] = None) -> int:
-    """generate_folder.py:207-252 with PIL doing what torchvision's Resize(BILINEAR) / ToTensor / Normalize / ToPILImage do there."""
+def stylize_hwc(G: ResNetGenerator, x: torch.Tensor) -> torch.Tensor:
+    """(B,3,H,W) fp32 in [-1,1] on the GPU -> (B,H,W,3) uint8 on the GPU: `stylize(G, x).permute(0, 2, 3, 1)`, bit for bit, without
+    the fp32 NCHW tensor, its clone and the elementwise launches in between."""
+    return G.forward_u8(x)
+
+
+@torch.inference_mode()
+def stylize_images(G: ResNetGenerator, images: Sequence[torch.Tensor], img_size: int = 256) -> torch.Tensor:
+    """Decoded uint8 (H, W, 3) device tensors of any sizes -> (B, S, S, 3) uint8 on the device: Resize((S, S), BILINEAR) -> ToTensor ->
+    Normalize(0.5, 0.5) (generate_folder.py:175-180) on the device, bit-identical to Pillow, then the generator and its uint8 epilogue."""
+    from . import dataio
+    dev = images[0].device
+    pipe = getattr(G, "_infer_pipe", None)
+    if pipe is None or pipe.S != img_size or pipe.device != dev or pipe.max_batch < len(images):
+        pipe = dataio.InputPipeline(img_size, dev, max_batch=max(16, len(images)), filter=dataio.BILINEAR)
+        object.__setattr__(G, "_infer_pipe", pipe)            # plain attribute, like the module's bridge
+    x = pipe.run(images, [dataio.infer_job(int(im.shape[0]), int(im.shape[1]), img_size) for im in images])
+    return stylize_hwc(G, x)
+
+
+@torch.inference_mode()
+def stylize_folder(G, src_dir: str, out_dir: str, device: str = "cuda", img_size: int = 256, batch: int = 16, limit: Optional[int] = None,
+                   device_io: bool = False) -> int:
+    """generate_folder.py:207-252 with PIL doing what torchvision's Resize(BILINEAR) / ToTensor / Normalize / ToPILImage do there.
+    device_io: PIL only decodes and encodes; each photo is uploaded as uint8 HWC, `stylize_images` resizes, normalises, runs the
+    generator and converts on the device, and one contiguous HWC download feeds PIL.  The files written are byte-identical."""
     import numpy as np
     from PIL import Image
     exts = {".jpg", ".jpeg", ".png", ".bmp", ".webp", ".tif", ".tiff"}
@@ -81,9 +108,13 @@ def stylize_folder(G, src_dir: str, out_dir: str, device: str = "cuda", img_size
     out_root.mkdir(parents=True, exist_ok=True)
     for i in range(0, len(paths), batch):
         chunk = paths[i:i + batch]
-        arr = np.stack([np.asarray(Image.open(p).convert("RGB").resize((img_size, img_size), Image.BILINEAR), dtype=np.float32) for p in chunk])
-        x = torch.from_numpy(arr).permute(0, 3, 1, 2).div(255.0).sub(0.5).div(0.5).contiguous().to(device)
-        y = stylize(G, x).cpu().permute(0, 2, 3, 1).numpy()
+        if device_io:
+            imgs = [torch.from_numpy(np.array(Image.open(p).convert("RGB"))).to(device) for p in chunk]
+            y = stylize_images(G, imgs, img_size).cpu().numpy()
+        else:
+            arr = np.stack([np.asarray(Image.open(p).convert("RGB").resize((img_size, img_size), Image.BILINEAR), dtype=np.float32) for p in chunk])
+            x = torch.from_numpy(arr).permute(0, 3, 1, 2).div(255.0).sub(0.5).div(0.5).contiguous().to(device)
+            y = stylize(G, x).cpu().permute(0, 2, 3, 1).numpy()
         for p, img in zip(chunk, y):
             save = (out_root / p.relative_to(src_root)).with_suffix(".jpg")
             save.parent.mkdir(parents=True, exist_ok=True)

@@ -539,6 +539,11 @@ class HipOps:
         assert dst.dtype == torch.float32 and dst.is_contiguous()
         return self._call("gan_view_to_nchw", self._v(src), Cr, self._p(dst), self._s())
 
+    def view_to_u8_hwc(self, src: View, Cr, dst: torch.Tensor) -> Op:
+        """Interior of src -> packed (B, H, W, Cr) uint8: clamp(-1, 1) * 0.5 + 0.5, * 255, round half to even (inference.to_uint8)."""
+        assert dst.dtype == torch.uint8 and dst.is_contiguous() and tuple(dst.shape) == (src.B, src.H, src.W, Cr)
+        return self._call("gan_view_to_u8_hwc", self._v(src), Cr, self._p(dst), self._s())
+
     def view_copy(self, src: View, dst: View, halo_mode) -> Op:
         return self._call("gan_view_copy", self._v(src), self._v(dst), halo_mode, self._s())
 

@@ -311,6 +311,14 @@ int gan_view_copy(const gan_view* src, const gan_view* dst, int halo_mode, void*
 /* The three are exact: every value is rounded once to the destination type (a NaN stays a NaN in exactly the copies that read it).
  * gan_nchw_to_view writes 0 to channels C .. dst->C of every pixel it writes; GAN_HALO_NONE writes the interior only, GAN_HALO_REFLECT
  * (both calls; needs y0 < H and x0 < W) and GAN_HALO_REPLICATE (gan_nchw_to_view) the padded extent of y0 / x0 pixels as well. */
+/* Output epilogue of inference (GAN_Variant1/generate_folder.py:183-185 fused with the NCHW -> HWC turn): dst is packed [B][H][W][C]
+ * uint8, 1 <= C <= 4, C <= src->C, src fp32 or bf16;  dst[b][y][x][c] = (uint8) rint(((clamp(v, -1, 1) * 0.5f) + 0.5f) * 255.f) with v
+ * the interior value as fp32, every operation rounded to fp32 on its own, rint half to even: bit-identical to
+ * y.clamp(-1, 1).mul(0.5).add(0.5).mul(255).round().byte() of what the fp32 NCHW conversion above writes, permuted to HWC.
+ * A NaN gives 0 (torch leaves that conversion undefined); +-inf clamp like any other value.  Halo pixels are never read and the
+ * values of the pad channels C .. src->C never reach dst.  C == 3 with W % 4 == 0 and a four-byte aligned dst (the generator's case)
+ * is written as dwords, anything else as bytes. */
+int gan_view_to_u8_hwc(const gan_view* src, int C, uint8_t* dst, void* stream);
 
 /* ---- AvgPool2d(kernel 3, stride 2, padding 1, count_include_pad=False): the downsampling between the scales of
  *      MultiscaleDiscriminator (GAN_Variant1/models/discriminator_patchgan.py:100, 110-112; get_intermediate_features :125-127).
@@ -387,13 +395,24 @@ typedef struct gan_input_job {
   int32_t hb_off, hk_off, hksize;  /* horizontal taps in the tables block (int32 units): bounds [res_w][2], taps [res_w][hksize] */
   int32_t vb_off, vk_off, vksize;  /* vertical taps: bounds [res_h][2], taps [res_h][vksize] */
 } gan_input_job;
-/* Pillow's bicubic taps for resizing in_size -> out_size (Resample.c precompute_coeffs, 22-bit fixed point).  Host-only, no GPU. */
+/* Pillow's taps for resizing in_size -> out_size (Resample.c precompute_coeffs + normalize_coeffs_8bpc, 22-bit fixed point).  Host-only,
+ * no GPU.  The filter ids are Pillow's: BILINEAR is Resample.c bilinear_filter (1 - |x| for |x| < 1, support 1), BICUBIC its
+ * bicubic_filter (Keys, a = -0.5, support 2); ksize = ceil(support * max(in / out, 1)) * 2 + 1.  Any other id is an error.  The two
+ * entries without a filter argument are the BICUBIC case. */
+enum { GAN_RESIZE_BILINEAR = 2, GAN_RESIZE_BICUBIC = 3 };
+int gan_resize_ksize_filter(int in_size, int out_size, int filter);
+int gan_resize_coeffs_filter(int in_size, int out_size, int filter, int32_t* bounds /* [out][2]: first index, count */,
+                             int32_t* kk /* [out][ksize] */, int ksize);
 int gan_resize_ksize(int in_size, int out_size);
 int gan_resize_coeffs(int in_size, int out_size, int32_t* bounds /* [out][2]: first index, count */, int32_t* kk /* [out][ksize] */, int ksize);
 /* jobs_dev/tables_dev: device copies; jobs_host: the same jobs readable by the host (validation, launch shapes).
  * tmp: >= B*tmp_rows*S*4 bytes (tmp_rows >= max crop_h); img: B*S*S*4 bytes; mean_ws: B int32; out: fp32 [B][3][S][S] in [-1,1]. */
 int gan_input_pipeline(const gan_input_job* jobs_dev, const gan_input_job* jobs_host, int B, const int32_t* tables_dev, int S,
                        uint8_t* tmp, int tmp_rows, uint8_t* img, int32_t* mean_ws, float* out, void* stream);
+/* The same with the jobs' tap counts validated against `filter` (one filter per call; the tables in the block are that filter's).
+ * The resize kernels read tables, so nothing else differs; the entry above is the BICUBIC case. */
+int gan_input_pipeline_filter(const gan_input_job* jobs_dev, const gan_input_job* jobs_host, int B, const int32_t* tables_dev, int S,
+                              int filter, uint8_t* tmp, int tmp_rows, uint8_t* img, int32_t* mean_ws, float* out, void* stream);
 
 /* ---- losses.  Every loss writes its value to *loss (device fp32, overwritten) and the gradient wrt its input.
  *      hinge: adv_hinge.py:6-62 (mode 0: mean relu(1-x), 1: mean relu(1+x), 2: -mean x), scaled by `scale`;

@@ -1,0 +1,123 @@
+"""Inference I/O, old path against new path in the same process (256x256, bf16, B = 1, 4, 16).
+
+(a) output path: inference.stylize + download + host permute to HWC   vs   inference.stylize_hwc + one contiguous download
+(b) folder path: inference.stylize_folder on 64 seeded PNGs of mixed sizes, host I/O vs device I/O (images/s, decode and JPEG encode included)
+
+Every shape is warmed up; the two paths are then timed in rotation for --rounds rounds (a host clock around work that ends in a device
+synchronise: each call ends in a download); the median round and the spread (min .. max) are reported.  The outputs of the two paths
+are compared before anything is timed.
+usage: bench_stylize.py [--size 256] [--batches 1,4,16] [--calls 40] [--rounds 5] [--photos 64] [--out FILE]
+"""
+import argparse
+import os
+import statistics
+import sys
+import tempfile
+import time
+from pathlib import Path
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from gan_variant_research_amd import BF16, cut as C, inference as I  # noqa: E402
+
+
+def make_folder(root: Path, n: int, seed: int = 0):
+    """n PNGs of mixed sizes (120 .. 640 pixels a side) under root and root/sub, smooth content plus noise, from a seed."""
+    from PIL import Image
+    rng = np.random.default_rng(seed)
+    (root / "sub").mkdir(parents=True, exist_ok=True)
+    for i in range(n):
+        h, w = (int(v) for v in rng.integers(120, 641, 2))
+        yy, xx = np.mgrid[0:h, 0:w]
+        base = np.stack([127 + 120 * np.sin(yy / 17.0 + c + i) * np.cos(xx / 23.0 - c) for c in range(3)], -1)
+        img = np.clip(base + rng.integers(-20, 21, (h, w, 3)), 0, 255).astype(np.uint8)
+        Image.fromarray(img).save(root / ("sub" if i % 4 == 0 else ".") / f"p{i:03d}.png")
+
+
+def rotate(paths, rounds):
+    """paths: name -> callable returning the seconds one round of it took.  Runs them in rotation; name -> list of round times."""
+    times = {k: [] for k in paths}
+    for _ in range(rounds):
+        for k, fn in paths.items():
+            times[k].append(fn())
+    return times
+
+
+def line(label, unit, vals, better_is_lower):
+    a, b = (statistics.median(vals[k]) for k in ("old", "new"))
+    sa, sb = ((min(vals[k]), max(vals[k])) for k in ("old", "new"))
+    apart = sb[1] < sa[0] if better_is_lower else sb[0] > sa[1]          # every new round beats every old round
+    gain = a / b if better_is_lower else b / a
+    verdict = f"new/old speed {gain:.3f}x" + ("" if apart else "  (rounds overlap: not faster beyond the spread)")
+    return (f"{label}: old {a:.3f} {unit} [{sa[0]:.3f} .. {sa[1]:.3f}]   new {b:.3f} {unit} [{sb[0]:.3f} .. {sb[1]:.3f}]   {verdict}")
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--size", type=int, default=256)
+    ap.add_argument("--batches", default="1,4,16")
+    ap.add_argument("--calls", type=int, default=40)
+    ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--photos", type=int, default=64)
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    assert torch.cuda.is_available(), "bench_stylize.py measures on the GPU"
+    dev, S = torch.device("cuda:0"), a.size
+    C.set_seed(0)
+    G = C.ResNetGenerator(3, 3, 64, 9).to(dev).eval()
+    for p in G.parameters():
+        p.requires_grad_(False)
+    G.compute_dtype = BF16
+    lines = [f"# tools/bench_stylize.py --size {S} --batches {a.batches} --calls {a.calls} --rounds {a.rounds} --photos {a.photos}",
+             f"# generator ngf 64, 9 blocks, bf16 operands, eager launches; median of {a.rounds} alternating rounds [min .. max]",
+             f"# (a) ms per call of {a.calls} consecutive calls, each ending in the download of the uint8 HWC batch to the host"]
+    old_out = lambda x: I.stylize(G, x).cpu().permute(0, 2, 3, 1).contiguous()
+    new_out = lambda x: I.stylize_hwc(G, x).cpu()
+    for B in (int(v) for v in a.batches.split(",")):
+        x = (torch.rand(B, 3, S, S) * 2 - 1).to(dev)
+        for _ in range(3):
+            yo, yn = old_out(x), new_out(x)
+        assert torch.equal(yo, yn), "the two output paths differ"
+
+        def timed(fn):
+            def run():
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                for _ in range(a.calls):
+                    fn(x)
+                torch.cuda.synchronize()
+                return (time.perf_counter() - t0) / a.calls * 1e3
+            return run
+        lines.append(line(f"(a) B={B:2d} {S}x{S}", "ms", rotate({"old": timed(old_out), "new": timed(new_out)}, a.rounds), True))
+        print(lines[-1], flush=True)
+    lines.append(f"# (b) images/s over one pass of a folder of {a.photos} PNGs (120 .. 640 pixels a side), PNG decode and JPEG encode included")
+    with tempfile.TemporaryDirectory() as tmp:
+        tmp = Path(tmp)
+        make_folder(tmp / "photos", a.photos)
+        for B in (int(v) for v in a.batches.split(",")):
+            def folder(device_io, out):
+                def run():
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    n = I.stylize_folder(G, str(tmp / "photos"), str(tmp / out), device=str(dev), img_size=S, batch=B, device_io=device_io)
+                    torch.cuda.synchronize()
+                    return n / (time.perf_counter() - t0)
+                return run
+            paths = {"old": folder(False, f"host{B}"), "new": folder(True, f"dev{B}")}
+            for fn in paths.values():
+                fn()
+            ho = {p.name: p.read_bytes() for p in (tmp / f"host{B}").rglob("*.jpg")}
+            do = {p.name: p.read_bytes() for p in (tmp / f"dev{B}").rglob("*.jpg")}
+            assert len(ho) == a.photos and ho == do, "the two folder paths wrote different files"
+            lines.append(line(f"(b) batch={B:2d} {S}x{S}", "images/s", rotate(paths, a.rounds), False))
+            print(lines[-1], flush=True)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+
+
+if __name__ == "__main__":
+    main()
