@@ -47,7 +47,10 @@ __global__ __launch_bounds__(256) void adam_apply_kernel(const gan_adam_tensor* 
   for (int i = threadIdx.x; i < nchunks; i += 256) s += ws[i];
   s = block_sum(s, sh);
   const float total = sqrtf(s);
-  const float coef = max_norm > 0.f ? fminf(1.f, max_norm / (total + 1e-6f)) : 1.f;
+  // clip_grad_norm_ clamps with torch.clamp, which keeps a NaN: a NaN norm gives a NaN coefficient and every gradient goes NaN.  fminf
+  // would return 1 and update every tensor without a NaN as if nothing had happened.  An Inf norm gives 0 either way.
+  const float clip = max_norm / (total + 1e-6f);
+  const float coef = max_norm > 0.f ? (clip != clip ? clip : fminf(1.f, clip)) : 1.f;
   // GradScaler.step: an inf / nan anywhere in the (unscaled) gradients shows in the global norm; the whole step is then skipped
   const bool found_inf = !(total <= 3.4028234e38f);
   if (blockIdx.x == 0 && threadIdx.x == 0) { norm_out[0] = total; norm_out[1] = coef; norm_out[2] = found_inf ? 1.f : 0.f; }

@@ -15,6 +15,10 @@
 // trainer never materialises W_sn: the operand copies are packed from W with scale = sigma, and the backward uses <G, W> / sigma.
 #include "common.h"
 
+// max(x, eps) as F.normalize takes it (torch.clamp_min): a NaN norm stays NaN, so a NaN anywhere in the vector makes all of the
+// normalised vector NaN.  fmaxf(NaN, eps) is eps, which would leave the other elements finite (and huge).
+static __device__ __forceinline__ float sn_clamp_min(float x, float eps) { return x < eps ? eps : x; }
+
 namespace {
 
 // t[j] = sum_i W[i][j] * u[i]      (one thread per column, coalesced across j)
@@ -32,7 +36,7 @@ __global__ __launch_bounds__(1024) void sn_normalize_kernel(const float* __restr
   float s = 0.f;
   for (int i = threadIdx.x; i < n; i += 1024) s += x[i] * x[i];
   s = block_sum(s, sh);
-  const float d = fmaxf(sqrtf(s), eps);
+  const float d = sn_clamp_min(sqrtf(s), eps);
   for (int i = threadIdx.x; i < n; i += 1024) out[i] = x[i] / d;
 }
 
@@ -54,7 +58,7 @@ __global__ __launch_bounds__(1024) void sn_sigma_kernel(const float* __restrict_
     float q = 0.f;
     for (int i = threadIdx.x; i < h; i += 1024) q += s[i] * s[i];
     q = block_sum(q, sh);
-    d = fmaxf(sqrtf(q), eps);
+    d = sn_clamp_min(sqrtf(q), eps);
   }
   float a = 0.f;
   for (int i = threadIdx.x; i < h; i += 1024) {
@@ -191,7 +195,7 @@ __global__ __launch_bounds__(1024) void snb_finish_kernel(const gan_sn_desc* __r
     float q = 0.f;
     for (int c = threadIdx.x; c < g.Cb; c += blockDim.x) q += g.nrm[c];
     q = block_sum(q, sh);
-    d = fmaxf(sqrtf(q), eps);
+    d = sn_clamp_min(sqrtf(q), eps);
     for (int j = threadIdx.x; j < D.w; j += blockDim.x) {
       const float vj = g.t[j] / d;
       D.v[j] = vj;
@@ -209,7 +213,7 @@ __global__ __launch_bounds__(1024) void snb_finish_kernel(const gan_sn_desc* __r
     q2 += s * s;
   }
   float du = 1.f;
-  if (power_iter) du = fmaxf(sqrtf(block_sum(q2, sh)), eps);
+  if (power_iter) du = sn_clamp_min(sqrtf(block_sum(q2, sh)), eps);
   float a = 0.f;
   for (int i = threadIdx.x; i < D.h; i += blockDim.x) {
     const float s = g.sp[i];

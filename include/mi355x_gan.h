@@ -332,7 +332,14 @@ int gan_avgpool_bwd(const gan_view* gy, const gan_view* gx, int accumulate, void
  *      W = weight_orig as an h x w row-major matrix (h = Cout, w = Cin*kh*kw: the OIHW tensor itself); u [h], v [w] are the
  *      module's weight_u / weight_v buffers.  fwd: if power_iter, v <- normalize(W^T u), u <- normalize(W v) in place; then
  *      *sigma = u . (W v) and Wsn = W / sigma.  bwd: dW = (G - <G, Wsn> u v^T) / sigma with G = dL/dWsn (u, v, sigma: the values
- *      the forward left).  ws: fp32, >= gan_spectral_norm_ws_floats(h, w). */
+ *      the forward left).  ws: fp32, >= gan_spectral_norm_ws_floats(h, w) = h + w + 272 floats; nothing past it is written.
+ *      Range: the squares of t = W^T u and s = W v stay normal and their sums finite for 2^-63 <= |t_j|, ||t|| < 2^64 (the same for s);
+ *      smaller elements add at most 2^-126 each.  Below ||t|| < eps the divisor is eps (v = t / eps, not a unit vector): with the
+ *      reference's eps = 1e-12 a W scaled by 1e-15 is there, and an all-zero W gives u = v = 0, sigma = 0 and W_sn = 0 / 0 = NaN.
+ *      Non-finite, power_iter = 1: a NaN in W or u makes every element of u, v, sigma and W_sn NaN (the max with eps keeps a NaN
+ *      norm, as F.normalize's clamp_min does); v is overwritten without being read.  power_iter = 0: u and v are not written, and a
+ *      NaN in W, u or v makes sigma and every element of W_sn NaN.  bwd: a NaN in G makes every element of dW NaN (it enters
+ *      <G, W_sn>), and so does the NaN sigma and W_sn that such a forward leaves.  Refused: a NULL pointer, h <= 0 or w <= 0. */
 int64_t gan_spectral_norm_ws_floats(int h, int w);
 int gan_spectral_norm_fwd(const float* W, int h, int w, float* u, float* v, int power_iter, float eps, float* sigma, float* Wsn,
                           float* ws, void* stream);
@@ -346,7 +353,14 @@ int gan_spectral_norm_bwd(const float* G, const float* Wsn, const float* u, cons
  *        packed from W with gan_pack_desc.scale = sigma.  Semantics of gan_spectral_norm_fwd.
  *   bwd (2 launches): dW (+)= (G - (<G, W> / sigma) u_snap v_snap^T) / sigma, G = dL/dW_sn as the weight-gradient kernels leave it;
  *        accumulate lets the real and fake halves of a D-step add into one weight_orig gradient.
- * Reductions run in a fixed order without atomics: repeated calls are bit-identical. */
+ * Reductions run in a fixed order without atomics: repeated calls are bit-identical.
+ * Extents: h <= 512 x w <= 8192 is what the trainers use; h and w are otherwise only limited by int32 tile counts.  Per descriptor
+ *   ws >= gan_spectral_norm_batch_ws_floats(h, w) = R w + w + Cb + Cb h + R Cb floats (R = ceil(h / 32) row tiles, Cb = ceil(w / 256)
+ *   column tiles); nothing past it is written, and nothing past u[h), v[w), the snapshots, sigma[1) and dW[h w).
+ * Range and eps branch: as gan_spectral_norm_fwd.  Non-finite: a NaN in W, u or G of one descriptor reaches only that descriptor's
+ *   outputs (with power_iter = 1, W or u: u, v, sigma, the snapshots and dW all NaN; G: dW all NaN); every other descriptor keeps
+ *   its bits.
+ * Refused: descs NULL, n <= 0, total_blocks <= 0 (the descriptors themselves live on the device and are not validated). */
 typedef struct gan_sn_desc {
   const float* W;                /* weight_orig as an h x w row-major matrix */
   float* u; float* v;            /* the module's weight_u [h], weight_v [w] */
@@ -472,16 +486,34 @@ typedef struct gan_adam_tensor {
  *   LambdaLR with lambda_rule) rewrites one device float and the prebuilt launch stays valid.
  * inv_scale_dev (optional device float) and skip_nonfinite: torch.amp.GradScaler's unscale_ / step (amp_utils.py:29-41): gradients are
  *   multiplied by *inv_scale_dev, and with skip_nonfinite a non-finite total norm skips the update AND the step counters; found_inf is
- *   written to norm_out[2] either way (gan_scaler_update consumes it). */
+ *   written to norm_out[2] either way (gan_scaler_update consumes it).
+ * Extents: ws >= nchunks floats, all of them written; norm_out 3 floats; chunk k is the slice [chunk_off[k], chunk_off[k] + 16384) of
+ *   tensor chunk_tensor[k], cut at numel; the table has to cover every element of every tensor once.  Slices need no alignment.
+ * Scalars: beta1, beta2 and ema_decay are fp32, and 1 - beta is formed in fp32 from them; for beta2 = 0.999 that is 1.3e-5 (relative)
+ *   away from the 1 - 0.999 torch forms in double.  The bias corrections 1 - beta^t are evaluated in fp64 from the fp32 betas and the
+ *   device step counters (int32), then rounded once.  norm_out[1] is the coefficient applied; every element is the fp32 evaluation of
+ *   torch's single-tensor expression with that coefficient (tests/optim_cases.py counts its roundings).
+ * Range: the squares of the scaled gradients stay normal and their sum finite for 2^-63 <= |g * scale| < 2^64 / sqrt(number of live
+ *   elements); smaller gradients add at most 2^-126 each to the sum of squares, larger ones give an Inf norm (below).
+ * Non-finite gradients (skipped tensors are never read: a NaN in their p, m, v stays where it is and touches nothing):
+ *   skip_nonfinite = 1: norm_out[0] holds the NaN / Inf norm, norm_out[2] = 1, nothing else is written and no counter moves.
+ *   skip_nonfinite = 0, as torch.nn.utils.clip_grad_norm_ + Adam.step behave: with clipping on, a NaN gives the coefficient NaN
+ *     (clamp keeps it) and p, m, v of EVERY live tensor go NaN; an Inf gives the coefficient 0, the Inf element goes NaN (Inf * 0) and
+ *     all others take a zero gradient.  Without clipping only the non-finite elements go non-finite.  The counters move.
+ * Refused arguments (NULL table / chunk arrays / norm_out / ws, ntensors or nchunks <= 0) return -1 and launch nothing. */
 int gan_adam_step(const gan_adam_tensor* table, int ntensors, const int32_t* chunk_tensor, const int64_t* chunk_off,
                   int nchunks, float lr, float beta1, float beta2, float eps, float max_norm, float grad_scale,
                   float ema_decay, const float* lr_dev, const float* inv_scale_dev, int skip_nonfinite, float* norm_out, float* ws, void* stream);
 /* torch.amp.GradScaler.update on the device (amp_utils.py:22,41): scale *= backoff_factor after an overflow (found_inf != 0, e.g.
- * norm_out + 2 of gan_adam_step), *= growth_factor after growth_interval clean steps; inv_scale = 1 / scale; no host synchronisation. */
+ * norm_out + 2 of gan_adam_step), *= growth_factor after growth_interval clean steps; inv_scale = 1 / scale; no host synchronisation.
+ * One rounding for the product, one for the reciprocal.  A scale backed off below 2^-126 goes subnormal and 1 / scale overflows to Inf
+ * below 2^-128, as the fp32 expressions do: there is no floor.  Refused: a NULL pointer, growth_factor < 1, backoff_factor outside
+ * (0, 1], growth_interval <= 0. */
 int gan_scaler_update(float* scale, float* inv_scale, int32_t* growth_tracker, const float* found_inf, float growth_factor,
                       float backoff_factor, int growth_interval, void* stream);
 
-/* small helpers */
+/* small helpers: p[0 .. n) = v bit for bit (-0.0, NaN, Inf included); y[0 .. n) += a * x within one rounding of the multiply-add
+ * (contracted or not).  n = 0 does nothing; a NULL pointer or n < 0 returns -1 and writes nothing. */
 int gan_fill_f32(float* p, int64_t n, float v, void* stream);
 int gan_axpy_f32(float* y, const float* x, float a, int64_t n, void* stream);   /* y += a*x */
 

@@ -9,6 +9,8 @@ from __future__ import annotations
 
 import math
 
+import numpy as np
+
 import torch
 import torch.nn.functional as F
 
@@ -731,12 +733,18 @@ class EmuOps:
 
     def adam_step(self, table, ntensors, chunk_tensor, chunk_off, nchunks, lr, b1, b2, eps, max_norm, grad_scale, ema_decay, norm_out, ws,
                   lr_dev=None, inv_scale=None, skip_nonfinite=False):
+        f32 = lambda x: float(np.float32(x))
+        # the scalars as the C ABI receives them: 1 - beta and 1 - decay are formed from the fp32 values (for beta2 = 0.999 that is
+        # 1.3e-5 away from the double 1 - 0.999, relative)
+        lr, b1, b2, eps, max_norm, grad_scale, ema_decay = (f32(x) for x in (lr, b1, b2, eps, max_norm, grad_scale, ema_decay))
+
         def op():
             gs = grad_scale * (float(inv_scale) if inv_scale is not None else 1.0)
             rate = float(lr_dev) if lr_dev is not None else lr
             live = [e for e in table if e.get("g") is not None]
             tot = math.sqrt(sum(float(((e["g"] * gs) ** 2).sum()) for e in live))
-            coef = min(1.0, max_norm / (tot + 1e-6)) if max_norm > 0 else 1.0
+            clip = max_norm / (tot + 1e-6)
+            coef = (clip if math.isnan(clip) else min(1.0, clip)) if max_norm > 0 else 1.0      # torch.clamp keeps a NaN, min() does not
             found = not math.isfinite(tot)
             norm_out[0], norm_out[1], norm_out[2] = tot, coef, float(found)
             if skip_nonfinite and found:

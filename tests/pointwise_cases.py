@@ -89,27 +89,27 @@ class Fl:
         self.v = v if torch.is_tensor(v) else torch.tensor(float(v), dtype=torch.float64)
         self.e = torch.zeros_like(self.v) if e is None else e
 
-    @staticmethod
-    def of(a):
-        return a if isinstance(a, Fl) else Fl(a)
+    @classmethod
+    def of(cls, a):          # results take the class of the left operand, so a subclass (tests/optim_cases.py: E) keeps its operations
+        return a if isinstance(a, Fl) else cls(a)
 
     def __add__(self, o):
-        o = Fl.of(o)
+        o = self.of(o)
         v = self.v + o.v
-        return Fl(v, self.e + o.e + U * v.abs())
+        return type(self)(v, self.e + o.e + U * v.abs())
 
     def __sub__(self, o):
-        o = Fl.of(o)
+        o = self.of(o)
         v = self.v - o.v
-        return Fl(v, self.e + o.e + U * v.abs())
+        return type(self)(v, self.e + o.e + U * v.abs())
 
     def __rsub__(self, o):
-        return Fl.of(o) - self
+        return self.of(o) - self
 
     def __mul__(self, o):
-        o = Fl.of(o)
+        o = self.of(o)
         v = self.v * o.v
-        return Fl(v, self.v.abs() * o.e + o.v.abs() * self.e + self.e * o.e + U * v.abs() + ETA)
+        return type(self)(v, self.v.abs() * o.e + o.v.abs() * self.e + self.e * o.e + U * v.abs() + ETA)
 
     __radd__, __rmul__ = __add__, __mul__
 

@@ -5,6 +5,7 @@ import torch
 
 from gan_variant_research_amd import cut as C
 from gan_variant_research_amd._lib import BF16, F32
+from tests.spectral_ref64 import module_step64 as _ref64          # the float64 statement lives with the spectral-norm family
 
 DEV = "cuda:0"
 pytestmark = pytest.mark.gpu
@@ -35,18 +36,6 @@ def _entries(ops, shapes, seed=0):
                     "v_snap": torch.zeros(w, device=DEV), "G": dev(G), "dW": dev(dW0),
                     "ws": torch.zeros(ops.spectral_norm_batch_ws_floats(h, w), device=DEV), "host": (W, u, v, G, dW0)})
     return out
-
-
-def _ref64(W, u, v, G, power_iter=True, eps=1e-12):
-    """torch.nn.utils.spectral_norm's training-mode step and its weight gradient, in float64."""
-    W, u, v, G = (t.double() for t in (W, u, v, G))
-    if power_iter:
-        v = torch.nn.functional.normalize(W.t() @ u, dim=0, eps=eps)
-        u = torch.nn.functional.normalize(W @ v, dim=0, eps=eps)
-    sigma = torch.dot(u, W @ v)
-    Wr = W.clone().requires_grad_(True)
-    (Wr / torch.dot(u, Wr @ v) * G).sum().backward()        # u, v are constants of the backward
-    return u, v, sigma, Wr.grad
 
 
 def _rel(a, b):
