@@ -13,6 +13,7 @@ LIB_PATH = os.path.join(HERE, "libmi355x_gan.so")
 
 F32, BF16, FP8 = 0, 1, 2     # FP8: OCP e4m3 operand copies of the bottleneck convolutions (BASELINE.json configs[4])
 ACT_NONE, ACT_RELU, ACT_LRELU, ACT_TANH = 0, 1, 2, 3
+TAP_PAD = 1 << 30            # GAN_TAP_PAD: the tapoff entry of a padded tap (zero weights; the generic kernel reads zeros for it)
 HALO_NONE, HALO_ZERO, HALO_REFLECT, HALO_REPLICATE = 0, 1, 2, 3
 RESIZE_BILINEAR, RESIZE_BICUBIC = 2, 3      # Pillow's filter ids (Image.BILINEAR, Image.BICUBIC)
 

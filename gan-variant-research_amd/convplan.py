@@ -13,7 +13,7 @@ from typing import List, Optional, Tuple
 
 import torch
 
-from ._lib import ACT_NONE, BF16, F32, FP8, GanError
+from ._lib import ACT_NONE, BF16, F32, FP8, TAP_PAD, GanError
 from .runtime import IN_WS_CHUNKS, ConvCall, Ctx, View, WgradCall, cpad
 
 
@@ -106,6 +106,7 @@ class _Pack:
         """Picks the kernel for a planned call: range-patch (fragment-major weight copy) if it qualifies, else generic."""
         c.w = None
         if self.ctx.ops.conv_patch_ok(c):
+            assert self.ntaps == len(self.taps)      # Cin % 64 == 0: no padded tap (the range-patch kernel reads every tapoff as a pixel offset)
             c.w, c.w_frag = self.wf, True
             self._patch_tiles(c)
         else:
@@ -119,7 +120,9 @@ class _Pack:
     def tapoff(self, wp: int) -> torch.Tensor:
         t = self._tapoff.get(wp)
         if t is None:
-            t = self.ctx.i32([(dy * wp + dx) * self.cred for dy, dx, _ in self.taps] + [0] * (self.ntaps - len(self.taps)))
+            # padded taps (zero weights, khw = -1) carry the offset TAP_PAD: the generic kernel reads zeros for them, so that a non-finite pixel
+            # is never multiplied by their zero weights (the range-patch and window kernels have no padded tap or do not read the list)
+            t = self.ctx.i32([(dy * wp + dx) * self.cred for dy, dx, _ in self.taps] + [TAP_PAD] * (self.ntaps - len(self.taps)))
             self._tapoff[wp] = t
         return t
 

@@ -97,7 +97,7 @@ template <> __device__ __forceinline__ void st1<float>(float* p, float v) { *p =
 template <> __device__ __forceinline__ void st1<bf16_t>(bf16_t* p, float v) { *p = f2bf(v); }
 
 __device__ __forceinline__ float act_apply(float v, int act) {
-  if (act == GAN_ACT_RELU) return v > 0.f ? v : 0.f;
+  if (act == GAN_ACT_RELU) return v < 0.f ? 0.f : v;      // a NaN passes (torch.relu keeps it): never v > 0 ? v : 0, never fmaxf
   if (act == GAN_ACT_LRELU) return v > 0.f ? v : 0.2f * v;
   if (act == GAN_ACT_TANH) return tanhf(v);
   return v;

@@ -50,6 +50,10 @@ template <> struct Mma<float> {
   }
 };
 
+// what a padded tap reads (convplan pads the tap list to whole K-steps and marks the padded entries with tapoff = GAN_TAP_PAD): zeros, not
+// the pixel at some offset -- their weights are zero, and 0 x Inf or 0 x NaN must not enter a sum the reference does not have them in
+__device__ __attribute__((aligned(16))) const uint32_t zero_chunk[4] = {0u, 0u, 0u, 0u};
+
 __device__ __forceinline__ void glds16(const char* gbase, uint32_t goff, char* lds) {
   __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(gbase + goff),
                                    (__attribute__((address_space(3))) void*)lds, 16, 0, 0);
@@ -123,9 +127,18 @@ __global__ __launch_bounds__(WM* WN * 64) void conv_igemm_kernel(ConvArgs a) {
     char* sa = lds + buf * STAGE;
     char* sb = sa + BM * 128;
     const int kk = ks * BKE + cc * EPC;
-    const uint32_t koff = (uint32_t)(taptab[kk >> a.lgCin] + (kk & (a.Cin - 1))) * (uint32_t)sizeof(T);
+    const int toff = taptab[kk >> a.lgCin];
+    const bool padtap = toff >= GAN_TAP_PAD;      // a padded tap: this lane's chunk of every row is the zero chunk
+    const uint32_t koff = (uint32_t)(toff + (kk & (a.Cin - 1))) * (uint32_t)sizeof(T);
+    // two branches, each with a uniform base (a per-lane base would turn every load's address into 64-bit vector arithmetic); the second is
+    // skipped by every wave none of whose lanes stands on a padded tap -- all K-steps but the last of a layer with padded taps
+    if (!padtap) {
 #pragma unroll
-    for (int i = 0; i < AI; ++i) glds16(a.in, a_row[i] + koff, sa + lds_thr + i * (RSTEP * 128));
+      for (int i = 0; i < AI; ++i) glds16(a.in, a_row[i] + koff, sa + lds_thr + i * (RSTEP * 128));
+    } else {
+#pragma unroll
+      for (int i = 0; i < AI; ++i) glds16(reinterpret_cast<const char*>(zero_chunk), 0u, sa + lds_thr + i * (RSTEP * 128));
+    }
     const uint32_t kb = (uint32_t)(ks * BKE) * (uint32_t)sizeof(T);
 #pragma unroll
     for (int i = 0; i < BI; ++i)
@@ -215,7 +228,7 @@ __global__ __launch_bounds__(WM* WN * 64) void conv_igemm_kernel(ConvArgs a) {
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
               const float t = acc[i][j][e] + bq[j][e];
-              v[e] = ACT == GAN_ACT_RELU ? fmaxf(t, 0.f) : ACT == GAN_ACT_LRELU ? (t > 0.f ? t : 0.2f * t) : ACT == GAN_ACT_TANH ? tanhf(t) : t;
+              v[e] = ACT == GAN_ACT_RELU ? (t < 0.f ? 0.f : t) : ACT == GAN_ACT_LRELU ? (t > 0.f ? t : 0.2f * t) : ACT == GAN_ACT_TANH ? tanhf(t) : t;
             }
             if (mask) {
               const int64_t mb = ((int64_t)(b * a.mask_Hp + ho * a.out_sy + a.mask_y0) * a.mask_Wp + wo * a.out_sx + a.mask_x0) * a.out_C;

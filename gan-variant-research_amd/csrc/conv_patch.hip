@@ -610,7 +610,7 @@ __device__ __forceinline__ void conv_patch_body(const PatchArgs& a) {
             for (int e = 0; e < 4; ++e) {
               const float t = FP8 ? acc[i][j0 + j][e] * oscale + bq[j][e] : acc[i][j0 + j][e] + bq[j][e];
               if constexpr (STATS) { const float tm = mok ? t : 0.f; ssum[4 * j + e] += tm; ssq[4 * j + e] += tm * tm; }
-              v[e] = ACT == GAN_ACT_RELU ? fmaxf(t, 0.f) : ACT == GAN_ACT_LRELU ? (t > 0.f ? t : 0.2f * t) : ACT == GAN_ACT_TANH ? tanhf(t) : t;
+              v[e] = ACT == GAN_ACT_RELU ? (t < 0.f ? 0.f : t) : ACT == GAN_ACT_LRELU ? (t > 0.f ? t : 0.2f * t) : ACT == GAN_ACT_TANH ? tanhf(t) : t;
             }
             if (MASK) {
               const int n = g.n0 + wn * (16 * FJ) + (j0 + j) * 16 + fg * 4;

@@ -28,6 +28,7 @@ extern "C" {
  * copy of a poisoned buffer is poisoned too. */
 enum { GAN_F32 = 0, GAN_BF16 = 1, GAN_FP8 = 2 };
 enum { GAN_ACT_NONE = 0, GAN_ACT_RELU = 1, GAN_ACT_LRELU = 2, GAN_ACT_TANH = 3 };
+#define GAN_TAP_PAD (1 << 30)   /* gan_conv_desc.tapoff entry of a padded tap (see there) */
 /* GAN_HALO_REPLICATE (nn.ReplicationPad2d, generator_resnet_attn.py:26-27,45-46: an option the shipped configs do not use): accepted by
  * gan_nchw_to_view only; its gradient is gan_pad_fold */
 enum { GAN_HALO_NONE = 0, GAN_HALO_ZERO = 1, GAN_HALO_REFLECT = 2, GAN_HALO_REPLICATE = 3 };
@@ -57,7 +58,10 @@ typedef struct gan_conv_desc {
   int32_t Nst;                   /* channels stored (<= out_C, multiple of 4) */
   const void* in;
   int32_t in_Hp, in_Wp, in_y0, in_x0, in_sy, in_sx;
-  const int32_t* tapoff;         /* device [ntaps]: (dy*in_Wp + dx)*Cin */
+  const int32_t* tapoff;         /* device [ntaps]: (dy*in_Wp + dx)*Cin; an entry >= GAN_TAP_PAD (2^30: a multiple of every Cin, beyond any
+                                    real tap) marks a padded tap: the generic kernel reads zeros for it, never a pixel (0 x Inf must
+                                    not enter a sum), so w[n][t][*] MUST be zero for such a t; the host cannot check device entries,
+                                    and only the generic kernel (w_layout 0) accepts them */
   const void* w;
   const float* bias;             /* device fp32 [>= Nst] or NULL */
   void* out;
@@ -126,6 +130,16 @@ typedef struct gan_wgrad_desc {
   int32_t _pad;
 } gan_wgrad_desc;
 
+/* Non-finite data in a gan_conv_igemm launch (tests/conv_cases.py).  A NaN or +-Inf in a real channel of one input pixel reaches the
+ * output pixels of ITS image whose taps read it and no other: every other image, and its partials in `stats`, keep the bits of a clean
+ * run.  Inside that footprint an element is non-finite wherever the float64 statement is, and a NaN stays a NaN through every
+ * activation (ReLU is t < 0 ? 0 : t, as torch.relu: never fmaxf) and through the mask factor; where the statement is finite behind an
+ * Inf (relu(-Inf) = 0, tanh(+-Inf) = +-1) so is the result.  Zero weights never widen the footprint, with ONE exception: a paired-phase
+ * launch (convplan._PairPack: both x-phases of a phase row as one 128-channel launch, for transposed forwards and strided input
+ * gradients with 64 output channels) multiplies the zero weights of one phase by the pixels the other phase reads, so both pixels of a
+ * 128-channel super-pixel are poisoned when one is (a 6x10 input of the 128 -> 64 layer: 12 output pixels for the reference's 9); the
+ * extra pixels are unspecified.  Pad channels (n >= the real Cout) of a poisoned output pixel are unspecified; elsewhere they are 0.
+ * The partial sums of a poisoned (image, channel) are non-finite. */
 const char* gan_last_error(void);
 int gan_version(void);
 

@@ -113,6 +113,12 @@ class EmuOps:
             return False
         if c.mask is not None and c.act != ACT_NONE:
             return False
+        if c.Wo < 2 or c.ntaps < 1:         # one-pixel-wide maps: the kernel's m / Wo by multiplication has no 32-bit magic
+            return False
+        lim = (1 << 32) - 4096              # 32-bit byte offsets into the input, output and mask tensors
+        if (c.B * c.x.Hp * c.x.Wp * c.Cin * 2 >= lim or c.B * c.out.Hp * c.out.Wp * c.out.C * 2 >= lim
+                or (c.mask is not None and c.B * c.mask.Hp * c.mask.Wp * c.out.C * 2 >= lim)):
+            return False
         m_img = c.Ho * c.Wo
         rows = min(256, m_img)
         wraps = (rows - 1) // c.Wo + 1
@@ -220,6 +226,9 @@ class EmuOps:
             ys0 = c.in_y0 + torch.arange(c.Ho) * c.in_sy
             xs0 = c.in_x0 + torch.arange(c.Wo) * c.in_sx
             for t, off in enumerate(toff):
+                if off >= 1 << 30:         # a padded tap (GAN_TAP_PAD): zero weights, and the kernel reads zeros for it (never the pixel at some offset)
+                    assert not w[:, t].any()
+                    continue
                 assert off % Cin == 0
                 dy, dx = (off // Cin) // Wp, (off // Cin) % Wp
                 if not w[:, t].any():
@@ -343,6 +352,8 @@ class EmuOps:
                 q = q.view(Nw // 16, 16, K // 32, 4, 16).permute(0, 2, 3, 1, 4)     # [n16][k32][fg][fr][8 slots x 2 bytes]
                 dst.view(-1).copy_(q.reshape(-1))
                 return
+            if scale is not None:       # bf16 / fp32 copies: a device float the copy is divided by (spectral norm's sigma), one fp32 division
+                out = out / scale.float()
             if layout == 1:
                 K = ntaps * Cin
                 out = out.view(Nw // 16, 16, K // 32, 4, 8).permute(0, 2, 3, 1, 4)

@@ -924,3 +924,48 @@ def body_limit(make, shape, dtype):
     assert bool(((gr > 0) & (gr <= (1 + 2 * U) / math.sqrt(EPS64))).all())
     assert bool(((gr >= lo) & (gr <= hi)).all()), "rstd outside the interval the conditioning contract allows"
     assert ratio(got[..., 0], mean, tm) <= 1.0
+
+
+# ------------------------------------------------------------------------------------------------ non-finite data (apply group)
+def body_nan_plane(make, dtype):
+    """One NaN in x makes the mean and xhat of its (image, channel) NaN: that whole plane of y -- reflect halo included -- is NaN for every
+    activation (ReLU keeps a NaN, as torch.relu does; it never writes 0 over the plane), with and without a residual, through gan_in_apply
+    and gan_in_apply_parts; every other plane is bit-identical to the clean run."""
+    ctx = make()
+    shape = (3, 6, 7, 16, 1)
+    B, H, W, C, p = shape
+    ops = ctx.ops
+    vals = make_x(shape, dtype)
+    bad = vals.clone()
+    bad[1, 1, 2, 5] = float("nan")
+    r = new_view(ctx, shape, dtype, make_g(shape, dtype, 11) * 2.0)
+    plane = torch.zeros(B, H + 2 * p, W + 2 * p, C, dtype=torch.bool)
+    plane[1, :, :, 5] = True
+    planes = 0
+    for act in ACTS_ALL:
+        for with_res in (False, True):
+            for entry in ("apply", "parts"):
+                outs = []
+                for data in (vals, bad):
+                    x = new_view(ctx, shape, dtype, halo=0)
+                    x.nhwc().copy_(data.to(ctx.device))
+                    y = new_view(ctx, shape, dtype, fill=Y_FILL)
+                    st = ctx.f32(B * C * 2, ST_FILL)
+                    if entry == "apply":
+                        ops.in_stats(x, EPS, st, ctx.f32(B * MAXCH * C * 2 + B * C * 2, WS_FILL))()
+                        ops.in_apply(x, st, act, r if with_res else None, y, R.HALO_REFLECT)()
+                    else:
+                        nparts = ops.in_partial_count(x)
+                        parts = ctx.f32(B * nparts * C * 2, ST_FILL)
+                        ops.in_partial(x, parts)()
+                        ops.in_apply_parts(x, parts, nparts, EPS, st, act, r if with_res else None, y, R.HALO_REFLECT)()
+                    sync(ctx)
+                    outs.append(snap(y))
+                clean, got = outs
+                what = f"{entry} act {act} residual {with_res} {NAME[dtype]}"
+                assert bool(torch.isfinite(clean.float()).all()), what
+                assert bool(torch.isnan(got.float())[plane].all()), f"{what}: the plane of the NaN is not NaN everywhere ({int((~torch.isnan(got.float())[plane]).sum())} finite elements)"
+                assert torch.equal(got.view(BITS[dtype])[~plane], clean.view(BITS[dtype])[~plane]), f"{what}: a plane without a NaN differs from the clean run"
+                planes += 1
+    print(f"[norm-family] apply  {NAME[dtype]} NaN plane: {planes} launches, the poisoned plane NaN, all others bit-identical")
+    return planes

@@ -176,3 +176,9 @@ def test_emulated_known_limit(shape, dtype):
 @pytest.mark.parametrize("group,wrong", [(g, w) for g, ws in N.WRONG.items() for w in ws], ids=lambda v: v if isinstance(v, str) else v.__name__)
 def test_emulated_family_rejects_a_wrong_reference(group, wrong):
     N.rejects(make, group, wrong)
+
+
+@pytest.mark.parametrize("dtype", [BF16, F32])
+def test_emulated_nan_plane(dtype):
+    """a NaN in x reaches its whole (image, channel) plane of y through every activation -- ReLU included -- and no other plane"""
+    assert N.body_nan_plane(make, dtype) == 16

@@ -52,3 +52,9 @@ def test_unsupported_widths_return_their_error():
 def test_family_rejects_a_wrong_reference(group, wrong):
     """The kernels' results held to a deliberately wrong reference: every group's assertions fail.  The kernels are never made to misbehave."""
     N.rejects(make, group, wrong)
+
+
+@pytest.mark.parametrize("dtype", [BF16, F32])
+def test_nan_plane(dtype):
+    """a NaN in x reaches its whole (image, channel) plane of y through every activation -- ReLU included -- and no other plane"""
+    assert N.body_nan_plane(make, dtype) == 16
