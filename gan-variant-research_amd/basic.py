@@ -55,6 +55,12 @@ class ResnetGenerator(nn.Module):
         from . import autograd as AG
         return AG.generator_forward(self, x, "basic")
 
+    def forward_u8(self, x):
+        """Forward-only: (B,3,H,W) fp32 in [-1,1] -> (B,H,W,3) uint8 on the device, `inference.to_uint8(forward(x))` turned HWC, bit for
+        bit, through the fused epilogue after the last layer (cut.ResNetGenerator.forward_u8)."""
+        from . import autograd as AG
+        return AG.generator_forward_u8(self, x, "basic")
+
 
 class NLayerDiscriminator(nn.Module):
     """Basic_GAN/src/models.py:71-107: keys net.{0,11}.{weight,bias}, net.{2,5,8}.weight -- with `spectral`, the three middle

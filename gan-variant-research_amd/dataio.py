@@ -16,6 +16,8 @@ glue is restated from its published source).  There is no CPU fallback: without 
 from __future__ import annotations
 
 import ctypes as C
+import os
+from concurrent.futures import ThreadPoolExecutor
 from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -95,6 +97,15 @@ def basic_job(h: int, w: int, load_size: int = 286, crop_size: int = 256, train:
 
 
 # ------------------------------------------------------------------------------------------------ the device pipeline
+def normalize_device(device) -> torch.device:
+    """`torch.device("cuda")` names the current device but compares unequal to the `cuda:0` a tensor on it reports: give an index-less
+    GPU device the current device's index, once, so that devices can be compared."""
+    device = torch.device(device)
+    if device.type == "cuda" and device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    return device
+
+
 class InputPipeline:
     """Batched transform on one GPU.  `run(images, jobs)`: images = uint8 (H, W, 3) device tensors (one per job, any sizes), jobs from
     the `*_job` functions (all with an S x S window) -> (B, 3, S, S) fp32 in [-1, 1].  `filter` is Pillow's resampling filter of every
@@ -106,6 +117,7 @@ class InputPipeline:
         self.S, self.device, self.filter = int(image_size), torch.device(device), int(filter)
         if self.device.type != "cuda":
             raise GanError("the input pipeline runs on the GPU (there is no CPU fallback)")
+        self.device = normalize_device(self.device)       # images report an indexed device: `run` compares against this one
         if self.filter not in (BILINEAR, BICUBIC):
             raise GanError(f"input pipeline: unknown filter {filter} (BILINEAR = {BILINEAR}, BICUBIC = {BICUBIC})")
         self.lib = _lib.load()
@@ -229,3 +241,157 @@ def get_eval_transforms(image_size: int = 256, device="cuda", **kw) -> _Transfor
 def basic_image_tf(load_size: int, crop_size: int, train: bool, device="cuda", **kw) -> _Transform:
     """Basic_GAN/src/data.py:8-26 `_image_tf`."""
     return _Transform(lambda h, w: basic_job(h, w, load_size, crop_size, train), crop_size, device, **kw)
+
+
+# ------------------------------------------------------------------------------------------------ a folder decoded once
+DEFAULT_CACHE_GB = 8            # mi355x.dataset_cache_gb: the Kaggle folders of both reference configs decode to 1.44 GB
+ARENA_ALIGN = 256               # every image starts at a multiple of this, as separate tensors from the caching allocator did
+STAGE_BYTES = 64 << 20          # pinned staging buffer of one upload chunk (two of them, used in turn)
+
+
+def _decode(path) -> np.ndarray:
+    """The reference's decode (`Image.open(p).convert("RGB")`, dataset_unpaired.py / data.py:40) as a writable uint8 (H, W, 3) array."""
+    from PIL import Image
+    try:
+        with Image.open(path) as im:
+            return np.array(im.convert("RGB"))
+    except Exception as e:          # never skipped: the run stops and names the file
+        raise OSError(f"cannot decode image {path}: {e}") from e
+
+
+def _header_size(path) -> Tuple[int, int]:
+    from PIL import Image
+    try:
+        with Image.open(path) as im:
+            w, h = im.size
+    except Exception as e:
+        raise OSError(f"cannot open image {path}: {e}") from e
+    return int(h), int(w)
+
+
+class ImageStore:
+    """The images of `paths`, decoded once with Pillow on a thread pool, as uint8 (H, W, 3) tensors on `device` -- what
+    `InputPipeline.run` reads.  `store[i]` is image i (in the order of `paths`), `store.sizes[i]` its (h, w).
+
+    Resident (the decoded images fit `budget_bytes`; default DEFAULT_CACHE_GB GiB): one uint8 arena holds every image, each at a
+    multiple of 256 bytes (`store.offsets`); it is filled chunk by chunk through two pinned staging buffers with non-blocking copies,
+    and `store[i]` is a view into it.  Streaming (otherwise): nothing is kept; `store[i]` and `store.fetch(indices)` decode (fetch: on
+    the pool) and upload per call.  Both modes hand out the same tensors.  On a CPU device the arena / the fetched images are CPU
+    tensors (the drivers' host logic is tested that way; the pipeline itself has no CPU path).
+    `folder` only names the place in the error an empty list raises."""
+
+    def __init__(self, paths: Sequence, device, budget_bytes: Optional[int] = None, workers: Optional[int] = None, folder=None):
+        self._pool = None
+        self.paths = [os.fspath(p) for p in paths]
+        if not self.paths:
+            raise FileNotFoundError(f"no images found in {os.fspath(folder) if folder is not None else 'the given (empty) list of paths'}")
+        self.device = normalize_device(device)
+        self.workers = max(1, min(16, int(workers) if workers is not None else (os.cpu_count() or 1)))
+        self._pool = ThreadPoolExecutor(self.workers)
+        self._stage = self._stage_event = None
+        try:
+            self.sizes: List[Tuple[int, int]] = list(self._pool.map(_header_size, self.paths))
+            self.offsets, end = [], 0
+            for h, w in self.sizes:
+                self.offsets.append(end)
+                end += -(-(h * w * 3) // ARENA_ALIGN) * ARENA_ALIGN
+            self.nbytes = sum(h * w * 3 for h, w in self.sizes)
+            budget = DEFAULT_CACHE_GB << 30 if budget_bytes is None else int(budget_bytes)
+            self.resident = end <= budget
+            self.arena = None
+            if self.resident:
+                self._fill(end)
+        except BaseException:
+            self.close()
+            raise
+        if self.resident:
+            self.close()              # the pool has done its work; streaming keeps it for `fetch`
+
+    def close(self):
+        if self._pool is not None:
+            self._pool.shutdown(wait=True)
+            self._pool = None
+
+    def __del__(self):
+        self.close()
+
+    def __len__(self) -> int:
+        return len(self.paths)
+
+    def _checked(self, i: int, arr: np.ndarray) -> np.ndarray:
+        if arr.shape != self.sizes[i] + (3,):
+            raise OSError(f"image {self.paths[i]} decoded to {arr.shape[:2]}, its header said {self.sizes[i]}")
+        return arr
+
+    def _view(self, buf: torch.Tensor, off: int, i: int) -> torch.Tensor:
+        h, w = self.sizes[i]
+        return buf[off:off + h * w * 3].view(h, w, 3)
+
+    # ---- resident
+    def _fill(self, total: int):
+        cuda = self.device.type == "cuda"
+        self.arena = torch.empty(total, dtype=torch.uint8, device=self.device)
+        if not cuda:
+            dst = self.arena.numpy()
+
+            def put(i):
+                o, (h, w) = self.offsets[i], self.sizes[i]
+                dst[o:o + h * w * 3] = self._checked(i, _decode(self.paths[i])).reshape(-1)
+            list(self._pool.map(put, range(len(self))))
+            return
+        ends = self.offsets[1:] + [total]
+        cap = max(STAGE_BYTES, max(e - o for o, e in zip(self.offsets, ends)))
+        stages = [torch.empty(min(cap, total), dtype=torch.uint8, pin_memory=True) for _ in range(2)]
+        events = [None, None]
+        first, turn = 0, 0
+        while first < len(self):
+            last = first                      # images first .. last-1 fit one staging buffer
+            while last < len(self) and ends[last] - self.offsets[first] <= stages[0].numel():
+                last += 1
+            base, stage = self.offsets[first], stages[turn]
+            if events[turn] is not None:
+                events[turn].synchronize()    # the copy that last read this staging buffer has run
+            host = stage.numpy()
+
+            def put(i, host=host, base=base):
+                o, (h, w) = self.offsets[i] - base, self.sizes[i]
+                host[o:o + h * w * 3] = self._checked(i, _decode(self.paths[i])).reshape(-1)
+            list(self._pool.map(put, range(first, last)))
+            n = ends[last - 1] - base
+            self.arena[base:base + n].copy_(stage[:n], non_blocking=True)
+            events[turn] = torch.cuda.Event()
+            events[turn].record()
+            first, turn = last, turn ^ 1
+        torch.cuda.current_stream(self.device).synchronize()      # the staging buffers are released below
+
+    # ---- both modes
+    def __getitem__(self, i: int) -> torch.Tensor:
+        i = range(len(self))[i]
+        if self.resident:
+            return self._view(self.arena, self.offsets[i], i)
+        return torch.from_numpy(self._checked(i, _decode(self.paths[i]))).to(self.device)
+
+    def fetch(self, indices: Sequence[int]) -> List[torch.Tensor]:
+        """`[store[i] for i in indices]`; streaming mode decodes them on the pool and uploads them with one copy."""
+        idx = [range(len(self))[i] for i in indices]
+        if self.resident:
+            return [self._view(self.arena, self.offsets[i], i) for i in idx]
+        arrs = [self._checked(i, a) for i, a in zip(idx, self._pool.map(_decode, [self.paths[i] for i in idx]))]
+        if self.device.type != "cuda":
+            return [torch.from_numpy(a) for a in arrs]
+        offs, end = [], 0
+        for a in arrs:
+            offs.append(end)
+            end += -(-a.size // ARENA_ALIGN) * ARENA_ALIGN
+        if self._stage is None or self._stage.numel() < end:
+            self._stage, self._stage_event = torch.empty(max(end, 1 << 20), dtype=torch.uint8, pin_memory=True), None
+        if self._stage_event is not None:
+            self._stage_event.synchronize()
+        host = self._stage.numpy()
+        for o, a in zip(offs, arrs):
+            host[o:o + a.size] = a.reshape(-1)
+        dev = torch.empty(end, dtype=torch.uint8, device=self.device)
+        dev.copy_(self._stage[:end], non_blocking=True)
+        self._stage_event = torch.cuda.Event()
+        self._stage_event.record()
+        return [self._view(dev, o, i) for o, i in zip(offs, idx)]

@@ -6,7 +6,8 @@ Same flags, defaults and messages; the checkpoint is chosen as the reference cho
 the output tree mirrors the input tree as JPEGs (quality 95, 4:4:4).  What differs is what runs underneath: the generator is the HIP
 engine, and on the GPU the resize, the normalisation and the uint8 conversion run there as well (inference.stylize_images).
 Build-only flags: --ngf / --n-blocks (the reference reads the architecture from its own module), --fp32 (bf16 operands stand in for the
-reference's autocast by default), --graph (one hipGraph replay per batch shape), --host-io (resize and convert with PIL / torch on the host).
+reference's autocast by default), --graph (one hipGraph replay per batch shape), --host-io (resize and convert with PIL / torch on the host),
+--which G_A2B|G_B2A (a CycleGAN checkpoint of train_basic is recognised by its keys; this picks the generator, architecture read from the keys).
 """
 from __future__ import annotations
 
@@ -32,6 +33,7 @@ def parse_args(argv=None) -> argparse.Namespace:
     ap.add_argument("--fp32", action="store_true", help="fp32 operands instead of bf16 (build-only flag)")
     ap.add_argument("--graph", action="store_true", help="replay the generator pass as one hipGraph per batch shape (build-only flag)")
     ap.add_argument("--host-io", action="store_true", help="resize / normalise / convert on the host instead of the device (build-only flag)")
+    ap.add_argument("--which", default="G_A2B", choices=["G_A2B", "G_B2A"], help="generator of a CycleGAN checkpoint (train_basic's ckpt_e*.pt) to run (build-only flag)")
     return ap.parse_args(argv)
 
 
@@ -42,7 +44,7 @@ def main(argv=None) -> int:
         args.device = "cpu"
 
     print(f"Loading generator from: {args.ckpt}")
-    G = I.load_generator(args.ckpt, device=args.device, ngf=args.ngf, n_blocks=args.n_blocks, bf16=not args.fp32, use_graph=args.graph)
+    G = I.load_generator(args.ckpt, device=args.device, ngf=args.ngf, n_blocks=args.n_blocks, bf16=not args.fp32, use_graph=args.graph, which=args.which)
     n_params = sum(p.numel() for p in G.parameters())
     print(f"Generator parameters: {n_params:,}")
 

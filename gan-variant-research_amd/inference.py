@@ -39,15 +39,38 @@ def pick_state_dict(ckpt: Dict) -> Dict[str, torch.Tensor]:
     raise KeyError(f"no generator state_dict in checkpoint (keys: {list(ckpt)[:10]})")
 
 
-def load_generator(ckpt_path: str, device: str = "cuda", ngf: int = 64, n_blocks: int = 9, bf16: bool = True, use_graph: bool = False) -> ResNetGenerator:
-    """generate_folder.py:189-205.  The file is read with weights_only=True (tensors and plain containers; nothing is unpickled)."""
+def is_cyclegan_checkpoint(ckpt: Dict) -> bool:
+    """The dict Basic_GAN/src/train.py:127-137 saves (basic.CycleGANTrainer.save_checkpoint): both generators under their names."""
+    return isinstance(ckpt.get("G_A2B"), dict) and isinstance(ckpt.get("G_B2A"), dict)
+
+
+def _basic_generator(sd: Dict[str, torch.Tensor], device):
+    """basic.ResnetGenerator of the architecture the keys tell (models.py:23-65): the residual blocks are net.10 .. net.{9+n}, the
+    first convolution net.1 has ngf output channels.  The state dict is loaded strictly."""
+    from .basic import ResnetGenerator
+    n_blocks = sum(1 for k in sd if k.startswith("net.") and k.endswith(".block.1.weight"))
+    G = ResnetGenerator(3, 3, int(sd["net.1.weight"].shape[0]), n_blocks).to(device)
+    G.load_state_dict(sd, strict=True)
+    return G
+
+
+def load_generator(ckpt_path: str, device: str = "cuda", ngf: int = 64, n_blocks: int = 9, bf16: bool = True, use_graph: bool = False,
+                   which: str = "G_A2B"):
+    """generate_folder.py:189-205.  The file is read with weights_only=True (tensors and plain containers; nothing is unpickled).
+    A CycleGAN checkpoint (keys G_A2B and G_B2A) yields `basic.ResnetGenerator` holding `ckpt[which]`, its width and depth read from the
+    keys (`ngf` / `n_blocks` are not consulted); every other checkpoint yields the CUT `ResNetGenerator` as the reference loads it."""
     ckpt = torch.load(ckpt_path, map_location=device, weights_only=True)
     if not isinstance(ckpt, dict):
         raise ValueError(f"Checkpoint {ckpt_path} is not a dict; got {type(ckpt)}")
-    G = ResNetGenerator(3, 3, ngf, n_blocks).to(device)
-    missing, unexpected = G.load_state_dict(pick_state_dict(ckpt), strict=False)
-    if missing or unexpected:
-        print(f"[WARN] generator state_dict: {len(missing)} missing, {len(unexpected)} unexpected keys (e.g. {(list(missing) + list(unexpected))[:4]})")
+    if is_cyclegan_checkpoint(ckpt):
+        if which not in ("G_A2B", "G_B2A"):
+            raise ValueError(f"which = {which!r}: a CycleGAN checkpoint holds G_A2B and G_B2A")
+        G = _basic_generator(ckpt[which], device)
+    else:
+        G = ResNetGenerator(3, 3, ngf, n_blocks).to(device)
+        missing, unexpected = G.load_state_dict(pick_state_dict(ckpt), strict=False)
+        if missing or unexpected:
+            print(f"[WARN] generator state_dict: {len(missing)} missing, {len(unexpected)} unexpected keys (e.g. {(list(missing) + list(unexpected))[:4]})")
     G.eval()
     for p in G.parameters():
         p.requires_grad_(False)

@@ -5,9 +5,10 @@
 Same flags, same YAML schema (the keys the reference reads; its dead keys are accepted and ignored), same `--set` coercion
 (true/false -> bool, then int, then float, else string), same checkpoint layout and file names, same loss CSV / JSON log lines.
 What differs is what runs underneath: the step is the fused `cut.CutTrainer` on the HIP kernels instead of torch.nn modules.
-Image folders are read with Pillow on the host and transformed on the device (dataio.py, the reference's train transform); when the
-configured folders do not exist -- or with `--synthetic` -- uniform noise batches of the right shape stand in (there is no dataset on
-the benchmark box).  Build-only keys live under `mi355x:` (amp dtype, synthetic data).
+Image folders are decoded once with Pillow at start-up into a `dataio.ImageStore` (resident on the device when they fit
+`mi355x.dataset_cache_gb`, default 8; decoded per batch otherwise) and transformed on the device (dataio.py, the reference's train
+transform); with `--synthetic` uniform noise batches of the right shape stand in (there is no dataset on the benchmark box); folders
+that do not exist are an error.  Build-only keys live under `mi355x:` (amp dtype, synthetic data, dataset_cache_gb).
 """
 from __future__ import annotations
 
@@ -71,25 +72,55 @@ def _list_images(folder) -> List[Path]:
     return sorted(p for p in root.rglob("*") if p.suffix.lower() in IMAGE_EXTS) if root.is_dir() else []
 
 
-def folder_batches(paths: List[Path], batch: int, image_size: int, device, seed: int) -> Iterator[torch.Tensor]:
-    """Shuffled, drop_last epochs over an image folder: Pillow decode on the host, the reference's train transform on the device
-    (dataio.get_train_transforms: random-crop-resize bicubic, flip, ColorJitter, normalise -- transforms.py:10-39)."""
-    from PIL import Image
+def build_store(paths: List[Path], device, config: dict, name: str, folder=None):
+    """One `dataio.ImageStore` per domain, decoded at start-up; `mi355x.dataset_cache_gb` (default 8) is what may stay on the device."""
+    import time
+    from .dataio import DEFAULT_CACHE_GB, ImageStore
+    build = config.get("mi355x", {}) or {}
+    t0 = time.perf_counter()
+    store = ImageStore(paths, device, budget_bytes=int(float(build.get("dataset_cache_gb", DEFAULT_CACHE_GB)) * (1 << 30)), folder=folder)
+    mode = f"resident on {store.device}" if store.resident else "streaming (decoded per batch)"
+    print(f"[data] {name}: {len(store)} images, {store.nbytes / 1e6:.1f} MB decoded, {mode}, {time.perf_counter() - t0:.2f} s")
+    return store
+
+
+def default_transform(image_size: int, device, max_batch: int = 64):
+    """The reference's train transform on the device (dataio.get_train_transforms: random-crop-resize bicubic, flip, ColorJitter,
+    normalise -- transforms.py:10-39)."""
     from .dataio import get_train_transforms
-    tf = get_train_transforms(image_size, device=device)
+    return get_train_transforms(image_size, device=device, max_batch=max_batch)
+
+
+def folder_batches(store, batch: int, tf, seed: int) -> Iterator[torch.Tensor]:
+    """Shuffled, drop_last epochs over an image folder held by a `dataio.ImageStore` (decoded once; on the device when it fits).  `tf`
+    draws one job per image of the batch, in order, and runs the transform (dataio._Transform)."""
     rng = random.Random(seed)
     while True:
-        order = list(paths)
+        order = list(range(len(store)))
         rng.shuffle(order)
         for i in range(0, len(order) - batch + 1, batch):
-            imgs = [torch.from_numpy(np.asarray(Image.open(p).convert("RGB"))) for p in order[i:i + batch]]
-            yield tf(imgs)
+            yield tf(store.fetch(order[i:i + batch]))
 
 
 def synthetic_batches(batch: int, image_size: int, device, seed: int) -> Iterator[torch.Tensor]:
     g = torch.Generator().manual_seed(seed)
     while True:
         yield (torch.rand(batch, 3, image_size, image_size, generator=g) * 2 - 1).to(device)
+
+
+def step_losses(trainer, photos_it, monet_it, start: int, stop: int, overlap: bool):
+    """The steps start .. stop-1, one `(step, loss dict)` at a time, in order.  overlap: step k is queued (sync="lag"), the host
+    prepares batch k+1 while the device runs it, then step k's losses are read (flush_losses) -- so they are checked for NaN and
+    delivered before the caller logs or saves anything of step k, and no batch beyond stop-1 is drawn."""
+    if not overlap:
+        for step in range(start, stop):
+            yield step, trainer.train_step(step, next(photos_it), next(monet_it))
+        return
+    batch = (next(photos_it), next(monet_it)) if start < stop else None
+    for step in range(start, stop):
+        trainer.train_step(step, batch[0], batch[1], sync="lag")
+        batch = (next(photos_it), next(monet_it)) if step + 1 < stop else None
+        yield step, trainer.flush_losses()
 
 
 class LossLog:
@@ -114,8 +145,14 @@ class LossLog:
         self.csv.close()
 
 
-def main(argv=None, ops=None, device: Optional[str] = None) -> dict:
-    """train_cutpp.py:340-498.  `ops` / `device` are test hooks (the CPU suite drives the host logic through the emulator)."""
+def main(argv=None, ops=None, device: Optional[str] = None, transform=None) -> dict:
+    """train_cutpp.py:340-498.  `ops` / `device` / `transform` are test hooks (the CPU suite drives the host logic through the emulator):
+    `transform(image_size, device)` returns the callable that turns a list of decoded uint8 (H, W, 3) images into the (B, 3, S, S) fp32
+    batch (default: `default_transform`, the device pipeline -- on a CPU device it raises that it runs on the GPU).
+
+    With image folders the host prepares batch k+1 while the device runs step k (the step is queued with sync="lag" and its losses are
+    read after the preparation): the rows of the CSV, the summaries and the checkpoints are those of the unoverlapped loop, a NaN step
+    raises before anything later is saved.  --synthetic reads every step's losses before it draws the next batch, as before."""
     args = parse_args(argv)
     with open(args.config) as f:
         config = yaml.safe_load(f)
@@ -141,7 +178,10 @@ def main(argv=None, ops=None, device: Optional[str] = None) -> dict:
         steps_per_epoch = 7038 // B          # the reference's photo count (train_gan_cutpp.yaml: 70 epochs x 7038 // 12 steps)
     else:
         seed = config.get("seed", 42)
-        photos_it, monet_it = folder_batches(photos_paths, B, S, device, seed), folder_batches(monet_paths, B, S, device, seed + 1)
+        make_tf = transform if transform is not None else (lambda size, dev: default_transform(size, dev, max_batch=max(B, 16)))
+        photos = build_store(photos_paths, device, config, "photos", config["data"]["photos_dir"])
+        monets = build_store(monet_paths, device, config, "monet", config["data"]["monet_dir"])
+        photos_it, monet_it = folder_batches(photos, B, make_tf(S, device), seed), folder_batches(monets, B, make_tf(S, device), seed + 1)
         steps_per_epoch = len(photos_paths) // B
         print(f"Photos: {len(photos_paths)}, Monet: {len(monet_paths)}")
 
@@ -157,9 +197,8 @@ def main(argv=None, ops=None, device: Optional[str] = None) -> dict:
     print(f"Training for {max_steps} steps")
 
     acc = defaultdict(list)
-    step, losses = start_step, {}
-    while step < max_steps:
-        losses = trainer.train_step(step, next(photos_it), next(monet_it))
+    losses = {}
+    for step, losses in step_losses(trainer, photos_it, monet_it, start_step, max_steps, overlap=not synthetic):
         for k, v in losses.items():
             acc[k].append(v)
         log.step(step, losses)
@@ -170,7 +209,7 @@ def main(argv=None, ops=None, device: Optional[str] = None) -> dict:
             path = ckpt_dir / f"ckpt_step{step}.pt"
             trainer.save_checkpoint(str(path), step)
             print(f"\nSaved checkpoint to {path}")
-        step += 1
+    step = max(start_step, max_steps)
     final = ckpt_dir / "ckpt_final.pt"
     trainer.save_checkpoint(str(final), step)
     print(f"\nTraining complete. Final checkpoint: {final}")
