@@ -2,7 +2,7 @@
 split covers several whole images: python tools/bench_wgrad8_multi.py [B] [H] [iters].  One launch each per iteration on real (random,
 non-zero) operands; the e4m3 copy of the output gradient carries power-of-two scales (quantize_fp8_pow2) and the call the promise.  Prints
 HIP-event times; under `rocprofv3 --kernel-trace --stats -- python ...` the kernel table gives the per-launch durations of
-wgrad_patch_kernel<false> (bf16, several images per split) and wgrad_patch_fp8_kernel<false, true>."""
+wgrad_patch_kernel<4> (bf16, several images per split) and wgrad_patch_fp8_kernel<false, true>."""
 import os, sys, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from gan_variant_research_amd import BF16, FP8
