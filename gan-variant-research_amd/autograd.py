@@ -19,7 +19,7 @@ import torch
 
 from . import _lib
 from ._lib import F32, BF16, HALO_NONE, HALO_ZERO
-from .nets import DiscriminatorNet, GeneratorNet, generator_keys
+from .nets import DiscriminatorFamilyNet, GeneratorNet, generator_keys
 from .runtime import Ctx, HipOps, Program, View, cpad
 
 # tests replace this with the CPU emulator's constructor; the product always builds HipOps (no CPU fallback)
@@ -330,15 +330,15 @@ class _DiscBridge(_Bridge):
             for k in self.conv_keys:
                 self.grads[k + ".weight"] = torch.zeros_like(self.params[k + ".weight_orig"])     # dL/dW_sn, written by the wgrad kernels
                 self.params[k + ".weight"] = torch.zeros_like(self.params[k + ".weight_orig"])    # shape template for the bridge-level plan
-        self.nets = self._build_nets(self.params)
-        return self.nets[0]
+        return self._family(self.params)
 
-    def _build_nets(self, params):
-        return [DiscriminatorNet(self.ctx, params, self.grads, self.style, p, self.ndf, self.n_layers) for p in self.prefixes]
+    def _family(self, params) -> DiscriminatorFamilyNet:
+        """The family engine over `params`, never with the fused trainers' SpectralNorm: the slots carry their own normalised weights."""
+        return DiscriminatorFamilyNet(self.ctx, params, self.grads, self.style, self.prefixes, self.ndf, self.n_layers)
 
     def _repack_program(self) -> Program:
         prog = Program("D.repack")
-        for net in self.nets:
+        for net in self.net.nets:
             prog.add(net.repack_program())
         return prog
 
@@ -346,7 +346,7 @@ class _DiscBridge(_Bridge):
         """Without spectral norm a slot shares the bridge's networks.  With it, the slot owns W_sn, the operand copies made from
         it and snapshots of u, v, sigma, and two programs (training / eval) that produce them from weight_orig."""
         if not self.sn:
-            s.nets = self.nets
+            s.net = self.net
             return
         ctx, ops = self.ctx, self.ctx.ops
         params = dict(self.params)
@@ -358,7 +358,7 @@ class _DiscBridge(_Bridge):
                   "ws": ctx.f32(ops.spectral_norm_ws_floats(h, w)), "u_buf": self.bufs[k + ".weight_u"], "v_buf": self.bufs[k + ".weight_v"]}
             params[k + ".weight"] = st["Wsn"]
             s.sn_state[k] = st
-        s.nets = self._build_nets(params)
+        s.net = self._family(params)
         s.sn_fwd = {}
         for training in (True, False):
             prog = Program("D.spectral_norm")
@@ -390,34 +390,27 @@ class _DiscBridge(_Bridge):
     def _slot_repack(self, s: _Slot):
         if s.repack is None:
             s.repack = Program("D.repack.slot")
-            for net in s.nets:
+            for net in s.net.nets:
                 s.repack.add(net.repack_program())
         s.repack.run()
 
-    def _passes(self, s: _Slot, B, H, W):
+    def _new_slot(self, B, H, W) -> _Slot:
+        """A slot with its weights, its family pass and the NCHW staging tensor of the input."""
+        s = _Slot()
         self._slot_weights(s)
-        dps = []
-        for net in s.nets:
-            dps.append(net.new_pass(B, H, W))
-            H, W = (H - 1) // 2 + 1, (W - 1) // 2 + 1       # AvgPool2d(3, 2, 1)
-        return dps
+        s.dp = s.net.new_pass(B, H, W)
+        s.xin = torch.zeros(B, self.net.in_c, H, W, dtype=torch.float32, device=self.device)
+        return s
 
     def _make_slot(self, B, H, W):
-        ops, net = self.ctx.ops, self.net
-        s = _Slot()
-        s.dps = self._passes(s, B, H, W)
-        s.xin = torch.zeros(B, net.in_c, H, W, dtype=torch.float32, device=self.device)
+        ops = self.ctx.ops
+        s = self._new_slot(B, H, W)
         s.fwd = Program("D.autograd.fwd")
-        s.fwd.add(ops.nchw_to_view(s.xin, net.in_c, s.dps[0].x, HALO_ZERO))
-        s.outs, s.g_outs = [], []
-        for i, dp in enumerate(s.dps):
-            if i > 0:
-                s.fwd.add(ops.avgpool_fwd(s.dps[i - 1].x, dp.x))
-            s.fwd.add(dp.fwd_program())
-            lg = dp.logits
-            s.outs.append(torch.zeros(B, 1, lg.H, lg.W, dtype=torch.float32, device=self.device))
-            s.fwd.add(ops.view_to_nchw(lg, 1, s.outs[-1]))
-            s.g_outs.append(torch.zeros_like(s.outs[-1]))
+        s.fwd.add(ops.nchw_to_view(s.xin, self.net.in_c, s.dp.x, HALO_ZERO))
+        s.fwd.add(s.dp.fwd_program())
+        s.outs = [torch.zeros(B, 1, lg.H, lg.W, dtype=torch.float32, device=self.device) for lg in s.dp.logits]
+        s.fwd.add([ops.view_to_nchw(lg, 1, out) for lg, out in zip(s.dp.logits, s.outs)])
+        s.g_outs = [torch.zeros_like(out) for out in s.outs]
         s.gx = torch.zeros_like(s.xin)
         return s
 
@@ -443,14 +436,11 @@ class _DiscBridge(_Bridge):
         prog = s.bwd.get(key)
         if prog is None:
             prog = Program("D.autograd.bwd")
-            for dp, g_out in zip(s.dps, s.g_outs):
-                gl = dp.grad_logits_view()
-                prog.add(ops.nchw_to_view(g_out, 1, gl, HALO_ZERO))
-                prog.add(dp.bwd_program(gl, wgrad=need_w, accumulate=False, need_input_grad=need_x))
+            gls = s.dp.grad_logits_views()
+            prog.add([ops.nchw_to_view(g_out, 1, gl, HALO_ZERO) for g_out, gl in zip(s.g_outs, gls)])
+            prog.add(s.dp.bwd_program(gls, wgrad=need_w, accumulate=False, need_input_grad=need_x))
             if need_x:
-                for i in range(len(s.dps) - 2, -1, -1):      # dL/dx_i += pool^T dL/dx_{i+1}
-                    prog.add(ops.avgpool_bwd(s.dps[i + 1].g_input, s.dps[i].g_input, True))
-                prog.add(ops.view_to_nchw(s.dps[0].g_input, self.net.in_c, s.gx))
+                prog.add(ops.view_to_nchw(s.dp.g_input, self.net.in_c, s.gx))
             if need_w and self.sn:
                 prog.add(self._sn_bwd_program(s))
             s.bwd[key] = prog
@@ -528,7 +518,7 @@ def discriminator_forward(module, x: torch.Tensor, style: str, prefix, ndf: int,
 # ------------------------------------------------------------------------------------------------ R1 (double backward)
 class _R1Fn(torch.autograd.Function):
     """r1 = mean_b sum_chw (d sum D(x) / dx)^2 with its parameter gradients computed in the forward (explicit second-order
-    program, DPass.r1_program); backward scales them by the incoming gradient."""
+    program, DFamilyPass.r1_program); backward scales them by the incoming gradient."""
 
     @staticmethod
     def forward(ctx, bridge: _DiscBridge, x, *params):
@@ -539,7 +529,7 @@ class _R1Fn(torch.autograd.Function):
             s.xin.copy_(x)
             s.prog.run()
             loss = s.loss.clone().reshape(())
-            last_biases = [net.convs[-1].grad_b for net in bridge.nets]
+            last_biases = [net.convs[-1].grad_b for net in bridge.net.nets]
             grads = []
             for k in bridge.names:
                 g = bridge.grads[k]
@@ -560,30 +550,14 @@ class _R1Fn(torch.autograd.Function):
 
 
 def _r1_slot(bridge: _DiscBridge, B, H, W) -> _Slot:
-    """With K scales D_total(x) = sum_i sum D_i(P^i x) (P = the average pool), so g = sum_i (P^i)^T g_i and
-    d r1 / d theta_i = <(2/B) P^i g, d g_i / d theta_i>: every scale runs its own first-order half, the input gradients are
-    folded back through the pools into g, and each scale's second-order half is seeded with g pooled down to its resolution."""
-    ctx, ops, net = bridge.ctx, bridge.ctx.ops, bridge.net
-    s = _Slot()
-    s.dps = bridge._passes(s, B, H, W)
-    s.xin = torch.zeros(B, net.in_c, H, W, dtype=torch.float32, device=bridge.device)
+    """The family pass's R1 program with unit scale, then the bridge's own spectral-norm backward from the slot's (u, v, sigma)."""
+    ctx = bridge.ctx
+    s = bridge._new_slot(B, H, W)
     s.loss = ctx.f32(1)
     s.scratch = ctx.f32(1)
     s.prog = Program("R1.autograd")
-    s.prog.add(ops.nchw_to_view(s.xin, net.in_c, s.dps[0].x, HALO_ZERO))
-    for i, dp in enumerate(s.dps):
-        if i > 0:
-            s.prog.add(ops.avgpool_fwd(s.dps[i - 1].x, dp.x))
-        s.prog.add(dp.fwd_program())
-        s.prog.add(dp.r1_first(s.scratch))
-    for i in range(len(s.dps) - 2, -1, -1):
-        s.prog.add(ops.avgpool_bwd(s.dps[i + 1].g_input, s.dps[i].g_input, True))
-    us = [ctx.view(B, dp.H, dp.W, dp.x.C, 1) for dp in s.dps]
-    s.prog.add(ops.r1_reduce(s.dps[0].g_input, net.in_c, 1.0, s.loss, us[0], ctx.scratch("r1_ws", 1024)))
-    for i, dp in enumerate(s.dps):
-        if i > 0:
-            s.prog.add(ops.avgpool_fwd(us[i - 1], us[i]))
-        s.prog.add(dp.r1_second(us[i]))
+    s.prog.add(ctx.ops.nchw_to_view(s.xin, bridge.net.in_c, s.dp.x, HALO_ZERO))
+    s.prog.add(s.dp.r1_program(1.0, s.loss, s.scratch))
     if bridge.sn:
         s.prog.add(bridge._sn_bwd_program(s))
     return s

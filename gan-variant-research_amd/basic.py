@@ -13,7 +13,7 @@ import torch.nn as nn
 
 from ._lib import BF16, F32, HALO_ZERO
 from .cut import FusedAdam, _adam_state_dict, _load_adam_state_dict
-from .nets import DiscriminatorNet, GeneratorNet, PartialSNDiscriminatorNet, SpectralNorm, fp8_switches
+from .nets import DiscriminatorFamilyNet, GeneratorNet, SpectralNorm, fp8_switches
 from .runtime import Ctx, HipOps, Program, View
 
 
@@ -185,16 +185,12 @@ class CycleGANTrainer:
             net.repack_program().run()
 
     def _d_net(self, D, opt, buffers):
-        """The discriminator's engine: DiscriminatorNet, or with spectral norm the one whose net.2 / net.5 / net.8 are normalised."""
-        if not getattr(D, "spectral", False):
-            return DiscriminatorNet(self.ctx, opt.params, opt.grads, "basic", ndf=D.ndf, n_layers=D.n_layers), None
-        keys = [k[:-len(".weight_orig")] for k in opt.names if k.endswith(".weight_orig")]
-        sn = SpectralNorm(self.ctx, keys, opt.params, opt.grads, buffers)
-        return PartialSNDiscriminatorNet(self.ctx, opt.params, opt.grads, sn, "basic", ndf=D.ndf, n_layers=D.n_layers), sn
-
-    def _d_fwd(self, net, dp) -> Program:
-        """A discriminator forward: with spectral norm the power iteration and the pack of the normalised layers' copies come first."""
-        return net.fwd_program(dp) if isinstance(net, PartialSNDiscriminatorNet) else dp.fwd_program()
+        """The discriminator's engine and, with spectral norm, the (u, v, sigma) of net.2 / net.5 / net.8."""
+        sn = None
+        if getattr(D, "spectral", False):
+            keys = [k[:-len(".weight_orig")] for k in opt.names if k.endswith(".weight_orig")]
+            sn = SpectralNorm(self.ctx, keys, opt.params, opt.grads, buffers)
+        return DiscriminatorFamilyNet(self.ctx, opt.params, opt.grads, "basic", [""], D.ndf, D.n_layers, sn=sn), sn
 
     def _slot(self, name):
         i = SLOTS[name]
@@ -217,18 +213,18 @@ class CycleGANTrainer:
         fwd.add(P["ab_b"].fwd_program(self.real_b)); fwd.add(P["ba_a"].fwd_program(self.real_a))
         self.db_fake, self.da_fake = self.DB.new_pass(B, S, S), self.DA.new_pass(B, S, S)
         self.db_real, self.da_real = self.DB.new_pass(B, S, S), self.DA.new_pass(B, S, S)
-        fwd.add(ops.view_copy(P["ab_a"].img, self.db_fake.x, HALO_ZERO)); fwd.add(self._d_fwd(self.DB, self.db_fake))
-        fwd.add(ops.view_copy(P["ba_b"].img, self.da_fake.x, HALO_ZERO)); fwd.add(self._d_fwd(self.DA, self.da_fake))
+        fwd.add(ops.view_copy(P["ab_a"].img, self.db_fake.x, HALO_ZERO)); fwd.add(self.db_fake.fwd_program())
+        fwd.add(ops.view_copy(P["ba_b"].img, self.da_fake.x, HALO_ZERO)); fwd.add(self.da_fake.fwd_program())
         self.P = P
 
         bwd = Program("G-bwd")
         gv = lambda: ctx.view(B, S, S, 8, 0)
         # adversarial terms: generators want D(fake) = real
-        gl_b, gl_a = self.db_fake.grad_logits_view(), self.da_fake.grad_logits_view()
-        bwd.add(ops.patch_loss(self.db_fake.logits, mode, 1.0, 1.0, self._slot("gan_b"), gl_b))
+        gl_b, gl_a = self.db_fake.grad_logits_views(), self.da_fake.grad_logits_views()      # one scale: lists of one
+        bwd.add(ops.patch_loss(self.db_fake.logits[0], mode, 1.0, 1.0, self._slot("gan_b"), gl_b[0]))
         bwd.add(self.db_fake.bwd_program(gl_b, wgrad=False, need_input_grad=True))
         g_adv_b = self.db_fake.g_input      # scratch of D_B: untouched until D_B's own step
-        bwd.add(ops.patch_loss(self.da_fake.logits, mode, 1.0, 1.0, self._slot("gan_a"), gl_a))
+        bwd.add(ops.patch_loss(self.da_fake.logits[0], mode, 1.0, 1.0, self._slot("gan_a"), gl_a[0]))
         bwd.add(self.da_fake.bwd_program(gl_a, wgrad=False, need_input_grad=True))
         g_adv_a = self.da_fake.g_input
         # cycle terms -> gradient wrt the fakes through the second generator
@@ -254,25 +250,17 @@ class CycleGANTrainer:
         def d_step(net, real_src, p_real, p_fake, s_real, s_fake, fake_img):
             prog = Program("D-step")
             prog.add(ops.nchw_to_view(real_src, 3, p_real.x, HALO_ZERO))
-            if isinstance(net, PartialSNDiscriminatorNet):
-                # spectral norm: each forward runs its own power iteration and each backward reads the snapshots of its own forward,
-                # so real forward -> backward -> spectral-norm backward, then the fake pass forwarded again from the G-step's output
-                prog.add(net.fwd_program(p_real))
-                gl = p_real.grad_logits_view()
-                prog.add(ops.patch_loss(p_real.logits, mode, 1.0, 0.5, self._slot(s_real), gl))
-                prog.add(net.wgrad_program(p_real, gl, accumulate=False))
-                prog.add(ops.view_copy(fake_img, p_fake.x, HALO_ZERO))
-                prog.add(net.fwd_program(p_fake))
-                gl2 = p_fake.grad_logits_view()
-                prog.add(ops.patch_loss(p_fake.logits, mode, 0.0, 0.5, self._slot(s_fake), gl2))
-                prog.add(net.wgrad_program(p_fake, gl2, accumulate=True))
-                return prog
             prog.add(p_real.fwd_program())
-            gl = p_real.grad_logits_view()
-            prog.add(ops.patch_loss(p_real.logits, mode, 1.0, 0.5, self._slot(s_real), gl))
+            gl = p_real.grad_logits_views()
+            prog.add(ops.patch_loss(p_real.logits[0], mode, 1.0, 0.5, self._slot(s_real), gl[0]))
             prog.add(p_real.bwd_program(gl, wgrad=True, accumulate=False))
-            gl2 = p_fake.grad_logits_view()
-            prog.add(ops.patch_loss(p_fake.logits, mode, 0.0, 0.5, self._slot(s_fake), gl2))
+            if net.sn is not None:
+                # spectral norm: each forward runs its own power iteration and each backward reads the snapshots of its own forward,
+                # so the fake pass is forwarded again from the G-step's output, after the real half's spectral-norm backward
+                prog.add(ops.view_copy(fake_img, p_fake.x, HALO_ZERO))
+                prog.add(p_fake.fwd_program())
+            gl2 = p_fake.grad_logits_views()
+            prog.add(ops.patch_loss(p_fake.logits[0], mode, 0.0, 0.5, self._slot(s_fake), gl2[0]))
             prog.add(p_fake.bwd_program(gl2, wgrad=True, accumulate=True))
             return prog
         self.prog_da = d_step(self.DA, self.real_a, self.da_real, self.da_fake, "da_real", "da_fake", P["ba_b"].img)
@@ -282,8 +270,7 @@ class CycleGANTrainer:
         self.upd_da = Program("DA-update"); self.upd_da.add(self.opt_DA.step_op(None, gs)); self.upd_da.add(self.DA.repack_program())
         self.upd_db = Program("DB-update"); self.upd_db.add(self.opt_DB.step_op(None, gs)); self.upd_db.add(self.DB.repack_program())
         for net in (self.DA, self.DB):
-            if isinstance(net, PartialSNDiscriminatorNet):
-                net.refresh_pack()          # the pack each forward runs covers every operand copy planned above
+            net.refresh_pack()              # spectral norm: the pack each forward runs covers every operand copy planned above
 
     # ---- epoch end (Basic_GAN/src/train.py:124-137): LambdaLR x 3, then the checkpoint dict
     def scheduler_step(self) -> float:

@@ -20,7 +20,7 @@ import torch
 import torch.nn as nn
 
 from ._lib import ACT_NONE, BF16, F32, HALO_NONE, HALO_ZERO
-from .nets import GeneratorNet, MultiscaleDiscriminatorNet, SpectralNorm, fp8_switches
+from .nets import DiscriminatorFamilyNet, GeneratorNet, SpectralNorm, fp8_switches
 from .runtime import ADAM_CHUNK, Ctx, HipOps, Program, View, cpad
 
 NCE_LAYERS_DEFAULT = (0, 4, 8, 12, 16)
@@ -206,7 +206,7 @@ class _PatchGANParams(nn.Module):
 
 class MultiscaleDiscriminator(nn.Module):
     """Signature and defaults of models/discriminator_patchgan.py:81-88.  The fused CutTrainer runs every scale count with or without
-    spectral norm (nets.MultiscaleDiscriminatorNet); forward() is the module API (autograd.py)."""
+    spectral norm (nets.DiscriminatorFamilyNet); forward() is the module API (autograd.py)."""
 
     def __init__(self, input_nc=3, ndf=64, n_layers=3, num_scales=3, use_spectral_norm=True):
         super().__init__()
@@ -488,9 +488,10 @@ class CutTrainer:
         if self.spectral_norm:
             keys = [k[:-len(".weight_orig")] for k in self.opt_D.names if k.endswith(".weight_orig")]
             self.sn = SpectralNorm(self.ctxD, keys, self.opt_D.params, self.opt_D.grads, self.d_buffers)
-        self.D = MultiscaleDiscriminatorNet(self.ctxD, self.opt_D.params, self.opt_D.grads, discriminator.ndf, discriminator.n_layers, K, self.sn)
-        self.D32 = self.D if self.ctx32 is self.ctxD else MultiscaleDiscriminatorNet(self.ctx32, self.opt_D.params, self.opt_D.grads,
-                                                                                    discriminator.ndf, discriminator.n_layers, K, self.sn)
+        d_net = lambda ctx: DiscriminatorFamilyNet(ctx, self.opt_D.params, self.opt_D.grads, "cut", [f"discriminators.{s}.model." for s in range(K)],
+                                                   discriminator.ndf, discriminator.n_layers, sn=self.sn)
+        self.D = d_net(self.ctxD)
+        self.D32 = self.D if self.ctx32 is self.ctxD else d_net(self.ctx32)
         self.nce_layers = feature_layers_present(config["patchnce"]["nce_layers"], nb) if lw["patchnce"] > 0 else []
         self.P = config["patchnce"]["num_patches"]
         # Identity warm-up (identity weight > 0): G(photos) and G(monets) are two full passes through the same weights, and

@@ -498,22 +498,9 @@ class DPass:
             xin = self.acts[li]
         return prog
 
-    def r1_program(self, scale: float, loss: torch.Tensor, scratch: torch.Tensor) -> Program:
-        """R1 penalty (train_cutpp.py:165-203) after this pass's forward: *loss = mean_b sum_chw (d sum D(x) / dx)^2 and the
-        weight gradients of scale * r1, as an explicit second-order program (no autograd graph):
-        first-order input gradient with the LeakyReLU masks fused in the dgrad epilogues (delta_i kept per layer), then the
-        linearised forward u_i = mask_i * (W_i * u_{i-1}) seeded with u_0 = scale * 2 g / B, with dW_i = wgrad(u_{i-1}, delta_i).
-        Bias gradients are zero except the last bias, whose gradient is None in the reference (the caller skips it)."""
-        ctx, ops = self.net.ctx, self.net.ctx.ops
-        pr = Program("R1")
-        pr.add(self.r1_first(scratch))
-        u = ctx.view(self.B, self.H, self.W, self.x.C, 1)
-        pr.add(ops.r1_reduce(self.g_input, self.net.in_c, scale, loss, u, ctx.scratch("r1_ws", 1024)))
-        pr.add(self.r1_second(u))
-        return pr
-
     def r1_first(self, scratch: torch.Tensor) -> Program:
-        """First-order half of R1: g = d sum D(x) / dx into self.g_input, the per-layer output gradients kept for r1_second."""
+        """First-order half of R1 (DFamilyPass.r1_program) after this pass's forward: g = d sum D(x) / dx into self.g_input with the LeakyReLU
+        masks fused in the dgrad epilogues, the per-layer output gradients (delta_i) kept for r1_second."""
         net, ops, B = self.net, self.net.ctx.ops, self.B
         assert net.style == "cut", "R1 is part of the CUT trainer (no norm layers in its discriminator)"
         pr = Program("R1.first")
@@ -525,8 +512,9 @@ class DPass:
         return pr
 
     def r1_second(self, u: View) -> Program:
-        """Second-order half: the weight gradients of <u_0, g(theta)> by the linearised forward from u_0 = `u` (zero halo 1).
-        With several scales u_0 is the pooled total input gradient, not this scale's own (autograd.py, _r1_slot)."""
+        """Second-order half: the weight gradients of <u_0, g(theta)> by the linearised forward u_i = mask_i * (W_i * u_{i-1}) from
+        u_0 = `u` (zero halo 1), with dW_i = wgrad(u_{i-1}, delta_i).  Bias gradients are zero except the last bias, whose gradient is None
+        in the reference (the caller skips it)."""
         net, ctx, B = self.net, self.net.ctx, self.B
         pr = Program("R1.second")
         deltas = self._r1_deltas
@@ -547,11 +535,10 @@ class DPass:
         return self.net.gbuf("g_logits", self.B, lg.H, lg.W, lg.C, 2)
 
     def bwd_program(self, g_logits: View, wgrad: bool = True, accumulate: bool = False, need_input_grad: bool = False,
-                    keep: Optional[list] = None, bias_grads: bool = True, bias_accumulate: Optional[bool] = None,
-                    write_only: Sequence[int] = ()) -> Program:
+                    keep: Optional[list] = None, write_only: Sequence[int] = ()) -> Program:
         """Backward from dL/dlogits.  keep: if a list, the per-layer output gradients (delta_i) are appended to it and
-        live in dedicated buffers (R1's second-order pass needs them).  bias_accumulate: for the bias gradients (default: accumulate).
-        write_only: indices of convolutions whose weight gradient is written even when `accumulate` (spectral norm's dL/dW_sn scratch)."""
+        live in dedicated buffers (R1's second-order pass needs them).  write_only: indices of convolutions whose weight gradient is
+        written even when `accumulate` (spectral norm's dL/dW_sn scratch); their bias gradients still follow `accumulate`."""
         net, ops, B = self.net, self.net.ctx.ops, self.B
         prog = Program("D.bwd")
         dy = g_logits
@@ -565,9 +552,10 @@ class DPass:
             if keep is not None:
                 keep.append(dy)
             if wgrad:
-                ba = accumulate if (bias_accumulate is None and li in write_only) else bias_accumulate
-                kw = {} if ba is None else {"bias_accumulate": ba}
-                prog.add(conv.wgrad(xin, dy, accumulate and li not in write_only, bias_too=bias_grads, **kw))
+                if li in write_only:
+                    prog.add(conv.wgrad(xin, dy, False, bias_accumulate=accumulate))
+                else:
+                    prog.add(conv.wgrad(xin, dy, accumulate))
             if li == 0:
                 if need_input_grad:
                     self.g_input = net.gbuf("g_dx", B, self.H, self.W, self.x.C, 0)
@@ -625,112 +613,60 @@ class SpectralNorm:
         return self._bwd[bool(accumulate)]
 
 
-class PartialSNDiscriminatorNet:
-    """A DiscriminatorNet with spectral norm on some of its convolutions only: Basic_GAN's NLayerDiscriminator(spectral=True)
-    (Basic_GAN/src/models.py:67-101) normalises the bias-free middle convolutions net.2 / net.5 / net.8 (`sn.keys`) and leaves net.0 and
-    net.11 plain.  The spectral-norm convolutions read weight_orig packed with scale sigma and write dL/dW_sn into `sn.G`; a forward is
-    one power iteration, the pack of their operand copies, then the layers; the repack after an optimiser step covers the plain ones."""
 
-    def __init__(self, ctx: Ctx, params: Dict[str, torch.Tensor], grads: Dict[str, torch.Tensor], sn: SpectralNorm, style="basic",
-                 ndf=64, n_layers=3, in_c=3):
-        self.ctx, self.sn = ctx, sn
-        params, grads = dict(params), dict(grads)
-        for k in sn.keys:
-            params[k + ".weight"], grads[k + ".weight"] = params[k + ".weight_orig"], sn.G[k]
-        self.net = DiscriminatorNet(ctx, params, grads, style, ndf=ndf, n_layers=n_layers, in_c=in_c)
-        self.sn_layers = [i for i, k in enumerate(self.net.keys) if k in sn.keys]
-        assert len(self.sn_layers) == len(sn.keys), (self.net.keys, sn.keys)
-        for i in self.sn_layers:
-            self.net.convs[i].pack_scale = sn.sigma[self.net.keys[i]]
+
+class DiscriminatorFamilyNet:
+    """The discriminator family of both trainers and of the module API: one PatchGAN net per key prefix, scale s on the input
+    average-pooled s times -- MultiscaleDiscriminator's `num_scales` CUT nets (discriminator_patchgan.py:75-116, prefixes
+    discriminators.{s}.model.) or Basic_GAN's single NLayerDiscriminator (Basic_GAN/src/models.py:67-101, one prefix).  A convolution is
+    spectral-normalised exactly when its key is in `sn.keys`: all of them in the CUT family, the bias-free middle ones (net.2 / net.5 /
+    net.8) in Basic_GAN's.  Those read weight_orig packed with scale sigma and write dL/dW_sn into `sn.G`; every forward packs their operand
+    copies itself after its power iteration, the repack after an optimiser step covers the plain ones.  With one scale and no spectral norm
+    every program is the single DiscriminatorNet's."""
+
+    def __init__(self, ctx: Ctx, params: Dict[str, torch.Tensor], grads: Dict[str, torch.Tensor], style: str, prefixes: Sequence[str],
+                 ndf=64, n_layers=3, in_c=3, sn: Optional[SpectralNorm] = None):
+        self.ctx, self.sn, self.in_c = ctx, sn, in_c
+        sn_keys = sn.keys if sn is not None else []
+        if sn_keys:
+            params, grads = dict(params), dict(grads)
+            for k in sn_keys:
+                params[k + ".weight"], grads[k + ".weight"] = params[k + ".weight_orig"], sn.G[k]
+        self.nets = [DiscriminatorNet(ctx, params, grads, style, p, ndf, n_layers, in_c) for p in prefixes]
+        self.nconv = self.nets[0].nconv
+        self.sn_layers = [[i for i, k in enumerate(net.keys) if k in sn_keys] for net in self.nets]      # per scale
+        assert sum(len(idx) for idx in self.sn_layers) == len(sn_keys), ([net.keys for net in self.nets], sn_keys)
+        for net, idx in zip(self.nets, self.sn_layers):
+            for i in idx:
+                net.convs[i].pack_scale = sn.sigma[net.keys[i]]
         self._pack = None
 
     def _copies(self, spectral: bool):
-        return [op.pack_args for i, c in enumerate(self.net.convs) if (i in self.sn_layers) == spectral for op in c.repack_ops()]
+        return [op.pack_args for net, idx in zip(self.nets, self.sn_layers) for i, conv in enumerate(net.convs) if (i in idx) == spectral
+                for op in conv.repack_ops()]
 
     def repack_program(self) -> Program:
-        """Operand copies of the plain convolutions after an optimiser step: one batched launch."""
+        """Operand copies of the plain convolutions after an optimiser step: one batched launch (none when every convolution is
+        normalised: those copies depend on the sigma of the next forward, which packs them itself)."""
         prog = Program("repack")
-        prog.add(self.ctx.ops.pack_weight_batch(self._copies(False)))
+        copies = self._copies(False)
+        if copies:
+            prog.add(self.ctx.ops.pack_weight_batch(copies))
         return prog
 
     def refresh_pack(self):
-        """(Re)builds the forward's pack launch over the spectral-norm convolutions' copies planned so far; call after planning passes."""
-        self._pack = self.ctx.ops.pack_weight_batch(self._copies(True))
-
-    def new_pass(self, B, H, W) -> "DPass":
-        return self.net.new_pass(B, H, W)
-
-    def fwd_program(self, dp: "DPass") -> Program:
-        prog = Program("PSND.fwd")
-        prog.add(self.sn.fwd_op())
-        prog.add(lambda: self._pack())
-        prog.add(dp.fwd_program())
-        return prog
-
-    def wgrad_program(self, dp: "DPass", g_logits: View, accumulate: bool) -> Program:
-        """Weight gradients of pass `dp`: the plain layers' written or added, dL/dW_sn written to the scratch, then one batched
-        spectral-norm backward that writes / adds dL/dweight_orig (it reads the snapshots of dp's own forward: run it before the next)."""
-        prog = Program("PSND.bwd")
-        prog.add(dp.bwd_program(g_logits, wgrad=True, accumulate=accumulate, write_only=self.sn_layers))
-        prog.add(self.sn.bwd_op(accumulate))
-        return prog
-
-
-class MultiscaleDiscriminatorNet:
-    """MultiscaleDiscriminator (discriminator_patchgan.py:75-116): `num_scales` CUT PatchGAN nets (keys discriminators.{s}.model.{2i}),
-    scale s on the input average-pooled s times, optionally spectral-normalised (`sn`).  With one scale and no spectral norm every
-    program is the single DiscriminatorNet's."""
-
-    def __init__(self, ctx: Ctx, params: Dict[str, torch.Tensor], grads: Dict[str, torch.Tensor], ndf=64, n_layers=3, num_scales=1,
-                 sn: Optional[SpectralNorm] = None, in_c=3):
-        self.ctx, self.sn, self.num_scales, self.in_c = ctx, sn, num_scales, in_c
-        if sn is not None:         # the convolutions read weight_orig (packed / sigma) and write dL/dW_sn into the scratch
-            params, grads = dict(params), dict(grads)
-            for k in sn.keys:
-                params[k + ".weight"], grads[k + ".weight"] = params[k + ".weight_orig"], sn.G[k]
-        self.nets = [DiscriminatorNet(ctx, params, grads, "cut", f"discriminators.{s}.model.", ndf, n_layers, in_c) for s in range(num_scales)]
-        self.nconv = self.nets[0].nconv
-        if sn is not None:
-            for s, net in enumerate(self.nets):
-                for i, conv in enumerate(net.convs):
-                    conv.pack_scale = sn.sigma[f"discriminators.{s}.model.{2 * i}"]
-        self._pack = None
-
-    @property
-    def convs(self) -> List[ConvLayer]:
-        return [c for net in self.nets for c in net.convs]
-
-    def _pack_all(self):
-        ops = [op for net in self.nets for layer in net.layers for op in layer.repack_ops()]
-        return self.ctx.ops.pack_weight_batch([op.pack_args for op in ops])
-
-    def repack_program(self) -> Program:
-        """Operand copies after an optimiser step: one batched launch.  A spectral-norm network has none here: its copies depend on the
-        sigma of the next forward, which packs them itself (pack_op)."""
+        """(Re)builds the pack every forward runs over the normalised convolutions' copies planned so far; call after planning passes."""
         if self.sn is not None:
-            return Program("repack")
-        if len(self.nets) == 1:
-            return self.nets[0].repack_program()
-        prog = Program("repack")
-        prog.add(self._pack_all())
-        return prog
+            self._pack = self.ctx.ops.pack_weight_batch(self._copies(True))
 
-    def refresh_pack(self):
-        """(Re)builds the forward's pack launch over every operand copy planned so far; call after planning new passes."""
-        if self.sn is not None:
-            self._pack = self._pack_all()
-
-    def pack_op(self):
-        return lambda: self._pack()
-
-    def new_pass(self, B, H, W) -> "MSDPass":
-        return MSDPass(self, B, H, W)
+    def new_pass(self, B, H, W) -> "DFamilyPass":
+        return DFamilyPass(self, B, H, W)
 
 
-class MSDPass:
-    """Buffers of one multiscale discriminator forward (+ backward): one DPass per scale."""
+class DFamilyPass:
+    """Buffers of one forward (+ backward) of the family: one DPass per scale."""
 
-    def __init__(self, net: MultiscaleDiscriminatorNet, B, H, W):
+    def __init__(self, net: DiscriminatorFamilyNet, B, H, W):
         self.net, self.B, self.H, self.W = net, B, H, W
         self.dps = []
         for n in net.nets:
@@ -741,13 +677,13 @@ class MSDPass:
         self.g_input = None
 
     def fwd_program(self) -> Program:
-        """With spectral norm: one power iteration over every scale's convolutions, the pack of this network's operand copies with
+        """With spectral norm: one power iteration over every normalised convolution, the pack of their operand copies with
         scale = sigma, then the scales."""
-        ops = self.net.ctx.ops
-        prog = Program("MSD.fwd")
-        if self.net.sn is not None:
-            prog.add(self.net.sn.fwd_op())
-            prog.add(self.net.pack_op())
+        net, ops = self.net, self.net.ctx.ops
+        prog = Program("D.family.fwd")
+        if net.sn is not None:
+            prog.add(net.sn.fwd_op())
+            prog.add(lambda: net._pack())
         for s, dp in enumerate(self.dps):
             if s > 0:
                 prog.add(ops.avgpool_fwd(self.dps[s - 1].x, dp.x))
@@ -757,41 +693,39 @@ class MSDPass:
     def grad_logits_views(self) -> List[View]:
         return [dp.grad_logits_view() for dp in self.dps]
 
+    def _pool_input_grads(self) -> list:
+        """dL/dx_i += pool^T dL/dx_{i+1}, down to scale 0."""
+        ops = self.net.ctx.ops
+        return [ops.avgpool_bwd(self.dps[i + 1].g_input, self.dps[i].g_input, True) for i in range(len(self.dps) - 2, -1, -1)]
+
     def bwd_program(self, g_logits: Sequence[View], wgrad: bool = True, accumulate: bool = False, need_input_grad: bool = False) -> Program:
-        """Per-scale backward; input gradients summed down to scale 0 through the pools (self.g_input).  With spectral norm the
-        weight gradients (dL/dW_sn) overwrite the scratch and one batched backward adds / writes dL/dweight_orig; the biases
-        take theirs directly."""
-        ops, sn = self.net.ctx.ops, self.net.sn
-        prog = Program("MSD.bwd")
-        for dp, gl in zip(self.dps, g_logits):
-            if sn is None:
-                prog.add(dp.bwd_program(gl, wgrad=wgrad, accumulate=accumulate, need_input_grad=need_input_grad))
-            else:
-                prog.add(dp.bwd_program(gl, wgrad=wgrad, accumulate=False, need_input_grad=need_input_grad, bias_accumulate=accumulate))
+        """Per-scale backward; input gradients summed down to scale 0 through the pools (self.g_input).  The normalised convolutions'
+        weight gradients (dL/dW_sn) overwrite the scratch and one batched spectral-norm backward adds / writes dL/dweight_orig (it reads
+        the snapshots of this pass's own forward: run it before the next); biases and plain weights take theirs directly."""
+        sn = self.net.sn
+        prog = Program("D.family.bwd")
+        for dp, gl, idx in zip(self.dps, g_logits, self.net.sn_layers):
+            prog.add(dp.bwd_program(gl, wgrad=wgrad, accumulate=accumulate, need_input_grad=need_input_grad, write_only=idx))
         if need_input_grad:
-            for i in range(len(self.dps) - 2, -1, -1):      # dL/dx_i += pool^T dL/dx_{i+1}
-                prog.add(ops.avgpool_bwd(self.dps[i + 1].g_input, self.dps[i].g_input, True))
+            prog.add(self._pool_input_grads())
             self.g_input = self.dps[0].g_input
         if wgrad and sn is not None:
             prog.add(sn.bwd_op(accumulate))
         return prog
 
     def r1_program(self, scale: float, loss: torch.Tensor, scratch: torch.Tensor) -> Program:
-        """R1 over every scale after this pass's input is in place (autograd.py, _r1_slot): the forward (with its power iteration
-        and pack), the first-order half at every scale, the input gradients pooled back to scale 0 and reduced, then each scale's
-        second-order half seeded with the total u_0 pooled down to its resolution; with spectral norm one batched backward."""
+        """R1 penalty (train_cutpp.py:165-203) once this pass's input is in place: *loss = mean_b sum_chw (d sum D(x) / dx)^2 and the weight
+        gradients of scale * r1, as an explicit second-order program (no autograd graph).  With K scales D_total(x) = sum_i sum D_i(P^i x)
+        (P = the average pool), so g = sum_i (P^i)^T g_i and d r1 / d theta_i = <(2 / B) P^i g, d g_i / d theta_i>: the forward (with its
+        power iteration and pack), every scale's first-order half, the input gradients folded back through the pools into g and reduced
+        (u_0 = scale * 2 g / B), then each scale's second-order half seeded with u_0 pooled down to its resolution; with spectral norm one
+        batched backward."""
         net, ctx, ops = self.net, self.net.ctx, self.net.ctx.ops
-        if len(self.dps) == 1 and net.sn is None:
-            pr = Program("R1")
-            pr.add(self.dps[0].fwd_program())
-            pr.add(self.dps[0].r1_program(scale, loss, scratch))
-            return pr
-        pr = Program("R1.multiscale")
+        pr = Program("R1")
         pr.add(self.fwd_program())
         for dp in self.dps:
             pr.add(dp.r1_first(scratch))
-        for i in range(len(self.dps) - 2, -1, -1):
-            pr.add(ops.avgpool_bwd(self.dps[i + 1].g_input, self.dps[i].g_input, True))
+        pr.add(self._pool_input_grads())
         us = [ctx.view(self.B, dp.H, dp.W, dp.x.C, 1) for dp in self.dps]
         pr.add(ops.r1_reduce(self.dps[0].g_input, net.in_c, scale, loss, us[0], ctx.scratch("r1_ws", 1024)))
         for i, dp in enumerate(self.dps):
