@@ -292,13 +292,15 @@ class AMPContext:
 
 class FusedAdam:
     """get_optimizer's torch.optim.Adam (sched_optim.py:5-27) over a flat parameter block, fused with clip_grad_norm_
-    and EMA.update (amp_utils.py:29-41, io_ckpt.py:23-29) in one multi-tensor launch."""
+    and EMA.update (amp_utils.py:29-41, io_ckpt.py:23-29) in one multi-tensor launch.  weight_decay is torch.optim.Adam's (L2, added to
+    the clipped gradient); decoupled makes it AdamW's.  With weight_decay 0 the launch is gan_adam_step, as it always was."""
 
     def __init__(self, ctx: Ctx, names: List[str], shapes: List[torch.Size], init: Dict[str, torch.Tensor], lr=2e-4, betas=(0.5, 0.999),
-                 eps=1e-8, weight_decay=0.0, ema_decay: Optional[float] = None):
-        if weight_decay != 0.0:
-            raise NotImplementedError("weight_decay != 0 is not used by the reference configs")
+                 eps=1e-8, weight_decay=0.0, ema_decay: Optional[float] = None, decoupled: bool = False):
+        if not weight_decay >= 0.0:
+            raise ValueError(f"Invalid weight_decay value: {weight_decay}")
         self.ctx, self.names, self.lr, self.betas, self.eps, self.ema_decay = ctx, names, lr, betas, eps, ema_decay
+        self.weight_decay, self.decoupled = float(weight_decay), bool(decoupled)
         sizes = [int(np.prod(s)) for s in shapes]
         self.offsets = np.concatenate([[0], np.cumsum([(n + 3) // 4 * 4 for n in sizes])]).astype(np.int64)  # 16-byte aligned slices
         total = int(self.offsets[-1])
@@ -353,9 +355,11 @@ class FusedAdam:
         return self._tables[key]
 
     def step_op(self, max_norm: Optional[float], grad_scale: float = 1.0, skip: Sequence[str] = ()):
-        return self.ctx.ops.adam_step(self.table(skip), len(self.names), self.chunk_tensor, self.chunk_off, self.nchunks, self.lr,
-                                      self.betas[0], self.betas[1], self.eps, max_norm if max_norm is not None else 0.0, grad_scale,
-                                      self.ema_decay if self.ema_decay is not None else 0.0, self.norm_out, self.ws, lr_dev=self.lr_dev)
+        args = (self.table(skip), len(self.names), self.chunk_tensor, self.chunk_off, self.nchunks, self.lr, self.betas[0], self.betas[1], self.eps,
+                max_norm if max_norm is not None else 0.0, grad_scale, self.ema_decay if self.ema_decay is not None else 0.0, self.norm_out, self.ws)
+        if self.weight_decay == 0.0:
+            return self.ctx.ops.adam_step(*args, lr_dev=self.lr_dev)
+        return self.ctx.ops.adam_step_wd(*args, self.weight_decay, self.decoupled, lr_dev=self.lr_dev)
 
 
 def _adam_state_dict(opt: "FusedAdam", with_initial_lr: bool = False) -> dict:
@@ -367,8 +371,10 @@ def _adam_state_dict(opt: "FusedAdam", with_initial_lr: bool = False) -> dict:
         shp = opt.params[n].shape
         state[i] = {"step": steps[i].float().reshape(()), "exp_avg": opt.flat_m[o:o + sz].view(shp).clone(),
                     "exp_avg_sq": opt.flat_v[o:o + sz].view(shp).clone()}
-    group = {"lr": opt.lr, "betas": tuple(opt.betas), "eps": opt.eps, "weight_decay": 0.0, "amsgrad": False, "maximize": False, "foreach": None,
-             "capturable": False, "differentiable": False, "fused": None, "params": list(range(len(opt.names)))}
+    group = {"lr": opt.lr, "betas": tuple(opt.betas), "eps": opt.eps, "weight_decay": opt.weight_decay, "amsgrad": False, "maximize": False,
+             "foreach": None, "capturable": False, "differentiable": False, "fused": None, "params": list(range(len(opt.names)))}
+    if opt.weight_decay != 0.0 and opt.decoupled:      # torch 2.x's Adam / AdamW write the key; without decay the dict stays what it was
+        group["decoupled_weight_decay"] = True
     if with_initial_lr:      # torch.optim.lr_scheduler.LambdaLR adds it to every param group it schedules (Basic_GAN/src/train.py:54-58)
         group["initial_lr"] = opt.base_lr
     return {"state": state, "param_groups": [group]}
@@ -386,7 +392,9 @@ def _load_adam_state_dict(opt: "FusedAdam", sd: dict):
         steps[i] = int(float(st["step"]))
     opt.steps.copy_(steps)
     g = sd["param_groups"][0]
-    if (tuple(g["betas"]), g["eps"]) != (tuple(opt.betas), opt.eps):
+    wd = float(g.get("weight_decay", 0.0))
+    decoupled = bool(g.get("decoupled_weight_decay", False)) and wd != 0.0
+    if (tuple(g["betas"]), g["eps"], wd, decoupled) != (tuple(opt.betas), opt.eps, opt.weight_decay, opt.decoupled and opt.weight_decay != 0.0):
         raise ValueError("checkpoint optimiser hyper-parameters differ from the trainer's config (they are baked into its programs)")
     if g["lr"] != opt.lr:       # a scheduler had moved it (Basic_GAN's LambdaLR): the device scalar follows the checkpoint
         opt.set_lr(g["lr"])
@@ -473,9 +481,13 @@ class CutTrainer:
         for k, b in discriminator.named_buffers():
             b.data = self.d_buffers[k]
         og, od = get_optimizer_config(config["optim"]["G"]), get_optimizer_config(config["optim"]["D"])
+        # optim.{G,D}.weight_decay is torch.optim.Adam's L2 term, as the reference passes it; mi355x.decoupled_weight_decay (build-only key,
+        # default false) makes both optimisers AdamW
+        decoupled = bool((config.get("mi355x") or {}).get("decoupled_weight_decay", False))
         self.opt_G = FusedAdam(self.ctx, list(gsd), [v.shape for v in gsd.values()], gsd, og["lr"], og["betas"], 1e-8, og["weight_decay"],
-                               ema_decay=config["ema"]["decay"])
-        self.opt_D = FusedAdam(self.ctxD, list(dsd), [v.shape for v in dsd.values()], dsd, od["lr"], od["betas"], 1e-8, od["weight_decay"])
+                               ema_decay=config["ema"]["decay"], decoupled=decoupled)
+        self.opt_D = FusedAdam(self.ctxD, list(dsd), [v.shape for v in dsd.values()], dsd, od["lr"], od["betas"], 1e-8, od["weight_decay"],
+                               decoupled=decoupled)
         for mod, opt in ((generator, self.opt_G), (discriminator, self.opt_D)):   # modules now alias the trained block
             for k, p in mod.named_parameters():
                 p.data = opt.params[k]

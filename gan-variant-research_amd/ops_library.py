@@ -147,7 +147,8 @@ _LIB.define("replication_pad2d(Tensor x, int pad) -> Tensor")
 _LIB.define("replication_pad2d_bwd(Tensor gy, int pad) -> Tensor")
 _LIB.define("act_bwd(Tensor y, Tensor gy, int act) -> Tensor")
 _LIB.define("fused_clip_adam_ema_(Tensor(a!)[] params, Tensor[] grads, Tensor(b!)[] m, Tensor(c!)[] v, Tensor(d!)[] ema, Tensor(e!) steps, float lr, float b1, "
-            "float b2, float eps, float max_norm, float grad_scale, float ema_decay, Tensor? inv_scale=None, bool skip_nonfinite=False) -> (Tensor, Tensor)")
+            "float b2, float eps, float max_norm, float grad_scale, float ema_decay, Tensor? inv_scale=None, bool skip_nonfinite=False, "
+            "float weight_decay=0.0, bool decoupled=False) -> (Tensor, Tensor)")
 _LIB.define("patchnce_fwd(Tensor src_feat, Tensor tgt_feat, Tensor ids, float temperature) -> (Tensor, Tensor)")
 _LIB.define("patchnce_bwd(Tensor saved, Tensor grad_loss) -> Tensor")
 _LIB.define("diffaugment_fwd(Tensor x, Tensor params) -> Tensor")
@@ -316,10 +317,11 @@ _LIB.impl("act_bwd", lambda y, gy, act: _act_bwd(_f(y), _f(gy), act), _IMPL)
 
 
 # ---- fused clip_grad_norm_ + Adam + EMA.update (amp_utils.py:29-41, sched_optim.py:5-27, io_ckpt.py:23-29)
-def _fused_adam(params, grads, m, v, ema, steps, lr, b1, b2, eps, max_norm, grad_scale, ema_decay, inv_scale=None, skip_nonfinite=False):
+def _fused_adam(params, grads, m, v, ema, steps, lr, b1, b2, eps, max_norm, grad_scale, ema_decay, inv_scale=None, skip_nonfinite=False,
+                weight_decay=0.0, decoupled=False):
     from .training import fused_adam_launch
     return fused_adam_launch(list(params), list(grads), list(m), list(v), list(ema), steps, lr, b1, b2, eps, max_norm, grad_scale, ema_decay,
-                             inv_scale, skip_nonfinite)
+                             inv_scale, skip_nonfinite, weight_decay, decoupled)
 
 
 _LIB.impl("fused_clip_adam_ema_", _fused_adam, _IMPL)

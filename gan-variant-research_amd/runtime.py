@@ -649,6 +649,16 @@ class HipOps:
                           C.c_float(b1), C.c_float(b2), C.c_float(eps), C.c_float(max_norm), C.c_float(grad_scale), C.c_float(ema_decay),
                           self._p(lr_dev), self._p(inv_scale), int(skip_nonfinite), self._p(norm_out), self._p(ws), self._s())
 
+    def adam_step_wd(self, table, ntensors, chunk_tensor, chunk_off, nchunks, lr, b1, b2, eps, max_norm, grad_scale, ema_decay, norm_out, ws,
+                     weight_decay, decoupled=False, lr_dev=None, inv_scale=None, skip_nonfinite=False) -> Op:
+        """adam_step with torch's weight decay: torch.optim.Adam(weight_decay) (L2, added to the clipped gradient) or, decoupled,
+        torch.optim.AdamW (p *= 1 - lr * weight_decay before the update).  The decay is not part of the norm."""
+        assert norm_out.numel() >= 3
+        return self._call("gan_adam_step_wd", self._p(table), ntensors, self._p(chunk_tensor), self._p(chunk_off), nchunks, C.c_float(lr),
+                          C.c_float(b1), C.c_float(b2), C.c_float(eps), C.c_float(max_norm), C.c_float(grad_scale), C.c_float(ema_decay),
+                          self._p(lr_dev), self._p(inv_scale), int(skip_nonfinite), C.c_float(weight_decay), int(decoupled), self._p(norm_out),
+                          self._p(ws), self._s())
+
     def scaler_update(self, scale, inv_scale, tracker, found_inf, growth=2.0, backoff=0.5, interval=2000) -> Op:
         assert tracker.dtype == torch.int32
         return self._call("gan_scaler_update", self._p(scale), self._p(inv_scale), self._p(tracker), self._p(found_inf), C.c_float(growth),

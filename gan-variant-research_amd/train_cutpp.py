@@ -8,7 +8,8 @@ What differs is what runs underneath: the step is the fused `cut.CutTrainer` on 
 Image folders are decoded once with Pillow at start-up into a `dataio.ImageStore` (resident on the device when they fit
 `mi355x.dataset_cache_gb`, default 8; decoded per batch otherwise) and transformed on the device (dataio.py, the reference's train
 transform); with `--synthetic` uniform noise batches of the right shape stand in (there is no dataset on the benchmark box); folders
-that do not exist are an error.  Build-only keys live under `mi355x:` (amp dtype, synthetic data, dataset_cache_gb).
+that do not exist are an error.  Build-only keys live under `mi355x:` (amp dtype, synthetic data, dataset_cache_gb,
+decoupled_weight_decay: `optim.{G,D}.weight_decay` as AdamW's decay instead of torch.optim.Adam's L2 term).
 """
 from __future__ import annotations
 

@@ -26,12 +26,20 @@ from .runtime import ADAM_CHUNK
 class HipAdam(torch.optim.Optimizer):
     """torch.optim.Adam semantics (single-tensor formula of torch/optim/adam.py) executed by gan_adam_step: global-norm clipping,
     the Adam update of every tensor and (optionally) an EMA shadow update in three launches regardless of the tensor count.
-    Parameters whose `.grad` is None are skipped exactly as torch does (no step increment)."""
+    Parameters whose `.grad` is None are skipped exactly as torch does (no step increment, no decay).
 
-    def __init__(self, params, lr=2e-4, betas=(0.5, 0.999), eps=1e-8, weight_decay=0.0, amsgrad=False):
-        if weight_decay != 0.0 or amsgrad:
-            raise NotImplementedError("the reference configs use weight_decay 0 and no amsgrad")
-        super().__init__(params, dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay, amsgrad=False))
+    weight_decay (per param group) and decoupled_weight_decay are torch.optim.Adam's: L2 decay joins the clipped gradient, decoupled decay
+    multiplies the parameter by 1 - lr * weight_decay first (AdamW).  A group with weight_decay 0 launches gan_adam_step, any other
+    gan_adam_step_wd.  The learning rate is a device float of each plan, rewritten when group['lr'] changed, so a
+    torch.optim.lr_scheduler on this optimiser keeps one table, one workspace and one prebuilt launch per group."""
+
+    def __init__(self, params, lr=2e-4, betas=(0.5, 0.999), eps=1e-8, weight_decay=0.0, amsgrad=False, *, decoupled_weight_decay=False):
+        if amsgrad:
+            raise NotImplementedError("amsgrad needs a fourth state tensor (max_exp_avg_sq) that gan_adam_tensor does not carry")
+        if not weight_decay >= 0.0:
+            raise ValueError(f"Invalid weight_decay value: {weight_decay}")
+        super().__init__(params, dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay, amsgrad=False,
+                                      decoupled_weight_decay=bool(decoupled_weight_decay)))
         self._ema: Dict[int, torch.Tensor] = {}      # id(param) -> shadow tensor (attached by EMA)
         self._ema_decay = 0.0
         self._plans = {}
@@ -55,7 +63,7 @@ class HipAdam(torch.optim.Optimizer):
 
     def _plan(self, gi, group, live):
         """Prebuilt launch for one param group and one pattern of present gradients (ops hold raw pointers)."""
-        key = (gi, live, group["lr"], group["betas"], group["eps"], torch.cuda.current_stream().cuda_stream if torch.cuda.is_available() else 0)
+        key = (gi, live, group["betas"], group["eps"], torch.cuda.current_stream().cuda_stream if torch.cuda.is_available() else 0)
         pl = self._plans.get(key)
         if pl is None:
             ps = group["params"]
@@ -70,7 +78,8 @@ class HipAdam(torch.optim.Optimizer):
                     ct.append(i); co.append(off)
             pl = {"ctx": ctx, "norm": torch.zeros(4, dtype=torch.float32, device=dev),
                   "ct": torch.tensor(ct, dtype=torch.int32, device=dev), "co": torch.tensor(co, dtype=torch.int64, device=dev),
-                  "ws": torch.zeros(len(ct) + 16, dtype=torch.float32, device=dev), "ops": {}}
+                  "ws": torch.zeros(len(ct) + 16, dtype=torch.float32, device=dev), "ops": {},
+                  "lr": float(group["lr"]), "lr_dev": torch.full((1,), float(group["lr"]), dtype=torch.float32, device=dev)}
             pl["table"] = ctx.ops.make_adam_table(ents)
             pl["n"], pl["nchunks"] = len(ps), len(ct)
             self._plans[key] = pl
@@ -91,11 +100,23 @@ class HipAdam(torch.optim.Optimizer):
                 if on:
                     self.state[p]["grad_buf"].copy_(p.grad)
             mn = float(max_grad_norm) if max_grad_norm is not None else 0.0
-            op = pl["ops"].get(mn)
+            if float(group["lr"]) != pl["lr"]:      # a scheduler moved the rate: one device float follows, the prebuilt launch stays
+                pl["lr"] = float(group["lr"])
+                pl["lr_dev"].fill_(pl["lr"])
+            wd, dec = float(group.get("weight_decay", 0.0)), bool(group.get("decoupled_weight_decay", False))
+            if not wd >= 0.0:
+                raise ValueError(f"Invalid weight_decay value: {wd}")
+            hk = (mn, wd, dec and wd != 0.0)
+            op = pl["ops"].get(hk)
             if op is None:
                 b1, b2 = group["betas"]
-                op = pl["ops"][mn] = pl["ctx"].ops.adam_step(pl["table"], pl["n"], pl["ct"], pl["co"], pl["nchunks"], group["lr"], b1, b2, group["eps"],
-                                                              mn, 1.0, self._ema_decay, pl["norm"], pl["ws"])
+                args = (pl["table"], pl["n"], pl["ct"], pl["co"], pl["nchunks"], pl["lr"], b1, b2, group["eps"], mn, 1.0, self._ema_decay,
+                        pl["norm"], pl["ws"])
+                if wd == 0.0:
+                    op = pl["ctx"].ops.adam_step(*args, lr_dev=pl["lr_dev"])
+                else:
+                    op = pl["ctx"].ops.adam_step_wd(*args, wd, dec, lr_dev=pl["lr_dev"])
+                pl["ops"][hk] = op
             op()
             self.last_grad_norm = pl["norm"]
             for p, on in zip(ps, live):            # EMA.update covers every parameter, also one the kernel skipped for want of a gradient
@@ -117,19 +138,30 @@ class HipAdam(torch.optim.Optimizer):
         self._plans = {}
         for group in self.param_groups:
             group["betas"] = tuple(group["betas"])
+            group.setdefault("decoupled_weight_decay", False)      # a checkpoint of a torch that does not write the key
             for p in group["params"]:
                 if p in self.state and "exp_avg" in self.state[p]:
                     self._state(p)
 
 
+class HipAdamW(HipAdam):
+    """torch.optim.AdamW: HipAdam with decoupled weight decay and torch's default of 1e-2."""
+
+    def __init__(self, params, lr=2e-4, betas=(0.5, 0.999), eps=1e-8, weight_decay=1e-2, amsgrad=False):
+        super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=amsgrad, decoupled_weight_decay=True)
+
+
 _FUSED_PLANS = {}
 
 
-def fused_adam_launch(params, grads, m, v, ema, steps, lr, b1, b2, eps, max_norm, grad_scale, ema_decay, inv_scale=None, skip_nonfinite=False):
+def fused_adam_launch(params, grads, m, v, ema, steps, lr, b1, b2, eps, max_norm, grad_scale, ema_decay, inv_scale=None, skip_nonfinite=False,
+                      weight_decay=0.0, decoupled=False):
     """Body of torch.ops.mi355x_gan.fused_clip_adam_ema_: clip_grad_norm_(max_norm; 0 = off) on grads * grad_scale, one Adam
     step of every tensor (per-tensor step counters `steps`, int32 [n], incremented on the device) and, if `ema` is non-empty,
     shadow <- decay * shadow + (1 - decay) * p, in three launches regardless of the tensor count.  inv_scale (device float) and
-    skip_nonfinite: GradScaler's unscale_ / step.  Returns (total gradient norm, found_inf).
+    skip_nonfinite: GradScaler's unscale_ / step.  weight_decay / decoupled: torch.optim.Adam's L2 decay or AdamW's (gan_adam_step_wd;
+    0 launches gan_adam_step).  The learning rate is a device float of the plan, rewritten when it changed.  Returns (total gradient
+    norm, found_inf).
     The prebuilt launch is keyed on the STATE tensors only (params, m, v, ema, steps): gradients are fresh tensors every step under
     zero_grad(set_to_none=True), so they are copied into staging buffers the plan owns (one multi-tensor copy) -- a plan per gradient
     address would grow without bound and pin every old gradient."""
@@ -155,27 +187,41 @@ def fused_adam_launch(params, grads, m, v, ema, steps, lr, b1, b2, eps, max_norm
         pl = _FUSED_PLANS[key] = {"ctx": ctx, "norm": torch.zeros(4, dtype=torch.float32, device=dev), "table": ctx.ops.make_adam_table(ents),
                                   "ct": torch.tensor(ct, dtype=torch.int32, device=dev), "co": torch.tensor(co, dtype=torch.int64, device=dev),
                                   "ws": torch.zeros(len(ct) + 16, dtype=torch.float32, device=dev), "gbuf": gbuf,
-                                  "keep": (params, m, v, ema, steps, inv_scale), "ops": {}}
+                                  "keep": (params, m, v, ema, steps, inv_scale), "ops": {},
+                                  "lr": float(lr), "lr_dev": torch.full((1,), float(lr), dtype=torch.float32, device=dev)}
     for g, p in zip(grads, params):
         assert g.dtype == torch.float32 and g.numel() == p.numel()
     torch._foreach_copy_(pl["gbuf"], [g.reshape(-1) for g in grads])
-    hk = (lr, b1, b2, eps, max_norm, grad_scale, ema_decay if ema else 0.0, bool(skip_nonfinite))
+    if float(lr) != pl["lr"]:
+        pl["lr"] = float(lr)
+        pl["lr_dev"].fill_(pl["lr"])
+    if not weight_decay >= 0.0:
+        raise ValueError(f"Invalid weight_decay value: {weight_decay}")
+    hk = (b1, b2, eps, max_norm, grad_scale, ema_decay if ema else 0.0, bool(skip_nonfinite), float(weight_decay), bool(decoupled) and weight_decay != 0.0)
     op = pl["ops"].get(hk)
     if op is None:
-        op = pl["ops"][hk] = pl["ctx"].ops.adam_step(pl["table"], n, pl["ct"], pl["co"], len(pl["ct"]), lr, b1, b2, eps, max_norm, grad_scale,
-                                                      ema_decay if ema else 0.0, pl["norm"], pl["ws"], inv_scale=inv_scale, skip_nonfinite=skip_nonfinite)
+        args = (pl["table"], n, pl["ct"], pl["co"], len(pl["ct"]), pl["lr"], b1, b2, eps, max_norm, grad_scale, ema_decay if ema else 0.0,
+                pl["norm"], pl["ws"])
+        kw = dict(lr_dev=pl["lr_dev"], inv_scale=inv_scale, skip_nonfinite=skip_nonfinite)
+        if weight_decay == 0.0:
+            op = pl["ctx"].ops.adam_step(*args, **kw)
+        else:
+            op = pl["ctx"].ops.adam_step_wd(*args, float(weight_decay), bool(decoupled), **kw)
+        pl["ops"][hk] = op
     op()
     AG.notify_weights_changed()
     return pl["norm"][:1].clone(), pl["norm"][2:3].clone()
 
 
 def get_optimizer(model, opt_config: dict):
-    """sched_optim.py:5-27 (Adam only on this path; the reference's default type is also 'adam')."""
+    """sched_optim.py:5-27: 'adam' (the reference's default type) -> HipAdam, 'adamw' -> HipAdamW, both with the config's weight_decay
+    (default 0.0, as sched_optim.py:18 reads it)."""
     kind = opt_config.get("type", "adam").lower()
-    if kind != "adam":
-        raise NotImplementedError(f"optimizer type {kind!r}: the MI355X path implements the reference's configured Adam")
-    return HipAdam(model.parameters(), lr=opt_config.get("lr", 2e-4), betas=tuple(opt_config.get("betas", [0.5, 0.999])),
-                   weight_decay=opt_config.get("weight_decay", 0.0))
+    if kind not in ("adam", "adamw"):
+        raise NotImplementedError(f"optimizer type {kind!r}: the MI355X path implements Adam and AdamW")
+    cls = HipAdam if kind == "adam" else HipAdamW
+    return cls(model.parameters(), lr=opt_config.get("lr", 2e-4), betas=tuple(opt_config.get("betas", [0.5, 0.999])),
+               weight_decay=opt_config.get("weight_decay", 0.0))
 
 
 class _UnitScaler:

@@ -518,6 +518,28 @@ typedef struct gan_adam_tensor {
 int gan_adam_step(const gan_adam_tensor* table, int ntensors, const int32_t* chunk_tensor, const int64_t* chunk_off,
                   int nchunks, float lr, float beta1, float beta2, float eps, float max_norm, float grad_scale,
                   float ema_decay, const float* lr_dev, const float* inv_scale_dev, int skip_nonfinite, float* norm_out, float* ws, void* stream);
+/* gan_adam_step with torch's weight decay (sched_optim.py:16-25 hands optim.{G,D}.weight_decay to torch.optim.Adam).  The arguments are
+ * gan_adam_step's in order, with weight_decay and decoupled in front of norm_out; everything said above holds, and in addition:
+ * weight_decay == 0: the kernels of gan_adam_step are launched, so every result equals gan_adam_step's bit for bit.
+ * decoupled = 0, torch.optim.Adam(weight_decay) (torch/optim/adam.py: grad = grad.add(param, alpha = weight_decay)).  The reference runs
+ *   unscale_ -> clip_grad_norm_ -> step, so the decay meets the gradient after scaling and clipping:
+ *   g_eff = g * (grad_scale * *inv_scale_dev * coef) + weight_decay * p_old, and m, v and p are gan_adam_step's expressions on g_eff.
+ * decoupled = 1, torch.optim.AdamW / Adam(decoupled_weight_decay = True): p' = p_old * (1 - rate * weight_decay), rate = *lr_dev when
+ *   given, else lr; m and v come from the undecayed gradient; p_new = p' - (rate / bc1) * m / denom.
+ * Both: the decay is NOT part of norm_out[0] (the norm), norm_out[1] (the coefficient) or norm_out[2] (found_inf): the norm is that of
+ *   the scaled gradients alone.  The EMA shadow reads p_new.  A tensor with g == NULL is not touched and not decayed (torch skips a
+ *   parameter without a gradient entirely).  p is read anyway: no load or store is added, 28 B/param (36 with EMA).
+ * Roundings, all fp32: decoupled = 0 adds the product weight_decay * p_old and its sum with the scaled gradient (or one fma) in front of
+ *   gan_adam_step's chain; decoupled = 1 adds rate * weight_decay, 1 - that (both once per block) and the product with p_old in front
+ *   of the final subtraction.
+ * Non-finite gradients: skip_nonfinite = 1: as gan_adam_step -- nothing but norm_out is written, so nothing is decayed either.
+ *   skip_nonfinite = 0: gan_adam_step's table with g_eff in place of g: a NaN coefficient makes p, m, v of every live tensor NaN; the
+ *   coefficient 0 after an Inf leaves g_eff = weight_decay * p (decoupled = 0) or 0 (decoupled = 1) for the finite elements and NaN at the Inf one.
+ * Refused, with -1 and nothing launched: gan_adam_step's cases, weight_decay < 0 or NaN, decoupled outside {0, 1}. */
+int gan_adam_step_wd(const gan_adam_tensor* table, int ntensors, const int32_t* chunk_tensor, const int64_t* chunk_off,
+                     int nchunks, float lr, float beta1, float beta2, float eps, float max_norm, float grad_scale,
+                     float ema_decay, const float* lr_dev, const float* inv_scale_dev, int skip_nonfinite, float weight_decay, int decoupled,
+                     float* norm_out, float* ws, void* stream);
 /* torch.amp.GradScaler.update on the device (amp_utils.py:22,41): scale *= backoff_factor after an overflow (found_inf != 0, e.g.
  * norm_out + 2 of gan_adam_step), *= growth_factor after growth_interval clean steps; inv_scale = 1 / scale; no host synchronisation.
  * One rounding for the product, one for the reciprocal.  A scale backed off below 2^-126 goes subnormal and 1 / scale overflows to Inf
