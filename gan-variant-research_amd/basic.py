@@ -130,8 +130,10 @@ class CycleGANTrainer:
 
     def __init__(self, G_A2B: ResnetGenerator, G_B2A: ResnetGenerator, D_A: NLayerDiscriminator, D_B: NLayerDiscriminator, cfg: dict,
                  batch_size: int, image_size: int, device="cuda", amp: Optional[bool] = None, ops=None, world_size: int = 1, process_group=None,
-                 fp8: Optional[bool] = None, fp8_wgrad: Optional[bool] = None):
-        """fp8 (default: cfg['mi355x']['fp8'], else False): the residual blocks' convolutions of both generators read e4m3 operand copies
+                 fp8: Optional[bool] = None, fp8_wgrad: Optional[bool] = None, average_losses: bool = False):
+        """average_losses (needs process_group): the three losses train_iteration returns are the means over the ranks -- one small
+        all-reduce of the loss slots queued in front of their read-back (the training driver).
+        fp8 (default: cfg['mi355x']['fp8'], else False): the residual blocks' convolutions of both generators read e4m3 operand copies
         in the forward pass and in the input gradient of all six generator passes; bf16 (amp) mode only.
         fp8_wgrad (default: cfg['mi355x']['fp8_wgrad'], else False): their weight gradients run on the same e4m3 copies; needs fp8.  The
         output gradients' copies carry power-of-two scales here (GeneratorNet.fp8_pow2_scales), so on 16x16 maps at batch >= 64 the e4m3
@@ -147,6 +149,7 @@ class CycleGANTrainer:
             self.ops.bind()
         self.ctx = Ctx(self.ops, self.device, self.dtype)
         self.world_size, self.pg = world_size, process_group
+        self.average_losses = bool(average_losses) and process_group is not None
         self.gan = GANLoss(cfg["loss"]["gan"])
         lr_g, lr_d, betas = cfg["optim"]["lr_g"], cfg["optim"]["lr_d"], tuple(cfg["optim"]["betas"])
         f32 = lambda sd: {k: v.detach().to(self.device, torch.float32) for k, v in sd.items()}
@@ -323,7 +326,7 @@ class CycleGANTrainer:
         return self.sched_epoch
 
     def _allreduce(self, opt):
-        if self.world_size > 1:
+        if self.world_size > 1 or getattr(self, "force_allreduce", False):
             import torch.distributed as dist
             dist.all_reduce(opt.flat_g, group=self.pg)
 
@@ -355,5 +358,11 @@ class CycleGANTrainer:
         _notify_weights_changed()
         if not sync:
             return None
+        if self.average_losses:              # every slot is rewritten by the next iteration's programs
+            import torch.distributed as dist
+            dist.all_reduce(self.losses, group=self.pg)
+            n = dist.get_world_size(self.pg)
+            if n > 1:
+                self.losses.mul_(1.0 / n)
         v = self.losses.tolist()
         return {"loss_G": sum(v[0:6]), "loss_D_A": v[6] + v[7], "loss_D_B": v[8] + v[9]}

@@ -438,8 +438,10 @@ class CutTrainer:
 
     def __init__(self, generator: ResNetGenerator, discriminator: MultiscaleDiscriminator, config: dict, batch_size: int, image_size: int,
                  device="cuda", amp: Optional[bool] = None, ops=None, world_size: int = 1, process_group=None, fp8: Optional[bool] = None,
-                 fp8_wgrad: Optional[bool] = None):
-        """fp8 (default: config['mi355x']['fp8'], else False): the residual blocks' convolutions read e4m3 operand copies in the forward pass
+                 fp8_wgrad: Optional[bool] = None, average_losses: bool = False):
+        """average_losses (needs process_group): the loss slots are averaged over the ranks, by one small all-reduce queued in front of
+        their read-back, so that every rank reports -- and checks for NaN -- the losses of the global batch (the training drivers).
+        fp8 (default: config['mi355x']['fp8'], else False): the residual blocks' convolutions read e4m3 operand copies in the forward pass
         and in the input gradient (BASELINE.json configs[4]); needs amp (bf16) -- see nets.GeneratorNet.
         fp8_wgrad (default: config['mi355x']['fp8_wgrad'], else False): their weight gradients run on the same e4m3 copies in all three
         generator passes of a step; needs fp8, whose passes write those copies."""
@@ -462,6 +464,7 @@ class CutTrainer:
         self.ctxD = Ctx(self.opsD, self.device, self.amp.dtype) if self.opsD is not self.ops else self.ctx
         self.ctx32 = self.ctxD if self.amp.dtype == F32 else Ctx(self.opsD, self.device, F32)
         self.world_size, self.pg = world_size, process_group
+        self.average_losses = bool(average_losses) and process_group is not None
         lw = config["loss_weights"]
         self.policy = config["diffaugment"].get("policy", ["color", "translation", "cutout"]) if config["diffaugment"].get("enable", False) else None
         self.aug = DiffAugment(self.policy) if self.policy is not None else None
@@ -742,11 +745,14 @@ class CutTrainer:
         self.D32.refresh_pack()
 
     # ------------------------------------------------------------------ per-step randomness
-    def sample_randomness(self, generator: Optional[torch.Generator] = None, nce_generator: Optional[torch.Generator] = None) -> dict:
+    def sample_randomness(self, generator: Optional[torch.Generator] = None, nce_generator: Optional[torch.Generator] = None,
+                          batch: Optional[int] = None) -> dict:
         """All device-RNG draws of one step, on the CPU generator, in the reference's consumption order.
         Data parallel: DiffAugment draws are per sample (rank-local `generator`), PatchNCE ids are shared by the whole
-        global batch (patchnce_cut.py:63), so every rank passes an identically seeded `nce_generator`."""
-        B, S = self.B, self.S
+        global batch (patchnce_cut.py:63), so every rank passes an identically seeded `nce_generator`.
+        batch (default: this trainer's): the number of DiffAugment rows drawn -- a rank draws the global batch's from generators seeded
+        alike on all ranks and passes its rows (`shard_randomness`) to train_step."""
+        B, S = (self.B if batch is None else int(batch)), self.S
         r = {}
         if self.aug is not None:
             for k in ("aug_real", "aug_fake_d", "aug_fake_g"):
@@ -754,6 +760,15 @@ class CutTrainer:
         ng = generator if nce_generator is None else nce_generator
         r["nce_ids"] = [torch.randint(0, hw, (min(self.P, hw),), generator=ng) for hw in self.nce_hw]
         return r
+
+    @staticmethod
+    def shard_randomness(rnd: dict, lo: int, hi: int) -> dict:
+        """Rows lo .. hi-1 of a global batch's draws: the DiffAugment rows of those samples, the PatchNCE ids whole."""
+        out = {"nce_ids": rnd["nce_ids"]}
+        for k in ("aug_real", "aug_fake_d", "aug_fake_g"):
+            if k in rnd:
+                out[k] = {n: (v[lo:hi] if v.dim() > 0 else v) for n, v in rnd[k].items()}
+        return out
 
     def _load_randomness(self, rnd: dict):
         B, S = self.B, self.S
@@ -865,6 +880,17 @@ class CutTrainer:
     def _allreduce(self, opt: FusedAdam):
         self._allreduce_finish(self._allreduce_start(opt))
 
+    def _average_losses(self):
+        """The loss slots become their mean over the ranks (`_loss_dict` is linear in them, the identity weight's slot is equal on all
+        ranks): queued on the step's stream in front of the read-back, the host waits for nothing here."""
+        if not self.average_losses:
+            return
+        import torch.distributed as dist
+        dist.all_reduce(self.losses, group=self.pg)          # the current stream is the bound one (train_step)
+        n = dist.get_world_size(self.pg)
+        if n > 1:
+            self.losses.mul_(1.0 / n)
+
     # ------------------------------------------------------------------ the step
     def train_step(self, step: int, photos: torch.Tensor, monets: torch.Tensor, rnd: Optional[dict] = None, sync: bool = True):
         """One iteration; returns the reference's loss dict (train_cutpp.py:315-323).  sync=True reads the losses back before
@@ -924,6 +950,7 @@ class CutTrainer:
         _notify_weights_changed()          # parameters changed through raw pointers: module-level bridges repack on next use
         if sync is False:
             return None
+        self._average_losses()
         meta = (step, idw, do_r1)
         if sync == "lag":
             # the read-back of this step's losses is queued behind its kernels and collected when the NEXT step has been queued:

@@ -216,15 +216,16 @@ class InputPipeline:
 # ------------------------------------------------------------------------------------------------ reference-named constructors
 class _Transform:
     """Callable in the shape of the reference's composed transform, but batched: `tf(images)` draws one job per image and returns the
-    device batch.  `tf.last_jobs` keeps the draws (tests replay them through Pillow)."""
+    device batch; `tf(images, jobs)` runs jobs drawn by the caller.  `tf.last_jobs` keeps the draws (tests replay them through Pillow)."""
 
     def __init__(self, make_job, image_size, device, **kw):
         self.make_job, self.image_size = make_job, image_size
         self.pipe = InputPipeline(image_size, device, **kw)
         self.last_jobs: List[Dict] = []
 
-    def __call__(self, images: Sequence[torch.Tensor]) -> torch.Tensor:
-        self.last_jobs = [self.make_job(int(im.shape[0]), int(im.shape[1])) for im in images]
+    def __call__(self, images: Sequence[torch.Tensor], jobs: Optional[Sequence[Dict]] = None) -> torch.Tensor:
+        """jobs: already drawn (a data-parallel rank draws the global batch's and passes those of its images); None: drawn here."""
+        self.last_jobs = [self.make_job(int(im.shape[0]), int(im.shape[1])) for im in images] if jobs is None else list(jobs)
         return self.pipe.run(images, self.last_jobs)
 
 

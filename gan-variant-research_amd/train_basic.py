@@ -1,6 +1,6 @@
 """CycleGAN training driver with the reference's command line (Basic_GAN/src/train.py:33-144):
 
-    python -m gan_variant_research_amd.train_basic --config Basic_GAN/configs/baseline.yaml [--resume CKPT] [--set a.b=c ...] [--synthetic]
+    python -m gan_variant_research_amd.train_basic --config Basic_GAN/configs/baseline.yaml [--resume CKPT] [--set a.b=c ...] [--synthetic] [--gpus N]
 
 `--config` is the reference's only flag (default `configs/baseline.yaml`, train.py:142); the YAML schema, the epoch loop (schedulers
 at every epoch end, `ckpt_e{epoch}.pt` every `save_every` epochs and at the last one) and the checkpoint layout are the reference's.
@@ -18,12 +18,18 @@ Where this driver departs from the reference:
     max(len A, len B) is no multiple of `batch_size`, only the full batches of an epoch run; the driver prints once how many items per
     epoch that leaves out (none are drawn for them).  With the shipped `batch_size: 1` the count is zero.
   * The progress bar's per-iteration losses (train.py:118-122) are printed as epoch means.
+  * `--gpus N` (build-only flag; launch.py) trains data-parallel on N GPUs of one node.  `training.batch_size` stays the per-GPU batch;
+    the loader batches N x batch_size items, every rank draws the whole global batch in order (`draw_batch`: Python's `random` moves as
+    in one process at that batch size) and fetches and transforms its own rows, so N ranks x B are one process at batch N B.  Only full
+    global batches run.  Rank 0 alone prints and saves, the losses are those of the global batch; checkpoints do not depend on N.
+    Every rank holds its own ImageStores (sharding them across ranks is not done) with 16 // N decode threads.
 """
 from __future__ import annotations
 
 import argparse
 import os
 import random
+import sys
 from typing import List, Optional
 
 import torch
@@ -32,6 +38,7 @@ import yaml
 
 from . import basic as BG
 from . import dataio
+from . import launch
 from .cut import set_seed
 from .train_cutpp import build_store, override_config
 
@@ -46,6 +53,7 @@ def parse_args(argv=None):
     ap.add_argument("--resume", type=str, default=None, help="checkpoint to continue from (build-only flag)")
     ap.add_argument("--set", nargs="+", default=[], help="override config values, e.g. training.epochs=2 (build-only flag)")
     ap.add_argument("--synthetic", action="store_true", help="uniform-noise batches instead of the image folders (build-only flag)")
+    launch.add_arguments(ap)
     return ap.parse_args(argv)
 
 
@@ -100,51 +108,79 @@ def main(argv=None, ops=None, device: Optional[str] = None, transform=None) -> d
     the device pipeline; on a CPU device it raises that it runs on the GPU).  Returns the last epoch, its mean losses, the checkpoints
     written, the three current learning rates and the per-epoch history of losses and rates."""
     args = parse_args(argv)
+    if args.gpus > 1 and "WORLD_SIZE" not in os.environ:      # this process becomes the launcher, before any GPU call
+        launch.launch_ranks(["-m", __spec__.name if __spec__ is not None else __name__], sys.argv[1:] if argv is None else list(argv), args.gpus,
+                            check_devices=not args.launch_check)
+        return {"launched": args.gpus}
+    launch.check_rank_count(args.gpus, check_devices=False)
+    world = launch.world_from_env(args.gpus)
+    if args.launch_check:
+        launch.launch_check()
+        return {"launch_check": True}
     with open(args.config) as f:
         cfg = yaml.safe_load(f)
     cfg = override_config(cfg, args.set)
+    set_seed(cfg["training"]["seed"])
+    with launch.join(world, device if device is not None else (cfg.get("runtime") or {}).get("device", "cuda"), ops) as place:
+        return _train(args, cfg, place, transform)
+
+
+def _train(args, cfg: dict, place, transform) -> dict:
+    """One rank's run (the only one without --gpus): `place.group` is None in the plain single-process run, which then does what it
+    always did.  With a group, N ranks x batch B are one process at batch N B (module docstring); rank 0 prints and saves."""
     tr_cfg, data = cfg["training"], cfg["data"]
-    set_seed(tr_cfg["seed"])
-    device = torch.device(device if device is not None else (cfg.get("runtime") or {}).get("device", "cuda"))
-    print(f"Using device: {device}")
+    device, ops, dp, N = place.device, place.ops, place.group is not None, place.world
+    say = print if place.first else (lambda *a, **kw: None)
+    say(f"Using device: {device}" + (f" ({N} rank(s), global batch {N * int(tr_cfg['batch_size'])})" if dp else ""))
     B, S, load_size = int(tr_cfg["batch_size"]), int(data["img_size"]), int(data["load_size"])
+    whole, rows = N * B, place.rows(B)                         # the global batch and this rank's rows of it
     synthetic = bool(args.synthetic or (cfg.get("mi355x") or {}).get("synthetic", False))
     if synthetic:
-        print("[train_basic] --synthetic: uniform-noise batches stand in for the data loader")
+        say("[train_basic] --synthetic: uniform-noise batches stand in for the data loader")
         n_items = SYNTHETIC_ITEMS
         g = torch.Generator().manual_seed(1234)
     else:
         folder_a, folder_b = os.path.join(data["root"], data["domain_a"]), os.path.join(data["root"], data["domain_b"])
-        store_a = build_store(list_images(data["root"], data["domain_a"]), device, cfg, "domain_a", folder_a)
-        store_b = build_store(list_images(data["root"], data["domain_b"]), device, cfg, "domain_b", folder_b)
+        workers = max(1, 16 // N) if dp else None
+        store_a = build_store(list_images(data["root"], data["domain_a"]), device, cfg, "domain_a", folder_a, workers, quiet=not place.first)
+        store_b = build_store(list_images(data["root"], data["domain_b"]), device, cfg, "domain_b", folder_b, workers, quiet=not place.first)
         n_items = max(len(store_a), len(store_b))
         make_tf = transform if transform is not None else (lambda size, dev: default_transform(size, dev, max_batch=max(B, 16)))
         tf_a, tf_b = make_tf(S, device), make_tf(S, device)
-        loader = make_loader(n_items, B)
-    if n_items < B:
-        raise ValueError(f"an epoch has {n_items} items, fewer than training.batch_size = {B}")
-    if n_items % B:
-        print(f"[train_basic] {n_items} items per epoch, batch_size {B}: the last {n_items % B} item(s) of every epoch are left out "
-              "(the trainer's buffers hold full batches only)")
+        loader = make_loader(n_items, whole)
+    if n_items < whole:
+        raise ValueError(f"an epoch has {n_items} items, fewer than training.batch_size = {whole}" + (f" = {N} ranks x {B}" if dp else ""))
+    if n_items % whole:
+        say(f"[train_basic] {n_items} items per epoch, batch_size {whole}: the last {n_items % whole} item(s) of every epoch are left out "
+            "(the trainer's buffers hold full batches only)")
 
     mods = BG.build_models(cfg, "cpu")
-    trainer = BG.CycleGANTrainer(*[m.to(device) for m in mods], cfg, B, S, device=device, amp=tr_cfg["amp"], ops=ops)
+    if dp:
+        trainer = BG.CycleGANTrainer(*[m.to(device) for m in mods], cfg, B, S, device=device, amp=tr_cfg["amp"], ops=ops, world_size=N,
+                                     process_group=place.group, average_losses=True)
+        trainer.force_allreduce = True       # a one-rank group runs the collectives too (sums over one rank: the same bits)
+    else:
+        trainer = BG.CycleGANTrainer(*[m.to(device) for m in mods], cfg, B, S, device=device, amp=tr_cfg["amp"], ops=ops)
     start_epoch = 1
     if args.resume:
         start_epoch = int(trainer.load_checkpoint(args.resume)) + 1
-        print(f"Resumed from epoch {start_epoch - 1}")
+        say(f"Resumed from epoch {start_epoch - 1}")
     total_epochs, save_dir = int(tr_cfg["epochs"]), tr_cfg["save_dir"]
-    os.makedirs(save_dir, exist_ok=True)
+    if place.first:
+        os.makedirs(save_dir, exist_ok=True)
 
     def batches():
         if synthetic:
-            for _ in range(n_items // B):
-                yield (torch.rand(2, B, 3, S, S, generator=g) * 2 - 1).to(device)
+            for _ in range(n_items // whole):
+                x = torch.rand(2, whole, 3, S, S, generator=g) * 2 - 1
+                yield (x[:, rows] if dp else x).to(device)
             return
         for items in loader:
-            if len(items) < B:
+            if len(items) < whole:
                 continue
-            ia, ib, jobs_a, jobs_b = draw_batch(items, store_a.sizes, store_b.sizes, load_size, S)
+            ia, ib, jobs_a, jobs_b = draw_batch(items, store_a.sizes, store_b.sizes, load_size, S)      # the global batch, on every rank
+            if dp:
+                ia, ib, jobs_a, jobs_b = ia[rows], ib[rows], jobs_a[rows], jobs_b[rows]
             yield tf_a(store_a.fetch(ia), jobs_a), tf_b(store_b.fetch(ib), jobs_b)
 
     rates = lambda: [o.lr for o in (trainer.opt_G, trainer.opt_DA, trainer.opt_DB)]
@@ -157,15 +193,23 @@ def main(argv=None, ops=None, device: Optional[str] = None, transform=None) -> d
                 sums[k] = sums.get(k, 0.0) + v
             n += 1
         means = {k: v / n for k, v in sums.items()}
-        print(f"Epoch {epoch}/{total_epochs}: {n} iterations, " + ", ".join(f"{k[5:]} {v:.3f}" for k, v in means.items()))
+        say(f"Epoch {epoch}/{total_epochs}: {n} iterations, " + ", ".join(f"{k[5:]} {v:.3f}" for k, v in means.items()))
         trainer.scheduler_step()          # epoch end: schedulers + checkpoint (train.py:124-137)
         if epoch % tr_cfg["save_every"] == 0 or epoch == total_epochs:
             path = os.path.join(save_dir, f"ckpt_e{epoch}.pt")
-            trainer.save_checkpoint(path, epoch)
+            if place.first:
+                trainer.save_checkpoint(path, epoch)
+                print(f"Saved checkpoint to {path}")
             checkpoints.append(path)
-            print(f"Saved checkpoint to {path}")
         history.append({"epoch": epoch, "losses": means, "lr": rates()})
-    return {"epoch": epoch, "losses": means, "checkpoints": checkpoints, "lr": rates(), "history": history}
+    if device.type == "cuda":
+        torch.cuda.synchronize(device)
+    out = {"epoch": epoch, "losses": means, "checkpoints": checkpoints, "lr": rates(), "history": history,
+           "digest": launch.state_digest((trainer.opt_G, trainer.opt_DA, trainer.opt_DB))}
+    if dp:
+        out.update(rank=place.rank, world=N)
+        print(f"[rank {place.rank}/{N}] state digest {out['digest']}", file=sys.stderr, flush=True)     # equal on all ranks
+    return out
 
 
 if __name__ == "__main__":
