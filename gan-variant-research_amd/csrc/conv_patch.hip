@@ -21,7 +21,9 @@
 //    precomputed, LDS buffer index folded into the ds_read immediate;
 //  * all global loads are plain VGPR loads (no LDS-DMA), so hipcc's counted s_waitcnt vmcnt(N) keeps the prefetch in flight;
 //  * the epilogue pairs lanes 16 apart (same pixel, adjacent channel quads) and writes 16-byte stores; optionally it also
-//    emits the InstanceNorm statistics of its tile (gan_conv_desc.stats) with DPP row reductions.
+//    emits the InstanceNorm statistics of its tile (gan_conv_desc.stats) with DPP row reductions;
+//  * no instantiation uses scratch: per-lane roles are recomputed from the lane index where they are used (lane_now) instead of being
+//    carried across the tap loop, and the epilogues retire the accumulators pixel group by pixel group with their temporaries pinned.
 #include <stdlib.h>
 #include <type_traits>
 #include <atomic>
@@ -74,6 +76,23 @@ __device__ __forceinline__ float row16_sum(float v) {
   v += dpp(v, std::integral_constant<int, 0x141>{});
   v += dpp(v, std::integral_constant<int, 0x140>{});
   return v;
+}
+
+// This lane's index in its wave, computed where it is needed (two v_mbcnt) instead of carried from the kernel's entry: per-lane values the
+// prologue derives from threadIdx.x and an epilogue uses again are live across the tap loop, where the wide tiles have no register for them
+// -- hipcc then keeps them in scratch and reloads them behind a vmcnt(0).  The asm is opaque, so nothing derived from it is hoisted either.
+__device__ __forceinline__ int lane_now() {
+  int l;
+  asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l));
+  return l;
+}
+
+// a * a rounded on its own, never contracted with the addition that consumes it: the sums of squares of the fused statistics are
+// sum + round(t * t) in every instantiation, whatever shape the surrounding code gives the compiler (the partials do not depend on the tile)
+typedef __attribute__((ext_vector_type(2))) float f32x2_t;
+__device__ __forceinline__ float sq_rn(float a) {
+#pragma clang fp contract(off)
+  return a * a;
 }
 
 __device__ __forceinline__ int pixbase(const PatchArgs& a, int b, int m) {
@@ -130,28 +149,33 @@ __device__ __forceinline__ void conv_patch_body(const PatchArgs& a) {
   int tau = (G & 7) == 0 ? (int)(blockIdx.x & 7) * (G >> 3) + (int)(blockIdx.x >> 3) : (int)blockIdx.x;
   if (tau >= a.tiles) return;
 
-  // slab staging role: patch row r = 64*j + wave*8 + (lane>>3); LDS position p = lane&7 holds source chunk p ^ (r&7)
-  const int sr = wave * 8 + (lane >> 3), sp = lane & 7, sc = sp ^ (sr & 7);
+  // slab staging role: patch row r = 64*j + wave*8 + (lane>>3); LDS position p = lane&7 holds source chunk p ^ (r&7).  Every per-lane part
+  // of it is a few bit operations on lane*16, the one lane-derived register the tap loop holds anyway (the weight fetches' offset), and
+  // is re-derived from an opaque copy of it at every use: carried as values of their own they are live across the whole tap loop, and
+  // on the 256-channel tiles hipcc kept them in scratch and reloaded them, behind a vmcnt(0), in front of every staged slice
+  const int lane16 = lane * 16;
   const uint32_t pix_bytes = (uint32_t)a.Cin * 2u;
-  const uint32_t st_lds = (uint32_t)(sr * 128 + sp * 16);
   auto slab_load = [&](const TileGeo& g, int chunk, int j) -> u32x4_t {
-    int srow = sr;
-    asm volatile("" : "+v"(srow));   // keeps the (unrolled) per-slice source addresses from being hoisted and spilled
+    int l16 = lane16;
+    asm volatile("" : "+v"(l16));
+    const int srow = wave * 8 + (l16 >> 7);                    // sr
+    const int sc16 = (l16 ^ (l16 >> 3)) & 0x70;                // 16 * (sp ^ (sr & 7)): sp = lane & 7, sr & 7 = lane >> 3
     int pix = g.P0 + 64 * j + srow;
     pix = pix < a.in_pix ? pix : a.in_pix - 1;
-    return *reinterpret_cast<const u32x4_t*>(a.in + (size_t)((uint32_t)pix * pix_bytes + (uint32_t)(chunk * 128 + sc * 16)));
+    return *reinterpret_cast<const u32x4_t*>(a.in + (size_t)((uint32_t)pix * pix_bytes + (uint32_t)(chunk * 128 + sc16)));
   };
   auto slab_store = [&](int buf, int j, const u32x4_t& v) {
-    *reinterpret_cast<u32x4_t*>(pbuf + buf * PATCHB + j * 8192 + st_lds) = v;
+    int l16 = lane16;
+    asm volatile("" : "+v"(l16));
+    *reinterpret_cast<u32x4_t*>(pbuf + buf * PATCHB + j * 8192 + wave * 1024 + l16) = v;      // sr * 128 + sp * 16 = wave * 1024 + lane * 16
   };
 
   const int wm = wave / WGN, wn = wave % WGN;
-  const int fr = lane & 15, fg = lane >> 4;
+  const int fg = lane >> 4;
   // weights, fragment-major: byte offset of (n16, kb, lane) = ((n16*KB + kb)*64 + lane)*16
   // weights through a buffer descriptor: voffset = lane*16 (constant), everything else is a wave-uniform scalar offset,
   // so a weight fetch costs no vector ALU work at all
   const __amdgpu_buffer_rsrc_t wrsrc = __builtin_amdgcn_make_buffer_rsrc((void*)a.w, 0, a.w_bytes, 0x00020000);
-  const int lane16 = lane * 16;
   const int wn_u = __builtin_amdgcn_readfirstlane(wn);
   auto w_load = [&](int n0_tile, int kb, u32x4_t (&f)[FJ]) {   // one MFMA k-step (32 channels) of this wave's weight rows
     const int base = __builtin_amdgcn_readfirstlane((((n0_tile + wn_u * (16 * FJ)) >> 4) * a.KB + kb) * 1024);   // provably wave-uniform: no waterfall
@@ -189,9 +213,10 @@ __device__ __forceinline__ void conv_patch_body(const PatchArgs& a) {
   int pcur = 0;
   while (true) {
     int lbase[FI];
+    const int fr_t = lane_now() & 15;
 #pragma unroll
     for (int i = 0; i < FI; ++i) {
-      int m = g.m0 + wm * (16 * FI) + i * 16 + fr;
+      int m = g.m0 + wm * (16 * FI) + i * 16 + fr_t;
       m = m < a.M_img ? m : a.M_img - 1;
       lbase[i] = pixbase(a, g.b, m) - g.P0;
     }
@@ -556,11 +581,10 @@ __device__ __forceinline__ void conv_patch_body(const PatchArgs& a) {
       constexpr int ACT = decltype(act_tag)::value;
       constexpr bool MASK = decltype(mask_tag)::value;
       constexpr bool STATS = decltype(stats_tag)::value;
-      // lane roles re-derived from an opaque copy: otherwise hipcc computes the epilogue's per-lane offsets once per kernel, finds no free
-      // register across the tap loop of the 256-channel tiles and spills them -- and every scratch reload waits with vmcnt(0), which
-      // also drains the stores in flight (measured: 21 k cycles of epilogue instead of 9 k)
-      int lane_o = lane;
-      asm volatile("" : "+v"(lane_o));
+      // lane roles re-derived from a lane index computed here: otherwise hipcc computes the epilogue's per-lane offsets once per kernel, finds
+      // no free register across the tap loop of the 256-channel tiles and spills them -- and every scratch reload waits with vmcnt(0),
+      // which also drains the stores in flight (measured: 21 k cycles of epilogue instead of 9 k)
+      const int lane_o = lane_now();
       const int fr = lane_o & 15, fg = lane_o >> 4;
       // results leave through a buffer descriptor: 32-bit offsets (the 64-bit address arithmetic per store was a fifth of the epilogue's
       // instructions and its temporaries spilled beside 144 accumulators), and a store outside the tile's real rows / channels is sent
@@ -569,13 +593,19 @@ __device__ __forceinline__ void conv_patch_body(const PatchArgs& a) {
       const __amdgpu_buffer_rsrc_t mrsrc = __builtin_amdgcn_make_buffer_rsrc((void*)a.mask, 0, a.mask_bytes, 0x00020000);
       float oscale = 1.f;
       if constexpr (FP8) oscale = a.w_scale[0] * (a.in_scale ? a.in_scale[g.b] : 1.f);
-      // The 256-channel tiles walk the pixel groups once per PAIR of channel fragments (JG passes): with 128-144 accumulators live, the
-      // bias quads and statistics of all four fragments at once (48 registers) do not fit beside the next tile's weights in flight
+      // The 256-channel tiles with statistics walk the pixel groups once per PAIR of channel fragments (JG passes): with 128-144 accumulators
+      // live, the bias quads and statistics of all four fragments at once (48 registers) do not fit beside the next tile's weights in flight.
+      // The first pass does not store: it keeps each pixel group's 16-byte run (4 registers for the 8 accumulators it retires) and the
+      // second pass stores both runs back to back, as the one-pass epilogues do -- a wave then writes every 128-byte line of its 64 channels
+      // whole.  Stored a pass apart (~2 us), the two 64-byte halves of a line left the L2 separately and HBM took 1.5x the bytes
+      // (PMC WRITE_SIZE, 256-row tile, 16 images: 52.8 MB per launch for 33.6 MB of output; now 33.6 MB).
       // Statistics are summed over groups of 64 (256-row tiles) or 144 (288-row tiles) pixels at either tile width -- HS groups per wave --
       // and combined in group order: the partials, and with them every result downstream, do not depend on the tile width the
       // planner picks (it depends on the batch size: G(x)[i] stays bit-identical whatever else is in the batch)
-      constexpr int JG = BN == 256 ? FJ / 2 : 1, JW = FJ / JG;
+      constexpr bool SPLIT = BN == 256 && STATS;
+      constexpr int JG = SPLIT ? FJ / 2 : 1, JW = FJ / JG;
       constexpr int HS = (BN == 256 && BM == 256) ? 2 : 1, FH = FI / HS;
+      u32x4_t keep[SPLIT ? FI : 1];   // SPLIT: the first pass's 16-byte run of every pixel group (4 registers for the 8 accumulators it retires)
 #pragma unroll
       for (int jg = 0; jg < JG; ++jg) {
         const int j0 = jg * JW;
@@ -587,16 +617,16 @@ __device__ __forceinline__ void conv_patch_body(const PatchArgs& a) {
         }
 #pragma unroll
         for (int h = 0; h < HS; ++h) {
-        float ssum[STATS ? 4 * JW : 1], ssq[STATS ? 4 * JW : 1];
+        f32x2_t ss[STATS ? 4 * JW : 1];   // (sum, sum of squares) of a channel: one v_pk_add_f32 per result
         if constexpr (STATS) {
 #pragma unroll
-          for (int q = 0; q < 4 * JW; ++q) ssum[q] = ssq[q] = 0.f;
+          for (int q = 0; q < 4 * JW; ++q) ss[q] = f32x2_t{0.f, 0.f};
         }
 #pragma unroll
         for (int i = h * FH; i < (h + 1) * FH; ++i) {
           __builtin_amdgcn_sched_barrier(0);   // keep the scheduler from overlapping pixel groups (registers: it spills on the wide tiles, and the narrow ones must leave room for the other streams)
           int lf = lane_o;
-          if constexpr (JG > 1) asm volatile("" : "+v"(lf));   // every pass recomputes its addresses from the lane id (shared, they would be spilled between the passes)
+          if constexpr (BN == 256) asm volatile("" : "+v"(lf));   // every pass recomputes its addresses from the lane id (shared, they would be spilled between the passes)
           const int m = g.m0 + wm * (16 * FI) + i * 16 + (lf & 15);
           const bool mok = m < a.M_img;
           const int mm = mok ? m : a.M_img - 1;
@@ -609,7 +639,7 @@ __device__ __forceinline__ void conv_patch_body(const PatchArgs& a) {
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
               const float t = FP8 ? acc[i][j0 + j][e] * oscale + bq[j][e] : acc[i][j0 + j][e] + bq[j][e];
-              if constexpr (STATS) { const float tm = mok ? t : 0.f; ssum[4 * j + e] += tm; ssq[4 * j + e] += tm * tm; }
+              if constexpr (STATS) { const float tm = mok ? t : 0.f; ss[4 * j + e] += f32x2_t{tm, sq_rn(tm)}; }
               v[e] = ACT == GAN_ACT_RELU ? (t < 0.f ? 0.f : t) : ACT == GAN_ACT_LRELU ? (t > 0.f ? t : 0.2f * t) : ACT == GAN_ACT_TANH ? tanhf(t) : t;
             }
             if (MASK) {
@@ -634,10 +664,24 @@ __device__ __forceinline__ void conv_patch_body(const PatchArgs& a) {
             const auto ra = __builtin_amdgcn_permlane16_swap(pk[2 * jp][0], pk[2 * jp + 1][0], false, false);
             const auto rb = __builtin_amdgcn_permlane16_swap(pk[2 * jp][1], pk[2 * jp + 1][1], false, false);
             const u32x4_t st = {ra[0], rb[0], ra[1], rb[1]};
-            const int fgl = JG > 1 ? lf >> 4 : fg;   // 256-channel tiles: from the opaque lane id (a hoisted 64-bit store base would be spilled and reloaded per store)
+            const int fgl = BN == 256 ? lf >> 4 : fg;   // 256-channel tiles: from the opaque lane id (a hoisted 64-bit store base would be spilled and reloaded per store)
             const int nst = g.n0 + wn * (16 * FJ) + (j0 + 2 * jp + (fgl & 1)) * 16 + (fgl & 2) * 4;
             const uint32_t off = (mok && nst < a.Nst) ? (ob + (uint32_t)nst) * 2u : 0xfffffff0u;
-            __builtin_amdgcn_raw_buffer_store_b128(st, orsrc, (int)off, 0, 0);
+            if constexpr (SPLIT) {
+              if (jg == 0) keep[i] = st;
+              else {
+                const int nst0 = nst - 2 * 16;      // the run the first pass kept: the same lane, two channel fragments down
+                const uint32_t off0 = (mok && nst0 < a.Nst) ? (ob + (uint32_t)nst0) * 2u : 0xfffffff0u;
+                __builtin_amdgcn_raw_buffer_store_b128(keep[i], orsrc, (int)off0, 0, 0);
+                __builtin_amdgcn_raw_buffer_store_b128(st, orsrc, (int)off, 0, 0);
+              }
+            } else {
+              __builtin_amdgcn_raw_buffer_store_b128(st, orsrc, (int)off, 0, 0);
+            }
+          }
+          if constexpr (SPLIT) {
+#pragma unroll
+            for (int q = 0; q < 4 * JW; ++q) asm volatile("" : "+v"(ss[q]));   // a register pair each, updated in place: left to itself hipcc sinks the sums below the loop, keeps every group alive and spills
           }
         }
         if constexpr (STATS) {
@@ -646,12 +690,12 @@ __device__ __forceinline__ void conv_patch_body(const PatchArgs& a) {
           // row (16-lane) all-reduce with DPP modifiers on the adds -- vector ALU only; __shfl_xor lowers to ds_bpermute and 256 of
           // those per wave cost 8 us per launch, as much as the statistics pass they replace
 #pragma unroll
-          for (int q = 0; q < 4 * JW; ++q) { ssum[q] = row16_sum(ssum[q]); ssq[q] = row16_sum(ssq[q]); }
+          for (int q = 0; q < 4 * JW; ++q) ss[q] = f32x2_t{row16_sum(ss[q][0]), row16_sum(ss[q][1])};
           if (fr == 0) {
 #pragma unroll
             for (int q = 0; q < 4 * JW; ++q) {
               const int ch = (j0 + (q >> 2)) * 16 + fg * 4 + (q & 3);           // channel inside this wave's 16*FJ
-              *reinterpret_cast<float2*>(stsh + ((((wm * HS + h) * WGN + wn) * (16 * FJ) + ch) << 1)) = make_float2(ssum[q], ssq[q]);
+              *reinterpret_cast<float2*>(stsh + ((((wm * HS + h) * WGN + wn) * (16 * FJ) + ch) << 1)) = make_float2(ss[q][0], ss[q][1]);
             }
           }
         }
@@ -660,6 +704,7 @@ __device__ __forceinline__ void conv_patch_body(const PatchArgs& a) {
       if constexpr (STATS) {
         __syncthreads();
         constexpr int WM = 8 / WGN * HS;
+        const int tid = wave * 64 + lane_now();
         if (tid < BN) {
           const int cwn = tid / (16 * FJ), cch = tid % (16 * FJ);
           float2 tot = make_float2(0.f, 0.f);
@@ -683,9 +728,6 @@ __device__ __forceinline__ void conv_patch_body(const PatchArgs& a) {
     // loads are in flight at no extra register; pass B walks the groups again and sums from the rounded gradient (what the consumer will
     // read) and y.  The per-tile partials are summed over the same pixel groups in the same order at either tile width.
     auto epilogue_chain = [&]() {
-      int lane_o = lane;
-      asm volatile("" : "+v"(lane_o));
-      const int fr = lane_o & 15, fg = lane_o >> 4;
       const __amdgpu_buffer_rsrc_t orsrc = __builtin_amdgcn_make_buffer_rsrc((void*)a.out, 0, a.out_bytes, 0x00020000);
       const __amdgpu_buffer_rsrc_t mrsrc = __builtin_amdgcn_make_buffer_rsrc((void*)a.mask, 0, a.mask_bytes, 0x00020000);
       constexpr int HS = (BN == 256 && BM == 256) ? 2 : 1, FH = FI / HS;
@@ -693,6 +735,7 @@ __device__ __forceinline__ void conv_patch_body(const PatchArgs& a) {
 #pragma unroll
       for (int i = 0; i < FI; ++i) {
         __builtin_amdgcn_sched_barrier(0);
+        const int lf = lane_now(), fr = lf & 15, fg = lf >> 4;   // per pixel group, and again in pass B: shared, the lane roles would be live across both passes
         const int m = g.m0 + wm * (16 * FI) + i * 16 + fr;
         const bool mok = m < a.M_img;
         const int mm = mok ? m : a.M_img - 1;
@@ -704,6 +747,7 @@ __device__ __forceinline__ void conv_patch_body(const PatchArgs& a) {
         for (int j = 0; j < FJ; ++j) {
           pk[i][j][0] = (uint32_t)f2bf(acc[i][j][0]) | ((uint32_t)f2bf(acc[i][j][1]) << 16);
           pk[i][j][1] = (uint32_t)f2bf(acc[i][j][2]) | ((uint32_t)f2bf(acc[i][j][3]) << 16);
+          asm volatile("" : "+v"(pk[i][j][0]), "+v"(pk[i][j][1]));   // pass B unpacks these: otherwise hipcc also keeps the halves it packed them from (two more registers per quad)
         }
 #pragma unroll
         for (int j = 0; j < FJ; ++j) {
@@ -725,6 +769,7 @@ __device__ __forceinline__ void conv_patch_body(const PatchArgs& a) {
         float ssum[4 * FJ], ssq[4 * FJ];
 #pragma unroll
         for (int q = 0; q < 4 * FJ; ++q) ssum[q] = ssq[q] = 0.f;
+        const int lf = lane_now(), fr = lf & 15, fg = lf >> 4;
 #pragma unroll
         for (int i = h * FH; i < (h + 1) * FH; ++i) {
           __builtin_amdgcn_sched_barrier(0);
@@ -758,6 +803,7 @@ __device__ __forceinline__ void conv_patch_body(const PatchArgs& a) {
       }
       __syncthreads();
       constexpr int WM = 8 / WGN * HS;
+      const int tid = wave * 64 + lane_now();
       if (tid < BN) {
         const int cwn = tid / (16 * FJ), cch = tid % (16 * FJ);
         float2 tot = make_float2(0.f, 0.f);
