@@ -121,6 +121,10 @@ PROTOTYPES = {
     "gan_resize_ksize_filter": (C.c_int, [C.c_int, C.c_int, C.c_int]),
     "gan_resize_coeffs_filter": (C.c_int, [C.c_int, C.c_int, C.c_int, vp, vp, C.c_int]),
     "gan_input_pipeline_filter": (C.c_int, [vp, vp, C.c_int, vp, C.c_int, C.c_int, vp, C.c_int, vp, vp, vp, vp]),
+    "gan_jpeg_bounds": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(i64), C.POINTER(i64)]),
+    "gan_jpeg_blocks": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, i64, vp, vp]),
+    "gan_jpeg_tables": (C.c_int, [vp, C.c_int, vp, vp, vp]),
+    "gan_jpeg_scan": (C.c_int, [vp, i64, C.c_int, C.c_int, C.c_int, vp, vp, i64, vp, vp]),
     "gan_spectral_norm_ws_floats": (C.c_int64, [C.c_int, C.c_int]),
     "gan_spectral_norm_fwd": (C.c_int, [vp, C.c_int, C.c_int, vp, vp, C.c_int, C.c_float, vp, vp, vp, vp]),
     "gan_spectral_norm_bwd": (C.c_int, [vp, vp, vp, vp, vp, C.c_int, C.c_int, vp, vp, vp]),

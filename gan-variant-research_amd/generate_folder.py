@@ -7,6 +7,7 @@ the output tree mirrors the input tree as JPEGs (quality 95, 4:4:4).  What diffe
 engine, and on the GPU the resize, the normalisation and the uint8 conversion run there as well (inference.stylize_images).
 Build-only flags: --ngf / --n-blocks (the reference reads the architecture from its own module), --fp32 (bf16 operands stand in for the
 reference's autocast by default), --graph (one hipGraph replay per batch shape), --host-io (resize and convert with PIL / torch on the host),
+--device-jpeg (the JPEG files are encoded on the device as well, byte-identical to PIL's), --io-threads N (PIL decodes / saves on a thread pool),
 --which G_A2B|G_B2A (a CycleGAN checkpoint of train_basic is recognised by its keys; this picks the generator, architecture read from the keys).
 """
 from __future__ import annotations
@@ -34,12 +35,21 @@ def parse_args(argv=None) -> argparse.Namespace:
     ap.add_argument("--graph", action="store_true", help="replay the generator pass as one hipGraph per batch shape (build-only flag)")
     ap.add_argument("--host-io", action="store_true", help="resize / normalise / convert on the host instead of the device (build-only flag)")
     ap.add_argument("--which", default="G_A2B", choices=["G_A2B", "G_B2A"], help="generator of a CycleGAN checkpoint (train_basic's ckpt_e*.pt) to run (build-only flag)")
-    return ap.parse_args(argv)
+    ap.add_argument("--device-jpeg", action="store_true", help="encode the JPEGs on the device, byte-identical to PIL's (build-only flag)")
+    ap.add_argument("--io-threads", type=int, default=1, help="threads for the PIL decodes (and the PIL saves without --device-jpeg), at most 16 (build-only flag)")
+    args = ap.parse_args(argv)
+    if args.device_jpeg and (args.host_io or args.device == "cpu"):
+        ap.error("--device-jpeg encodes what the device I/O path leaves on the GPU: not with --host-io or --device cpu")
+    if args.io_threads < 1:
+        ap.error("--io-threads must be at least 1")
+    return args
 
 
 def main(argv=None) -> int:
     args = parse_args(argv)
     if args.device == "cuda" and not torch.cuda.is_available():
+        if args.device_jpeg:
+            raise SystemExit("--device-jpeg needs the GPU: there is no host fallback for the device encoder")
         print("[WARN] CUDA not available. Falling back to CPU.")
         args.device = "cpu"
 
@@ -52,7 +62,8 @@ def main(argv=None) -> int:
           f"(size={args.size}, batch={args.batch}, device={args.device})")
     # the device input pipeline and the uint8 epilogue are HIP kernels: they run exactly when the generator runs on the HIP library
     n = I.stylize_folder(G, src_dir=args.photos, out_dir=args.out, device=args.device, img_size=args.size, batch=args.batch, limit=args.limit,
-                         device_io=args.device == "cuda" and not args.host_io)
+                         device_io=args.device == "cuda" and not args.host_io, device_jpeg=args.device_jpeg,
+                         io_threads=args.io_threads)
     print("Done.")
     return n
 

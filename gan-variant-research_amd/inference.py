@@ -4,8 +4,9 @@
 generate_folder.py:125-170 does; `stylize` is the tensor-level body of `stylize_folder` (:207-252): G(x) then
 clamp -> *0.5 + 0.5 -> *255 -> round -> uint8 (:183-185).  `stylize_hwc` is the same with the conversion and the HWC turn PIL needs
 fused into one kernel after the generator's last layer (gan_view_to_u8_hwc), `stylize_images` puts the device input pipeline with
-Pillow's BILINEAR taps (:175-180) in front of it.  JPEG / PNG decoding and JPEG encoding stay in PIL on the host; `stylize_folder`
-walks a PIL-readable folder, with the resize and both conversions on the host (the default) or on the device (`device_io=True`).
+Pillow's BILINEAR taps (:175-180) in front of it.  JPEG / PNG decoding stays in PIL on the host; JPEG encoding (:252) is PIL's by
+default and `JpegEncoder`'s on the device with `device_jpeg=True`, byte for byte the same files.  `stylize_folder` walks a
+PIL-readable folder, with the resize and both conversions on the host (the default) or on the device (`device_io=True`).
 The command line is generate_folder.py next to this file.
 """
 from __future__ import annotations
@@ -113,14 +114,105 @@ def stylize_images(G: ResNetGenerator, images: Sequence[torch.Tensor], img_size:
     return stylize_hwc(G, x)
 
 
+_JPEG_LUMA = (16, 11, 10, 16, 24, 40, 51, 61, 12, 12, 14, 19, 26, 58, 60, 55, 14, 13, 16, 24, 40, 57, 69, 56, 14, 17, 22, 29, 51, 87, 80, 62,
+              18, 22, 37, 56, 68, 109, 103, 77, 24, 35, 55, 64, 81, 104, 113, 92, 49, 64, 78, 87, 103, 121, 120, 101, 72, 92, 95, 98, 112, 100, 103, 99)
+_JPEG_CHROMA = (17, 18, 24, 47, 99, 99, 99, 99, 18, 21, 26, 66, 99, 99, 99, 99, 24, 26, 56, 99, 99, 99, 99, 99, 47, 66, 99, 99, 99, 99, 99, 99) + (99,) * 32
+_JPEG_ZIGZAG = (0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6, 7, 14, 21, 28,
+                35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63)
+
+
+def _segment(marker: int, body: bytes) -> bytes:
+    return bytes((0xFF, marker)) + (len(body) + 2).to_bytes(2, "big") + body
+
+
+class JpegEncoder:
+    """Baseline JPEG files from packed uint8 (B, H, W, 3) device batches, byte-identical to the reference's
+    pil.save(..., format="JPEG", quality=95, subsampling=0, optimize=True) (generate_folder.py:252).  Colour conversion, DCT,
+    quantisation, the optimal Huffman tables and the stuffed scan are made on the device (csrc/jpeg.hip); the host downloads B + 1
+    offsets, the tables and one contiguous block of scan bytes, and writes the headers around them.  Owns its buffers, like
+    dataio.InputPipeline; one encoder serves batches of up to `max_batch` images of one size."""
+
+    def __init__(self, device, max_batch: int, H: int, W: int, quality: int = 95, ops=None):
+        from . import autograd as AG
+        from ._lib import GanError
+        self.device, self.max_batch, self.H, self.W, self.quality = torch.device(device), int(max_batch), int(H), int(W), int(quality)
+        if not 1 <= self.quality <= 100:
+            raise ValueError(f"quality = {quality}: 1 .. 100")
+        if not (self.max_batch >= 1 and 1 <= self.H <= 65535 and 1 <= self.W <= 65535):
+            raise ValueError(f"JpegEncoder: max_batch = {max_batch}, H = {H}, W = {W}: max_batch >= 1 and 1 <= H, W <= 65535")
+        self.ops = AG._OPS_FACTORY(self.device) if ops is None else ops
+        if getattr(self.ops, "is_hip", False) and self.device.type != "cuda":
+            raise GanError("the MI355X path needs tensors on a GPU (there is no CPU fallback)")
+        ws_bytes, out_bytes = self.ops.jpeg_bounds(self.max_batch, self.H, self.W)
+        new = lambda shape, dt: torch.zeros(shape, dtype=dt, device=self.device)
+        self.rgb = new((self.max_batch, self.H, self.W, 3), torch.uint8)
+        self.ws, self.out = new(ws_bytes, torch.uint8), new(out_bytes, torch.uint8)
+        self.hist, self.codes = new((self.max_batch, 4, 256), torch.int32), new((self.max_batch, 4, 256), torch.int32)
+        self.dht, self.offsets = new((self.max_batch, 4, 272), torch.uint8), new(self.max_batch + 1, torch.int64)
+        self._programs = {}
+        s = 5000 // self.quality if self.quality < 50 else 200 - 2 * self.quality
+        head = b"\xff\xd8" + _segment(0xE0, b"JFIF\x00" + bytes((1, 1, 0, 0, 1, 0, 1, 0, 0)))
+        for i, base in enumerate((_JPEG_LUMA, _JPEG_CHROMA)):
+            q = [min(max((v * s + 50) // 100, 1), 255) for v in base]
+            head += _segment(0xDB, bytes([i]) + bytes(q[k] for k in _JPEG_ZIGZAG))
+        self._head = head + _segment(0xC0, bytes([8]) + self.H.to_bytes(2, "big") + self.W.to_bytes(2, "big") + bytes((3, 1, 0x11, 0, 2, 0x11, 1, 3, 0x11, 1)))
+        self._sos = _segment(0xDA, bytes((3, 1, 0x00, 2, 0x11, 3, 0x11, 0, 0x3F, 0)))
+
+    def _program(self, B: int):
+        prog = self._programs.get(B)
+        if prog is None:
+            o = self.ops
+            prog = self._programs[B] = [o.jpeg_blocks(self.rgb[:B], self.quality, self.ws, self.hist), o.jpeg_tables(self.hist, 4 * B, self.dht, self.codes),
+                                        o.jpeg_scan(self.ws, B, self.H, self.W, self.codes, self.out, self.offsets)]
+        return prog
+
+    @torch.inference_mode()
+    def encode(self, batch: torch.Tensor) -> list:
+        """(B, H, W, 3) uint8 on the encoder's device, B <= max_batch -> B complete JPEG files as bytes."""
+        B = int(batch.shape[0])
+        if batch.dtype != torch.uint8 or tuple(batch.shape[1:]) != (self.H, self.W, 3) or not 1 <= B <= self.max_batch or batch.device != self.rgb.device:
+            raise ValueError(f"JpegEncoder.encode: expected uint8 (1 .. {self.max_batch}, {self.H}, {self.W}, 3) on {self.rgb.device}, "
+                             f"got {batch.dtype} {tuple(batch.shape)} on {batch.device}")
+        self.rgb[:B].copy_(batch)
+        for op in self._program(B):
+            op()
+        off = self.offsets[:B + 1].cpu().tolist()
+        dht = self.dht[:B].cpu().numpy()
+        scan = self.out[:off[B]].cpu().numpy().tobytes()
+        files = []
+        for b in range(B):
+            tables = b""
+            for t, tc in enumerate((0x00, 0x10, 0x01, 0x11)):          # DC0, AC0, DC1, AC1
+                n = int(dht[b, t, :16].sum())
+                tables += _segment(0xC4, bytes([tc]) + dht[b, t, :16 + n].tobytes())
+            files.append(self._head + tables + self._sos + scan[off[b]:off[b + 1]] + b"\xff\xd9")
+        return files
+
+
+def _jpeg_encoder(G, device, batch: int, H: int, W: int) -> JpegEncoder:
+    """The encoder cached on the generator, like `_infer_pipe`."""
+    enc = getattr(G, "_jpeg_enc", None)
+    if enc is None or (enc.H, enc.W) != (H, W) or enc.device != device or enc.max_batch < batch:
+        enc = JpegEncoder(device, max(16, batch), H, W, quality=95)
+        object.__setattr__(G, "_jpeg_enc", enc)
+    return enc
+
+
 @torch.inference_mode()
 def stylize_folder(G, src_dir: str, out_dir: str, device: str = "cuda", img_size: int = 256, batch: int = 16, limit: Optional[int] = None,
-                   device_io: bool = False) -> int:
+                   device_io: bool = False, device_jpeg: bool = False, io_threads: int = 1) -> int:
     """generate_folder.py:207-252 with PIL doing what torchvision's Resize(BILINEAR) / ToTensor / Normalize / ToPILImage do there.
     device_io: PIL only decodes and encodes; each photo is uploaded as uint8 HWC, `stylize_images` resizes, normalises, runs the
-    generator and converts on the device, and one contiguous HWC download feeds PIL.  The files written are byte-identical."""
+    generator and converts on the device, and one contiguous HWC download feeds PIL.  The files written are byte-identical.
+    device_jpeg (needs device_io): the batch never comes back as pixels; `JpegEncoder` makes the files on the device and the host
+    writes their bytes.  io_threads > 1: the PIL decodes of a chunk (and, without device_jpeg, the PIL saves) run on a thread pool of
+    at most 16 workers, as dataio.ImageStore's does.  Same files either way."""
     import numpy as np
     from PIL import Image
+    if device_jpeg and not device_io:
+        raise ValueError("device_jpeg=True needs device_io=True: the encoder reads the uint8 batch the device epilogue leaves")
+    if io_threads < 1:
+        raise ValueError(f"io_threads = {io_threads}: at least 1")
     exts = {".jpg", ".jpeg", ".png", ".bmp", ".webp", ".tif", ".tiff"}
     src_root, out_root = Path(src_dir), Path(out_dir)
     paths = sorted(p for p in src_root.rglob("*") if p.suffix.lower() in exts)
@@ -129,17 +221,45 @@ def stylize_folder(G, src_dir: str, out_dir: str, device: str = "cuda", img_size
     if not paths:
         raise FileNotFoundError(f"No images found under: {src_dir}")
     out_root.mkdir(parents=True, exist_ok=True)
-    for i in range(0, len(paths), batch):
-        chunk = paths[i:i + batch]
-        if device_io:
-            imgs = [torch.from_numpy(np.array(Image.open(p).convert("RGB"))).to(device) for p in chunk]
-            y = stylize_images(G, imgs, img_size).cpu().numpy()
-        else:
-            arr = np.stack([np.asarray(Image.open(p).convert("RGB").resize((img_size, img_size), Image.BILINEAR), dtype=np.float32) for p in chunk])
-            x = torch.from_numpy(arr).permute(0, 3, 1, 2).div(255.0).sub(0.5).div(0.5).contiguous().to(device)
-            y = stylize(G, x).cpu().permute(0, 2, 3, 1).numpy()
-        for p, img in zip(chunk, y):
-            save = (out_root / p.relative_to(src_root)).with_suffix(".jpg")
-            save.parent.mkdir(parents=True, exist_ok=True)
-            Image.fromarray(img).save(save, format="JPEG", quality=95, subsampling=0, optimize=True)
+    pool = None
+    if io_threads > 1:
+        from concurrent.futures import ThreadPoolExecutor
+        pool = ThreadPoolExecutor(min(io_threads, 16))
+    each = (lambda fn, *its: list(pool.map(fn, *its))) if pool is not None else (lambda fn, *its: [fn(*a) for a in zip(*its)])
+
+    def decode(p):
+        return np.array(Image.open(p).convert("RGB"))
+
+    def decode_resized(p):
+        return np.asarray(Image.open(p).convert("RGB").resize((img_size, img_size), Image.BILINEAR), dtype=np.float32)
+
+    def target(p):
+        save = (out_root / p.relative_to(src_root)).with_suffix(".jpg")
+        save.parent.mkdir(parents=True, exist_ok=True)
+        return save
+
+    def save_pil(p, img):
+        Image.fromarray(img).save(target(p), format="JPEG", quality=95, subsampling=0, optimize=True)
+
+    def save_bytes(p, data):
+        target(p).write_bytes(data)
+
+    try:
+        for i in range(0, len(paths), batch):
+            chunk = paths[i:i + batch]
+            if device_io:
+                imgs = [torch.from_numpy(a).to(device) for a in each(decode, chunk)]
+                y = stylize_images(G, imgs, img_size)
+                if device_jpeg:
+                    each(save_bytes, chunk, _jpeg_encoder(G, y.device, len(chunk), img_size, img_size).encode(y))
+                    continue
+                y = y.cpu().numpy()
+            else:
+                arr = np.stack(each(decode_resized, chunk))
+                x = torch.from_numpy(arr).permute(0, 3, 1, 2).div(255.0).sub(0.5).div(0.5).contiguous().to(device)
+                y = stylize(G, x).cpu().permute(0, 2, 3, 1).numpy()
+            each(save_pil, chunk, y)
+    finally:
+        if pool is not None:
+            pool.shutdown()
     return len(paths)

@@ -544,6 +544,33 @@ class HipOps:
         assert dst.dtype == torch.uint8 and dst.is_contiguous() and tuple(dst.shape) == (src.B, src.H, src.W, Cr)
         return self._call("gan_view_to_u8_hwc", self._v(src), Cr, self._p(dst), self._s())
 
+    # ---- JPEG encoder (csrc/jpeg.hip; inference.JpegEncoder owns the buffers)
+    def jpeg_bounds(self, B, H, W):
+        """(workspace bytes, scan output bytes) for a batch of B images of H x W; refuses what the kernels refuse."""
+        ws, out = C.c_int64(0), C.c_int64(0)
+        _lib.check(self.lib.gan_jpeg_bounds(B, H, W, C.byref(ws), C.byref(out)), "gan_jpeg_bounds")
+        return int(ws.value), int(out.value)
+
+    def jpeg_blocks(self, rgb: torch.Tensor, quality, ws: torch.Tensor, hist: torch.Tensor) -> Op:
+        """Packed uint8 (B, H, W, 3) -> quantised zig-zag coefficients in ws, symbol histograms (B, 4, 256) in hist."""
+        B, H, W, _ = rgb.shape
+        assert rgb.dtype == torch.uint8 and rgb.is_contiguous() and rgb.shape[3] == 3 and ws.dtype == torch.uint8
+        assert hist.dtype == torch.int32 and hist.is_contiguous() and hist.numel() >= B * 1024
+        return self._call("gan_jpeg_blocks", self._p(rgb), B, H, W, int(quality), self._p(ws), ws.numel(), self._p(hist), self._s())
+
+    def jpeg_tables(self, hist: torch.Tensor, n, dht: torch.Tensor, codes: torch.Tensor) -> Op:
+        """n histograms of 256 counts -> optimal tables: dht (n, 272) uint8 = 16 counts + symbols, codes (n, 256) int32 = length << 16 | code."""
+        assert hist.dtype == torch.int32 and dht.dtype == torch.uint8 and codes.dtype == torch.int32
+        assert hist.is_contiguous() and dht.is_contiguous() and codes.is_contiguous()
+        assert hist.numel() >= n * 256 and dht.numel() >= n * 272 and codes.numel() >= n * 256
+        return self._call("gan_jpeg_tables", self._p(hist), int(n), self._p(dht), self._p(codes), self._s())
+
+    def jpeg_scan(self, ws: torch.Tensor, B, H, W, codes: torch.Tensor, out: torch.Tensor, offsets: torch.Tensor) -> Op:
+        """The stuffed, padded scans of the B images of ws back to back in out; offsets (B + 1) int64: image b is out[offsets[b]:offsets[b + 1]]."""
+        assert ws.dtype == torch.uint8 and out.dtype == torch.uint8 and codes.dtype == torch.int32 and offsets.dtype == torch.int64
+        assert codes.numel() >= B * 1024 and offsets.numel() >= B + 1 and out.is_contiguous() and offsets.is_contiguous()
+        return self._call("gan_jpeg_scan", self._p(ws), ws.numel(), B, H, W, self._p(codes), self._p(out), out.numel(), self._p(offsets), self._s())
+
     def view_copy(self, src: View, dst: View, halo_mode) -> Op:
         return self._call("gan_view_copy", self._v(src), self._v(dst), halo_mode, self._s())
 

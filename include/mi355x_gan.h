@@ -442,6 +442,44 @@ int gan_input_pipeline(const gan_input_job* jobs_dev, const gan_input_job* jobs_
 int gan_input_pipeline_filter(const gan_input_job* jobs_dev, const gan_input_job* jobs_host, int B, const int32_t* tables_dev, int S,
                               int filter, uint8_t* tmp, int tmp_rows, uint8_t* img, int32_t* mean_ws, float* out, void* stream);
 
+/* ---- Baseline JPEG encoder on the device: the file the reference writes with pil.save(..., format="JPEG", quality=95, subsampling=0,
+ *      optimize=True) (GAN_Variant1/generate_folder.py:252), byte for byte -- libjpeg's 8-bit JDCT_ISLOW path, 4:4:4, one interleaved
+ *      scan, optimal Huffman tables, no restart markers.  Integer arithmetic only; histogram adds and the ORs that pack the stream are
+ *      integer atomics, so repeated calls give identical bytes.  The caller writes the header (SOI, JFIF APP0, two DQT, SOF0 with the
+ *      true H and W, four DHT in the order DC0 AC0 DC1 AC1, SOS) from the tables these entries return, then the scan bytes, then EOI.
+ *      Blocks are in scan order: MCU-major (row-major 8x8 tiles), Y then Cb then Cr; nblk = 3 ceil(H/8) ceil(W/8).
+ *      Refused with a message, before any launch: a NULL pointer, B, H or W outside 1 .. 65535, quality outside 1 .. 100, an image of
+ *      more than 2^32 / 1728 blocks (bit offsets inside one image are 32-bit; 4096 x 4096 passes), B nblk >= 2^28, a workspace or an
+ *      output buffer smaller than gan_jpeg_bounds asks, a workspace that is not 16-byte aligned. */
+/* Host only: bytes of workspace and of scan output that (B, H, W) needs.  out_bytes = 2 B nblk 216: a block codes to at most
+ * 16 + 11 + 63 (16 + 10) = 1665 <= 1728 bits, and stuffing can at most double a stream. */
+int gan_jpeg_bounds(int B, int H, int W, int64_t* ws_bytes, int64_t* out_bytes);
+/* rgb: packed uint8 [B][H][W][3] (what gan_view_to_u8_hwc leaves).  Two launches.
+ *   colour (jccolor.c):  Y = (19595 R + 38470 G + 7471 B + 32768) >> 16,  Cb = (-11059 R - 21709 G + 32768 B + (128 << 16) + 32767) >> 16,
+ *     Cr = (32768 R - 27439 G - 5329 B + (128 << 16) + 32767) >> 16, each minus 128; the last column / row is replicated to a multiple of 8.
+ *   DCT (jfdctint.c, CONST_BITS 13, PASS1_BITS 2): rows, outputs 0/4 << 2, the others DESCALE(., 11); columns, outputs 0/4 DESCALE(., 2),
+ *     the others DESCALE(., 15); DESCALE(x, n) = (x + (1 << (n - 1))) >> n, arithmetic shift.
+ *   quantisation: q[k] = clamp((base[k] s + 50) / 100, 1, 255), s = quality < 50 ? 5000 / quality : 200 - 2 quality, base = the standard
+ *     luminance (Y) / chrominance (Cb, Cr) table; coefficient = sign(c) ((|c| + 4 q) / (8 q)); stored in zig-zag order in the workspace.
+ *   symbols (jchuff.c): DC = bit length of the difference to the same component's block of the previous MCU (0 at the start); AC =
+ *     run << 4 | bit length, 0xF0 per 16 zeros, 0x00 when the block ends in zeros.
+ * hist: uint32 [B][4][256], overwritten: symbol counts of the tables DC-Y, AC-Y, DC-C, AC-C of every image. */
+int gan_jpeg_blocks(const uint8_t* rgb, int B, int H, int W, int quality, void* ws, int64_t ws_bytes, uint32_t* hist, void* stream);
+/* jpeg_gen_optimal_table for n histograms (uint32 [n][256], each below 10^9 in sum), one wave each: a 257th pseudo-symbol of frequency 1;
+ * merge the two least frequent non-zero entries until one is left, the larger index first on ties; lengths above 16 folded down with
+ * libjpeg's bits[i] -= 2, bits[i-1]++, bits[j+1] += 2, bits[j]-- loop (lengths above 32, which libjpeg refuses, are counted as 32); the
+ * pseudo-symbol leaves the longest length; symbols ordered by (length before folding, value); canonical codes.
+ * dht: uint8 [n][272] = the DHT segment's 16 counts, then its symbols (zero past the last); codes: uint32 [n][256] = length << 16 | code,
+ * 0 for a symbol without a code. */
+int gan_jpeg_tables(const uint32_t* hist, int n, uint8_t* dht, uint32_t* codes, void* stream);
+/* The entropy-coded scan of the coefficients gan_jpeg_blocks left in ws, with codes uint32 [B][4][256] from gan_jpeg_tables.  Six
+ * launches: bits per block; exclusive scan per image; every block ORs its bits into the zeroed stream at its offset (most significant
+ * bit first), the last byte padded with 1-bits; 0xFF bytes counted, scanned and scattered with a 0x00 after each (the padded last
+ * byte included).  out: the streams of images 0 .. B-1 back to back; offsets: int64 [B + 1] on the device, image b is
+ * out[offsets[b] .. offsets[b + 1]).  Nothing past out[out_bytes) is written. */
+int gan_jpeg_scan(void* ws, int64_t ws_bytes, int B, int H, int W, const uint32_t* codes, uint8_t* out, int64_t out_bytes, int64_t* offsets,
+                  void* stream);
+
 /* ---- losses.  Every loss writes its value to *loss (device fp32, overwritten) and the gradient wrt its input.
  *      hinge: adv_hinge.py:6-62 (mode 0: mean relu(1-x), 1: mean relu(1+x), 2: -mean x), scaled by `scale`;
  *      lsgan/bce: Basic_GAN/src/losses.py:5-22 (mode 3: mse vs target, 4: bce-with-logits vs target in {0,1});

@@ -2,11 +2,13 @@
 
 (a) output path: inference.stylize + download + host permute to HWC   vs   inference.stylize_hwc + one contiguous download
 (b) folder path: inference.stylize_folder on 64 seeded PNGs of mixed sizes, host I/O vs device I/O (images/s, decode and JPEG encode included)
+(c) JPEG encode (--jpeg): the folder path at batch 16 on two folders (the mixed PNGs; 256 JPEGs of 256 x 256), device I/O with serial PIL
+    against PIL on a thread pool (io_threads 4, 16) against the device encoder (device_jpeg, io_threads 1, 4, 16); same files every mode
 
 Every shape is warmed up; the two paths are then timed in rotation for --rounds rounds (a host clock around work that ends in a device
 synchronise: each call ends in a download); the median round and the spread (min .. max) are reported.  The outputs of the two paths
 are compared before anything is timed.
-usage: bench_stylize.py [--size 256] [--batches 1,4,16] [--calls 40] [--rounds 5] [--photos 64] [--out FILE]
+usage: bench_stylize.py [--size 256] [--batches 1,4,16] [--calls 40] [--rounds 5] [--photos 64] [--out FILE] [--jpeg] [--only-jpeg]
 """
 import argparse
 import os
@@ -36,6 +38,54 @@ def make_folder(root: Path, n: int, seed: int = 0):
         Image.fromarray(img).save(root / ("sub" if i % 4 == 0 else ".") / f"p{i:03d}.png")
 
 
+def make_jpeg_folder(root: Path, n: int, size: int = 256, seed: int = 1):
+    """n JPEGs of size x size under root: the realistic input (the reference's photo_jpg folder)."""
+    from PIL import Image
+    rng = np.random.default_rng(seed)
+    root.mkdir(parents=True, exist_ok=True)
+    yy, xx = np.mgrid[0:size, 0:size]
+    for i in range(n):
+        base = np.stack([127 + 120 * np.sin(yy / (11.0 + i % 7) + c + i) * np.cos(xx / (19.0 + i % 5) - c) for c in range(3)], -1)
+        img = np.clip(base + rng.integers(-20, 21, (size, size, 3)), 0, 255).astype(np.uint8)
+        Image.fromarray(img).save(root / f"q{i:03d}.jpg", quality=90)
+
+
+JPEG_MODES = (("a  device_io, serial PIL", dict()), ("b  PIL pool, io_threads 4", dict(io_threads=4)), ("b  PIL pool, io_threads 16", dict(io_threads=16)),
+              ("c  device_jpeg, io_threads 1", dict(device_jpeg=True)), ("c  device_jpeg, io_threads 4", dict(device_jpeg=True, io_threads=4)),
+              ("c  device_jpeg, io_threads 16", dict(device_jpeg=True, io_threads=16)))
+
+
+def jpeg_section(G, dev, S, rounds, photos, tmp: Path):
+    """(c): every mode writes the same files (checked first), then the modes run in rotation; images/s, median [min .. max]."""
+    lines = [f"# (c) images/s over one pass of a folder, batch 16, {S}x{S}, decode and JPEG encode included; median of {rounds} alternating rounds [min .. max]"]
+    make_jpeg_folder(tmp / "jpegs", 256, S)
+    for label, src, n in ((f"{photos} PNGs of mixed sizes", tmp / "photos", photos), (f"256 JPEGs of {S}x{S}", tmp / "jpegs", 256)):
+        def mode(i, kw):
+            def run():
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                assert I.stylize_folder(G, str(src), str(tmp / f"c_{src.name}_{i}"), device=str(dev), img_size=S, batch=16, device_io=True, **kw) == n
+                torch.cuda.synchronize()
+                return n / (time.perf_counter() - t0)
+            return run
+        paths = {name: mode(i, kw) for i, (name, kw) in enumerate(JPEG_MODES)}
+        for fn in paths.values():
+            fn()
+        outs = [{p.name: p.read_bytes() for p in (tmp / f"c_{src.name}_{i}").rglob("*.jpg")} for i in range(len(JPEG_MODES))]
+        assert len(outs[0]) == n and all(o == outs[0] for o in outs), "the modes wrote different files"
+        times = rotate(paths, rounds)
+        lines.append(f"# {label}")
+        for name, v in times.items():
+            lines.append(f"(c) {name:30s} {statistics.median(v):8.1f} images/s [{min(v):8.1f} .. {max(v):8.1f}]")
+        for th in (4, 16):
+            b, c = times[f"b  PIL pool, io_threads {th}"], times[f"c  device_jpeg, io_threads {th}"]
+            verdict = "beats" if min(c) > max(b) else "does not beat"
+            lines.append(f"(c) io_threads {th:2d}: device_jpeg {verdict} the PIL pool beyond both spreads (min c {min(c):.1f} vs max b {max(b):.1f})")
+        for ln in lines[-(len(JPEG_MODES) + 3):]:
+            print(ln, flush=True)
+    return lines
+
+
 def rotate(paths, rounds):
     """paths: name -> callable returning the seconds one round of it took.  Runs them in rotation; name -> list of round times."""
     times = {k: [] for k in paths}
@@ -62,6 +112,8 @@ def main():
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--photos", type=int, default=64)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--jpeg", action="store_true", help="also run section (c)")
+    ap.add_argument("--only-jpeg", action="store_true", help="run section (c) alone")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "bench_stylize.py measures on the GPU"
     dev, S = torch.device("cuda:0"), a.size
@@ -70,12 +122,15 @@ def main():
     for p in G.parameters():
         p.requires_grad_(False)
     G.compute_dtype = BF16
-    lines = [f"# tools/bench_stylize.py --size {S} --batches {a.batches} --calls {a.calls} --rounds {a.rounds} --photos {a.photos}",
-             f"# generator ngf 64, 9 blocks, bf16 operands, eager launches; median of {a.rounds} alternating rounds [min .. max]",
-             f"# (a) ms per call of {a.calls} consecutive calls, each ending in the download of the uint8 HWC batch to the host"]
+    lines = [f"# tools/bench_stylize.py --size {S} --batches {a.batches} --calls {a.calls} --rounds {a.rounds} --photos {a.photos}"
+             + (" --only-jpeg" if a.only_jpeg else " --jpeg" if a.jpeg else ""),
+             f"# generator ngf 64, 9 blocks, bf16 operands, eager launches; median of {a.rounds} alternating rounds [min .. max]"]
+    if not a.only_jpeg:
+        lines.append(f"# (a) ms per call of {a.calls} consecutive calls, each ending in the download of the uint8 HWC batch to the host")
     old_out = lambda x: I.stylize(G, x).cpu().permute(0, 2, 3, 1).contiguous()
     new_out = lambda x: I.stylize_hwc(G, x).cpu()
-    for B in (int(v) for v in a.batches.split(",")):
+    batches = [] if a.only_jpeg else [int(v) for v in a.batches.split(",")]
+    for B in batches:
         x = (torch.rand(B, 3, S, S) * 2 - 1).to(dev)
         for _ in range(3):
             yo, yn = old_out(x), new_out(x)
@@ -92,11 +147,12 @@ def main():
             return run
         lines.append(line(f"(a) B={B:2d} {S}x{S}", "ms", rotate({"old": timed(old_out), "new": timed(new_out)}, a.rounds), True))
         print(lines[-1], flush=True)
-    lines.append(f"# (b) images/s over one pass of a folder of {a.photos} PNGs (120 .. 640 pixels a side), PNG decode and JPEG encode included")
+    if not a.only_jpeg:
+        lines.append(f"# (b) images/s over one pass of a folder of {a.photos} PNGs (120 .. 640 pixels a side), PNG decode and JPEG encode included")
     with tempfile.TemporaryDirectory() as tmp:
         tmp = Path(tmp)
         make_folder(tmp / "photos", a.photos)
-        for B in (int(v) for v in a.batches.split(",")):
+        for B in batches:
             def folder(device_io, out):
                 def run():
                     torch.cuda.synchronize()
@@ -113,6 +169,8 @@ def main():
             assert len(ho) == a.photos and ho == do, "the two folder paths wrote different files"
             lines.append(line(f"(b) batch={B:2d} {S}x{S}", "images/s", rotate(paths, a.rounds), False))
             print(lines[-1], flush=True)
+        if a.jpeg or a.only_jpeg:
+            lines += jpeg_section(G, dev, S, a.rounds, a.photos, tmp)
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
         with open(a.out, "w") as f:
