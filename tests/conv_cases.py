@@ -1,8 +1,8 @@
 """TEST INFRASTRUCTURE: cases, derived bounds and assertions for the convolution launches behind gan_conv_igemm (csrc/conv_igemm.hip,
 conv_patch.hip, conv_win7.hip), written against an op layer: tests/test_conv_family_cpu.py runs them on the emulator,
 tests/test_conv_family_gpu.py on HipOps, with the same shapes and the same assertions.  The float64 statements and the bounds are in
-tests/conv_ref64.py; the weight gradient, its reduction and the bias gradient are not held here (a `Spec` names the direction in `op`,
-and `run` dispatches on it: a further direction is one more branch of `run` and of `reference`).
+tests/conv_ref64.py; the weight gradient, its reduction and the bias gradient are held by the family of their own in tests/wgrad_cases.py
+(tests/test_wgrad_family_cpu.py, tests/test_wgrad_family_gpu.py).  A `Spec` names the direction in `op`, and `run` dispatches on it.
 
 A `Spec` is one planned request on a ConvLayer (forward or input gradient, with its epilogue); `run` plans it on a recording op layer,
 fills every output, partial buffer and guard zone with a sentinel (the views are slices of larger tensors, 128 / 256 bytes in), launches
