@@ -52,6 +52,19 @@ class GanPackDesc(C.Structure):
                 ("swap", i32), ("I2", i32), ("KK", i32), ("layout", i32), ("first_block", i32), ("nblocks", i32), ("scale", vp)]
 
 
+class GanJpegdecImage(C.Structure):
+    _fields_ = [("ncomp", i32), ("H", i32), ("W", i32), ("hmax", i32), ("vmax", i32), ("mcux", i32), ("mcuy", i32), ("seg_first", i32), ("seg_count", i32),
+                ("dc_tab", i32 * 3), ("ac_tab", i32 * 3), ("q_tab", i32 * 3), ("reserved", i32 * 2), ("coef_off", i64), ("plane_off", i64), ("out_off", i64)]
+
+
+class GanJpegdecSegment(C.Structure):
+    _fields_ = [("image", i32), ("mcu_first", i32), ("mcu_count", i32), ("byte_begin", i32), ("byte_end", i32)]
+
+
+JPEGDEC_ERR = {1: "no Huffman code", 2: "run past coefficient 63", 4: "bits beyond the segment", 8: "DC outside int16", 16: "bytes left over",
+               32: "wrong RSTn", 64: "marker inside a segment", 128: "IDCT range"}
+
+
 class GanSnDesc(C.Structure):
     _fields_ = [("W", vp), ("u", vp), ("v", vp), ("sigma", vp), ("u_snap", vp), ("v_snap", vp), ("G", vp), ("dW", vp), ("ws", vp),
                 ("h", i32), ("w", i32), ("first_block", i32), ("nblocks", i32)]
@@ -125,6 +138,12 @@ PROTOTYPES = {
     "gan_jpeg_blocks": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, i64, vp, vp]),
     "gan_jpeg_tables": (C.c_int, [vp, C.c_int, vp, vp, vp]),
     "gan_jpeg_scan": (C.c_int, [vp, i64, C.c_int, C.c_int, C.c_int, vp, vp, i64, vp, vp]),
+    "gan_jpegdec_block_offsets": (C.c_int, [C.c_int, C.c_int, C.POINTER(i64)]),
+    "gan_jpegdec_bounds": (C.c_int, [vp, C.c_int, C.POINTER(i64)]),
+    "gan_jpegdec_tables": (C.c_int, [vp, vp, i64, C.c_int, C.c_int, vp, i64, vp]),
+    "gan_jpegdec_entropy": (C.c_int, [vp, vp, i64, C.c_int, C.c_int, vp, i64, vp]),
+    "gan_jpegdec_idct": (C.c_int, [vp, vp, i64, C.c_int, C.c_int, vp, i64, vp]),
+    "gan_jpegdec_pixels": (C.c_int, [vp, vp, i64, C.c_int, C.c_int, vp, i64, vp, i64, vp, vp]),
     "gan_spectral_norm_ws_floats": (C.c_int64, [C.c_int, C.c_int]),
     "gan_spectral_norm_fwd": (C.c_int, [vp, C.c_int, C.c_int, vp, vp, C.c_int, C.c_float, vp, vp, vp, vp]),
     "gan_spectral_norm_bwd": (C.c_int, [vp, vp, vp, vp, vp, C.c_int, C.c_int, vp, vp, vp]),

@@ -248,6 +248,8 @@ def basic_image_tf(load_size: int, crop_size: int, train: bool, device="cuda", *
 DEFAULT_CACHE_GB = 8            # mi355x.dataset_cache_gb: the Kaggle folders of both reference configs decode to 1.44 GB
 ARENA_ALIGN = 256               # every image starts at a multiple of this, as separate tensors from the caching allocator did
 STAGE_BYTES = 64 << 20          # pinned staging buffer of one upload chunk (two of them, used in turn)
+DECODE_CHUNK = 256              # files per JpegDecoder.decode call: the entropy decode is one lane per restart segment, so its
+                                # throughput comes from the number of files in flight
 
 
 def _decode(path) -> np.ndarray:
@@ -270,6 +272,240 @@ def _header_size(path) -> Tuple[int, int]:
     return int(h), int(w)
 
 
+# ------------------------------------------------------------------------------------------------ baseline JPEGs decoded on the device
+_JPEG_ZIGZAG = (0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6, 7, 14, 21, 28,
+                35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63)
+
+
+def parse_jpeg(data: bytes) -> Optional[Dict]:
+    """The plan of a file the device decoder takes, or None ("not mine": Pillow decodes it).  Accepted: SOF0, 8-bit samples, 8-bit
+    quantisation tables, one interleaved scan of all components with Ss = 0, Se = 63, Ah = Al = 0; one component sampled 1x1, or
+    components 1, 2, 3 with chroma 1x1 and luma 1x1, 2x1 or 2x2; no Adobe APP14; DHT counts that sum to at most 256 and do not
+    over-subscribe the code space; an EOI after the scan, with nothing but RSTn markers and stuffed 0xFF bytes before it, and as many
+    RSTn as the restart interval asks.  Anything else -- progressive, arithmetic, 12-bit, CMYK, 4:1:1 / 4:4:0, several scans, DNL, fill
+    bytes, an unknown marker, a truncated file, another format -- is None."""
+    n = len(data)
+    if n < 4 or data[0] != 0xFF or data[1] != 0xD8:
+        return None
+    pos, qt, dht, sof, ri = 2, {}, {}, None, 0
+    while True:
+        if pos + 4 > n or data[pos] != 0xFF:
+            return None
+        m = data[pos + 1]
+        L = (data[pos + 2] << 8) | data[pos + 3]
+        if L < 2 or pos + 2 + L > n:
+            return None
+        body = data[pos + 4:pos + 2 + L]
+        if m == 0xDB:
+            while body:
+                if body[0] >> 4 != 0 or (body[0] & 15) > 3 or len(body) < 65:
+                    return None
+                q = np.zeros(64, np.uint16)
+                q[list(_JPEG_ZIGZAG)] = np.frombuffer(body[1:65], np.uint8)
+                qt[body[0] & 15] = q
+                body = body[65:]
+        elif m == 0xC4:
+            while body:
+                if len(body) < 17 or body[0] >> 4 > 1 or (body[0] & 15) > 1:
+                    return None
+                counts = body[1:17]
+                total, code = sum(counts), 0
+                for l in range(16):
+                    code += counts[l]
+                    if code > (1 << (l + 1)):
+                        return None
+                    code <<= 1
+                if total > 256 or len(body) < 17 + total:
+                    return None
+                dht[(body[0] >> 4) * 2 + (body[0] & 15)] = body[1:17 + total]
+                body = body[17 + total:]
+        elif m == 0xC0:
+            if sof is not None or len(body) < 6 or body[0] != 8 or len(body) != 6 + 3 * body[5]:
+                return None
+            sof = ((body[1] << 8) | body[2], (body[3] << 8) | body[4], [(body[6 + 3 * c], body[7 + 3 * c] >> 4, body[7 + 3 * c] & 15, body[8 + 3 * c]) for c in range(body[5])])
+        elif m == 0xDD:
+            if L != 4:
+                return None
+            ri = (body[0] << 8) | body[1]
+        elif m == 0xEE:
+            if body[:5] == b"Adobe":
+                return None
+        elif m == 0xDA:
+            break
+        elif not (0xE0 <= m <= 0xEF or m == 0xFE):
+            return None
+        pos += 2 + L
+    if sof is None:
+        return None
+    H, W, comps = sof
+    if H < 1 or W < 1 or len(comps) not in (1, 3) or len(body) != 4 + 2 * len(comps) or body[0] != len(comps):
+        return None
+    if tuple(body[-3:]) != (0, 63, 0):
+        return None
+    if len(comps) == 1:
+        if comps[0][1:3] != (1, 1):
+            return None
+        hmax = vmax = 1
+    else:
+        if tuple(c[0] for c in comps) != (1, 2, 3) or comps[1][1:3] != (1, 1) or comps[2][1:3] != (1, 1) or comps[0][1:3] not in ((1, 1), (2, 1), (2, 2)):
+            return None
+        hmax, vmax = comps[0][1:3]
+    dc_tab, ac_tab, q_tab = [0, 0, 0], [2, 2, 2], [0, 0, 0]
+    for c, (cid, _, _, tq) in enumerate(comps):
+        sel, tabs = body[1 + 2 * c], body[2 + 2 * c]
+        td, ta = tabs >> 4, tabs & 15
+        if sel != cid or td > 1 or ta > 1 or td not in dht or 2 + ta not in dht or tq not in qt:
+            return None
+        dc_tab[c], ac_tab[c], q_tab[c] = td, 2 + ta, tq
+    sb = pos + 2 + L
+    arr = np.frombuffer(data, np.uint8)
+    ff = np.flatnonzero(arr[sb:n - 1] == 0xFF) + sb          # one vectorised search: stuffed bytes, RSTn and the end of the scan
+    nxt = arr[ff + 1]
+    mpos, mk = ff[nxt != 0], nxt[nxt != 0]
+    other = np.flatnonzero((mk & 0xF8) != 0xD0)
+    if other.size == 0 or mk[other[0]] != 0xD9:
+        return None
+    e = int(other[0])
+    rst, end = mpos[:e], int(mpos[e])
+    mcux, mcuy = -(-W // (8 * hmax)), -(-H // (8 * vmax))
+    per = ri if ri else mcux * mcuy
+    nseg = -(-mcux * mcuy // per)
+    if rst.size != nseg - 1:
+        return None
+    begins = np.concatenate([[sb], rst + 2]).astype(np.int64)
+    ends = np.concatenate([rst, [end]]).astype(np.int64)
+    return {"H": H, "W": W, "ncomp": len(comps), "hmax": hmax, "vmax": vmax, "mcux": mcux, "mcuy": mcuy, "qt": qt, "dht": dht,
+            "dc_tab": dc_tab, "ac_tab": ac_tab, "q_tab": q_tab, "scan": (sb, end), "seg_begin": begins, "seg_end": ends, "per": per, "data": data}
+
+
+class JpegDecoder:
+    """Baseline JPEG files -> packed uint8 (H, W, 3) tensors on `device`, pixel-identical to `_decode` (Pillow) for every source.  The
+    files `parse` accepts are decoded by csrc/jpegdec.hip: their descriptors, tables and scan bytes go up in one copy from one pinned
+    staging buffer, four launches decode any number of files together, and the host reads one error word per file.  Every other
+    source, and every file the kernels flagged, goes through `_decode` -- which returns Pillow's pixels or raises its OSError, as
+    without the decoder.  Owns and grows its buffers, like InputPipeline.  `stats` counts which way the sources went."""
+
+    def __init__(self, device, ops=None):
+        from . import autograd as AG
+        self.device = normalize_device(device)
+        self.ops = AG._OPS_FACTORY(self.device) if ops is None else ops
+        if getattr(self.ops, "is_hip", False) and self.device.type != "cuda":
+            raise GanError("the MI355X path needs tensors on a GPU (there is no CPU fallback)")
+        self.stats = {"device": 0, "unsupported": 0, "flagged": 0}
+        self.last_errors: Dict[int, int] = {}          # source index -> error word, of the last call
+        self.last_block = None
+        self._host = self._dev = self._ws = self._err = None
+
+    @staticmethod
+    def parse(data: bytes) -> Optional[Dict]:
+        return parse_jpeg(data)
+
+    def _grow(self, name: str, nbytes: int, dtype=torch.uint8, host=False):
+        t = getattr(self, name)
+        if t is None or t.numel() < nbytes:
+            n = max(int(nbytes * 1.5), 1 << 16)
+            t = torch.zeros(n, dtype=dtype, pin_memory=True) if host and self.device.type == "cuda" else torch.zeros(n, dtype=dtype, device="cpu" if host else self.device)
+            setattr(self, name, t)
+        return t
+
+    def _pack(self, plans: Sequence[Dict], out_offsets: Sequence[int]):
+        """The upload block of `plans` in the staging buffer -> (block bytes, images, segments, workspace bytes)."""
+        n = len(plans)
+        imgs = (_lib.GanJpegdecImage * n)()
+        nseg = sum(len(p["seg_begin"]) for p in plans)
+        o_seg, o_dht, o_qt, o_scan = self.ops.jpegdec_block_offsets(n, nseg)
+        total = o_scan + sum(-(-(p["scan"][1] - p["scan"][0]) // 16) * 16 for p in plans)
+        segs = np.zeros((nseg, 5), np.int32)
+        host = self._grow("_host", total, host=True).numpy()
+        host[o_dht:o_scan] = 0
+        s0, at = 0, o_scan
+        for i, (p, im) in enumerate(zip(plans, imgs)):
+            k = len(p["seg_begin"])
+            im.ncomp, im.H, im.W, im.hmax, im.vmax, im.mcux, im.mcuy, im.seg_first, im.seg_count = p["ncomp"], p["H"], p["W"], p["hmax"], p["vmax"], p["mcux"], p["mcuy"], s0, k
+            for c in range(3):
+                im.dc_tab[c], im.ac_tab[c], im.q_tab[c] = p["dc_tab"][c], p["ac_tab"][c], p["q_tab"][c]
+            im.out_off = int(out_offsets[i])
+            sb, se = p["scan"]
+            shift = at - sb
+            segs[s0:s0 + k, 0] = i
+            segs[s0:s0 + k, 1] = np.arange(k) * p["per"]
+            segs[s0:s0 + k, 2] = np.minimum(p["per"], p["mcux"] * p["mcuy"] - segs[s0:s0 + k, 1])
+            segs[s0:s0 + k, 3], segs[s0:s0 + k, 4] = p["seg_begin"] + shift, p["seg_end"] + shift
+            host[at:at + se - sb] = np.frombuffer(p["data"], np.uint8, se - sb, sb)
+            for t, raw in p["dht"].items():
+                host[o_dht + (4 * i + t) * 272:o_dht + (4 * i + t) * 272 + len(raw)] = np.frombuffer(raw, np.uint8)
+            for t, q in p["qt"].items():
+                host[o_qt + (4 * i + t) * 128:o_qt + (4 * i + t + 1) * 128].view(np.uint16)[:] = q
+            s0, at = s0 + k, at + -(-(se - sb) // 16) * 16
+        ws_bytes = self.ops.jpegdec_bounds(imgs)
+        host[:o_seg] = np.frombuffer(imgs, np.uint8)
+        host[o_seg:o_dht].view(np.int32)[:] = segs.reshape(-1)
+        return total, n, nseg, ws_bytes
+
+    def load(self, source):
+        """(bytes, plan or None) of a path or of bytes: the part of `decode` that a thread pool can do ahead."""
+        data = bytes(source) if isinstance(source, (bytes, bytearray, memoryview)) else open(os.fspath(source), "rb").read()
+        return data, parse_jpeg(data)
+
+    @torch.inference_mode()
+    def decode(self, sources: Sequence, out: Optional[torch.Tensor] = None, offsets: Optional[Sequence[int]] = None, each=None) -> List[torch.Tensor]:
+        """sources: paths or bytes, any number.  out / offsets: a flat uint8 tensor on the decoder's device and the byte offset of every
+        image in it (the store's arena); None: one new buffer, every image at a multiple of ARENA_ALIGN.  each: a `map` for the host work
+        per file (reading and parsing; Pillow's decode of what is not the device's), e.g. a thread pool's.  Returns (H, W, 3) views."""
+        import io
+        each = map if each is None else each
+        sources = list(sources)
+        is_bytes = lambda s: isinstance(s, (bytes, bytearray, memoryview))
+        host_decode = lambda i: _decode(io.BytesIO(bytes(sources[i])) if is_bytes(sources[i]) else sources[i])
+        loaded = list(each(self.load, sources))
+        plans = [p for _, p in loaded]
+        mine = [i for i, p in enumerate(plans) if p is not None]
+        rest = [i for i, p in enumerate(plans) if p is None]
+        arrs = dict(zip(rest, each(host_decode, rest)))
+        shapes = [(plans[i]["H"], plans[i]["W"]) if plans[i] is not None else arrs[i].shape[:2] for i in range(len(sources))]
+        if out is None:
+            offsets, end = [], 0
+            for h, w in shapes:
+                offsets.append(end)
+                end += -(-(h * w * 3) // ARENA_ALIGN) * ARENA_ALIGN
+            out = torch.empty(max(end, 1), dtype=torch.uint8, device=self.device)
+        elif offsets is None or len(offsets) != len(sources) or out.dtype != torch.uint8 or out.dim() != 1 or not out.is_contiguous() or out.device != self.device:
+            raise GanError(f"JpegDecoder.decode: `out` must be a flat contiguous uint8 tensor on {self.device} with one offset per source")
+        self.last_errors = {}
+        if mine:
+            total, n, nseg, ws_bytes = self._pack([plans[i] for i in mine], [offsets[i] for i in mine])
+            self.last_block = (total, n, nseg)                   # the staging buffer and the workspace still hold this call (tests locate a difference there)
+            ws, err = self._grow("_ws", ws_bytes), self._grow("_err", n, torch.int32)
+            if self.device.type == "cuda":
+                dev = self._grow("_dev", total)
+                dev[:total].copy_(self._host[:total], non_blocking=True)
+            else:
+                dev = self._host
+            o = self.ops
+            try:
+                o.jpegdec_tables(dev, self._host, total, n, nseg, ws)
+                o.jpegdec_entropy(dev, self._host, total, n, nseg, ws)
+                o.jpegdec_idct(dev, self._host, total, n, nseg, ws)
+                o.jpegdec_pixels(dev, self._host, total, n, nseg, ws, out, err)
+            except GanError:
+                if self.device.type == "cuda":
+                    torch.cuda.current_stream(self.device).synchronize()      # the upload has left the staging buffer before it is reused
+                raise
+            words = err[:n].cpu().tolist()                       # one download per call; it also orders the staging buffer's reuse
+            self.last_errors = {i: int(w) for i, w in zip(mine, words) if w}
+            flagged = sorted(self.last_errors)
+            for i, a in zip(flagged, each(host_decode, flagged)):      # Pillow's pixels, or its OSError
+                if a.shape[:2] != shapes[i]:
+                    raise OSError(f"image {sources[i]!r} decoded to {a.shape[:2]}, its header said {shapes[i]}")
+                arrs[i] = a
+        for i, a in arrs.items():
+            out[offsets[i]:offsets[i] + a.size].copy_(torch.from_numpy(a).reshape(-1))
+        self.stats["device"] += len(mine) - len(self.last_errors)
+        self.stats["flagged"] += len(self.last_errors)
+        self.stats["unsupported"] += len(rest)
+        return [out[o:o + h * w * 3].view(h, w, 3) for o, (h, w) in zip(offsets, shapes)]
+
+
 class ImageStore:
     """The images of `paths`, decoded once with Pillow on a thread pool, as uint8 (H, W, 3) tensors on `device` -- what
     `InputPipeline.run` reads.  `store[i]` is image i (in the order of `paths`), `store.sizes[i]` its (h, w).
@@ -279,14 +515,21 @@ class ImageStore:
     and `store[i]` is a view into it.  Streaming (otherwise): nothing is kept; `store[i]` and `store.fetch(indices)` decode (fetch: on
     the pool) and upload per call.  Both modes hand out the same tensors.  On a CPU device the arena / the fetched images are CPU
     tensors (the drivers' host logic is tested that way; the pipeline itself has no CPU path).
-    `folder` only names the place in the error an empty list raises."""
+    `folder` only names the place in the error an empty list raises.
+    device_decode: the baseline JPEGs among the files are decoded by a `JpegDecoder` on the device -- resident: read and parsed on the
+    pool and decoded chunk by chunk (DECODE_CHUNK files) straight into the arena; streaming: `fetch` decodes its batch there.  Every
+    other file, and every file the decoder flags, still goes through Pillow; the store holds the same bytes either way."""
 
-    def __init__(self, paths: Sequence, device, budget_bytes: Optional[int] = None, workers: Optional[int] = None, folder=None):
+    def __init__(self, paths: Sequence, device, budget_bytes: Optional[int] = None, workers: Optional[int] = None, folder=None,
+                 device_decode: bool = False, decoder: Optional[JpegDecoder] = None):
         self._pool = None
+        self._decoder = None
         self.paths = [os.fspath(p) for p in paths]
         if not self.paths:
             raise FileNotFoundError(f"no images found in {os.fspath(folder) if folder is not None else 'the given (empty) list of paths'}")
         self.device = normalize_device(device)
+        if device_decode:
+            self._decoder = decoder if decoder is not None else JpegDecoder(self.device)
         self.workers = max(1, min(16, int(workers) if workers is not None else (os.cpu_count() or 1)))
         self._pool = ThreadPoolExecutor(self.workers)
         self._stage = self._stage_event = None
@@ -329,9 +572,23 @@ class ImageStore:
         return buf[off:off + h * w * 3].view(h, w, 3)
 
     # ---- resident
+    def _device_decode(self, idx: Sequence[int], out=None, offsets=None) -> List[torch.Tensor]:
+        imgs = self._decoder.decode([self.paths[i] for i in idx], out=out, offsets=offsets, each=self._pool.map)
+        for i, im in zip(idx, imgs):
+            if tuple(im.shape) != self.sizes[i] + (3,):
+                raise OSError(f"image {self.paths[i]} decoded to {tuple(im.shape[:2])}, its header said {self.sizes[i]}")
+        return imgs
+
     def _fill(self, total: int):
         cuda = self.device.type == "cuda"
         self.arena = torch.empty(total, dtype=torch.uint8, device=self.device)
+        if self._decoder is not None:
+            for first in range(0, len(self), DECODE_CHUNK):
+                idx = range(first, min(first + DECODE_CHUNK, len(self)))
+                self._device_decode(idx, self.arena, [self.offsets[i] for i in idx])
+            if cuda:
+                torch.cuda.current_stream(self.device).synchronize()
+            return
         if not cuda:
             dst = self.arena.numpy()
 
@@ -370,6 +627,8 @@ class ImageStore:
         i = range(len(self))[i]
         if self.resident:
             return self._view(self.arena, self.offsets[i], i)
+        if self._decoder is not None:
+            return self._device_decode([i])[0]
         return torch.from_numpy(self._checked(i, _decode(self.paths[i]))).to(self.device)
 
     def fetch(self, indices: Sequence[int]) -> List[torch.Tensor]:
@@ -377,6 +636,8 @@ class ImageStore:
         idx = [range(len(self))[i] for i in indices]
         if self.resident:
             return [self._view(self.arena, self.offsets[i], i) for i in idx]
+        if self._decoder is not None:
+            return self._device_decode(idx)
         arrs = [self._checked(i, a) for i, a in zip(idx, self._pool.map(_decode, [self.paths[i] for i in idx]))]
         if self.device.type != "cuda":
             return [torch.from_numpy(a) for a in arrs]

@@ -8,6 +8,7 @@ engine, and on the GPU the resize, the normalisation and the uint8 conversion ru
 Build-only flags: --ngf / --n-blocks (the reference reads the architecture from its own module), --fp32 (bf16 operands stand in for the
 reference's autocast by default), --graph (one hipGraph replay per batch shape), --host-io (resize and convert with PIL / torch on the host),
 --device-jpeg (the JPEG files are encoded on the device as well, byte-identical to PIL's), --io-threads N (PIL decodes / saves on a thread pool),
+--device-decode [--decode-chunk N] (baseline JPEGs are decoded on the device, N files at a time ahead of the generator, pixel-identical to PIL's),
 --which G_A2B|G_B2A (a CycleGAN checkpoint of train_basic is recognised by its keys; this picks the generator, architecture read from the keys).
 """
 from __future__ import annotations
@@ -37,7 +38,13 @@ def parse_args(argv=None) -> argparse.Namespace:
     ap.add_argument("--which", default="G_A2B", choices=["G_A2B", "G_B2A"], help="generator of a CycleGAN checkpoint (train_basic's ckpt_e*.pt) to run (build-only flag)")
     ap.add_argument("--device-jpeg", action="store_true", help="encode the JPEGs on the device, byte-identical to PIL's (build-only flag)")
     ap.add_argument("--io-threads", type=int, default=1, help="threads for the PIL decodes (and the PIL saves without --device-jpeg), at most 16 (build-only flag)")
+    ap.add_argument("--device-decode", action="store_true", help="decode baseline JPEGs on the device, pixel-identical to PIL's (build-only flag)")
+    ap.add_argument("--decode-chunk", type=int, default=256, help="files per device decode, independent of --batch (build-only flag)")
     args = ap.parse_args(argv)
+    if args.device_decode and (args.host_io or args.device == "cpu"):
+        ap.error("--device-decode feeds the device I/O path on the GPU: not with --host-io or --device cpu")
+    if args.decode_chunk < 1:
+        ap.error("--decode-chunk must be at least 1")
     if args.device_jpeg and (args.host_io or args.device == "cpu"):
         ap.error("--device-jpeg encodes what the device I/O path leaves on the GPU: not with --host-io or --device cpu")
     if args.io_threads < 1:
@@ -50,6 +57,8 @@ def main(argv=None) -> int:
     if args.device == "cuda" and not torch.cuda.is_available():
         if args.device_jpeg:
             raise SystemExit("--device-jpeg needs the GPU: there is no host fallback for the device encoder")
+        if args.device_decode:
+            raise SystemExit("--device-decode needs the GPU: there is no host fallback for the device decoder")
         print("[WARN] CUDA not available. Falling back to CPU.")
         args.device = "cpu"
 
@@ -63,7 +72,7 @@ def main(argv=None) -> int:
     # the device input pipeline and the uint8 epilogue are HIP kernels: they run exactly when the generator runs on the HIP library
     n = I.stylize_folder(G, src_dir=args.photos, out_dir=args.out, device=args.device, img_size=args.size, batch=args.batch, limit=args.limit,
                          device_io=args.device == "cuda" and not args.host_io, device_jpeg=args.device_jpeg,
-                         io_threads=args.io_threads)
+                         io_threads=args.io_threads, **(dict(device_decode=True, decode_chunk=args.decode_chunk) if args.device_decode else {}))
     print("Done.")
     return n
 

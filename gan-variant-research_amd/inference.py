@@ -4,7 +4,8 @@
 generate_folder.py:125-170 does; `stylize` is the tensor-level body of `stylize_folder` (:207-252): G(x) then
 clamp -> *0.5 + 0.5 -> *255 -> round -> uint8 (:183-185).  `stylize_hwc` is the same with the conversion and the HWC turn PIL needs
 fused into one kernel after the generator's last layer (gan_view_to_u8_hwc), `stylize_images` puts the device input pipeline with
-Pillow's BILINEAR taps (:175-180) in front of it.  JPEG / PNG decoding stays in PIL on the host; JPEG encoding (:252) is PIL's by
+Pillow's BILINEAR taps (:175-180) in front of it.  JPEG / PNG decoding is PIL's on the host by default and, for baseline JPEGs,
+`dataio.JpegDecoder`'s on the device with `device_decode=True` (the same pixels); JPEG encoding (:252) is PIL's by
 default and `JpegEncoder`'s on the device with `device_jpeg=True`, byte for byte the same files.  `stylize_folder` walks a
 PIL-readable folder, with the resize and both conversions on the host (the default) or on the device (`device_io=True`).
 The command line is generate_folder.py next to this file.
@@ -198,19 +199,37 @@ def _jpeg_encoder(G, device, batch: int, H: int, W: int) -> JpegEncoder:
     return enc
 
 
+def _jpeg_decoder(G, device):
+    """The decoder cached on the generator, like `_infer_pipe`."""
+    from . import dataio
+    dev = dataio.normalize_device(device)
+    dec = getattr(G, "_jpeg_dec", None)
+    if dec is None or dec.device != dev:
+        dec = dataio.JpegDecoder(dev)
+        object.__setattr__(G, "_jpeg_dec", dec)
+    return dec
+
+
 @torch.inference_mode()
 def stylize_folder(G, src_dir: str, out_dir: str, device: str = "cuda", img_size: int = 256, batch: int = 16, limit: Optional[int] = None,
-                   device_io: bool = False, device_jpeg: bool = False, io_threads: int = 1) -> int:
+                   device_io: bool = False, device_jpeg: bool = False, io_threads: int = 1, device_decode: bool = False, decode_chunk: int = 256) -> int:
     """generate_folder.py:207-252 with PIL doing what torchvision's Resize(BILINEAR) / ToTensor / Normalize / ToPILImage do there.
     device_io: PIL only decodes and encodes; each photo is uploaded as uint8 HWC, `stylize_images` resizes, normalises, runs the
     generator and converts on the device, and one contiguous HWC download feeds PIL.  The files written are byte-identical.
     device_jpeg (needs device_io): the batch never comes back as pixels; `JpegEncoder` makes the files on the device and the host
     writes their bytes.  io_threads > 1: the PIL decodes of a chunk (and, without device_jpeg, the PIL saves) run on a thread pool of
-    at most 16 workers, as dataio.ImageStore's does.  Same files either way."""
+    at most 16 workers, as dataio.ImageStore's does.  device_decode (needs device_io): `dataio.JpegDecoder` decodes the baseline JPEGs
+    on the device, `decode_chunk` files per call whatever `batch` is (its entropy stage has one lane per restart segment: many files in
+    flight are its throughput), one chunk ahead on a side stream while the generator works on the previous one; other files, and files
+    the decoder flags, still go through PIL.  Same files either way."""
     import numpy as np
     from PIL import Image
     if device_jpeg and not device_io:
         raise ValueError("device_jpeg=True needs device_io=True: the encoder reads the uint8 batch the device epilogue leaves")
+    if device_decode and not device_io:
+        raise ValueError("device_decode=True needs device_io=True: the decoder leaves the uint8 images the device input pipeline reads")
+    if decode_chunk < 1:
+        raise ValueError(f"decode_chunk = {decode_chunk}: at least 1")
     if io_threads < 1:
         raise ValueError(f"io_threads = {io_threads}: at least 1")
     exts = {".jpg", ".jpeg", ".png", ".bmp", ".webp", ".tif", ".tiff"}
@@ -244,11 +263,40 @@ def stylize_folder(G, src_dir: str, out_dir: str, device: str = "cuda", img_size
     def save_bytes(p, data):
         target(p).write_bytes(data)
 
+    def decoded_ahead():
+        """The images of `paths` in chunks of decode_chunk files, the next chunk being decoded while the caller works on this one."""
+        from concurrent.futures import ThreadPoolExecutor
+        dec = _jpeg_decoder(G, device)
+        cuda = dec.device.type == "cuda"
+        side = torch.cuda.Stream(dec.device) if cuda else None
+        main = torch.cuda.current_stream(dec.device) if cuda else None
+
+        def job(s):
+            if not cuda:
+                return dec.decode(paths[s:s + decode_chunk], each=each)
+            with torch.cuda.stream(side):
+                return dec.decode(paths[s:s + decode_chunk], each=each)      # returns after its error words came back: the pixels are there
+        with ThreadPoolExecutor(1) as ahead:
+            fut = ahead.submit(job, 0)
+            for s in range(0, len(paths), decode_chunk):
+                imgs = fut.result()
+                if s + decode_chunk < len(paths):
+                    fut = ahead.submit(job, s + decode_chunk)
+                if cuda:
+                    imgs[0].record_stream(main)      # one buffer behind all views; allocated on the side stream, read on this one
+                yield imgs
+
     try:
+        ready, chunks = [], decoded_ahead() if device_decode else None
         for i in range(0, len(paths), batch):
             chunk = paths[i:i + batch]
             if device_io:
-                imgs = [torch.from_numpy(a).to(device) for a in each(decode, chunk)]
+                if device_decode:
+                    while len(ready) < min(i + batch, len(paths)):
+                        ready.extend(next(chunks))
+                    imgs, ready[i:i + batch] = ready[i:i + batch], [None] * len(chunk)
+                else:
+                    imgs = [torch.from_numpy(a).to(device) for a in each(decode, chunk)]
                 y = stylize_images(G, imgs, img_size)
                 if device_jpeg:
                     each(save_bytes, chunk, _jpeg_encoder(G, y.device, len(chunk), img_size, img_size).encode(y))
@@ -260,6 +308,8 @@ def stylize_folder(G, src_dir: str, out_dir: str, device: str = "cuda", img_size
                 y = stylize(G, x).cpu().permute(0, 2, 3, 1).numpy()
             each(save_pil, chunk, y)
     finally:
+        if chunks is not None:
+            chunks.close()
         if pool is not None:
             pool.shutdown()
     return len(paths)

@@ -571,6 +571,48 @@ class HipOps:
         assert codes.numel() >= B * 1024 and offsets.numel() >= B + 1 and out.is_contiguous() and offsets.is_contiguous()
         return self._call("gan_jpeg_scan", self._p(ws), ws.numel(), B, H, W, self._p(codes), self._p(out), out.numel(), self._p(offsets), self._s())
 
+    # ---- JPEG decoder (csrc/jpegdec.hip; dataio.JpegDecoder owns the buffers).  A decode's descriptors are new with every call, so these
+    #      entries launch at once instead of returning a prebuilt Op.
+    def _now(self, name: str, *args):
+        rc = getattr(self.lib, name)(*args)
+        if rc != 0:
+            raise _lib.GanError(f"{name}: {self.lib.gan_last_error().decode()}")
+
+    def jpegdec_block_offsets(self, n, nseg):
+        """Byte offsets (segments, dht, qt, scan bytes) of the upload block of n images and nseg restart segments."""
+        off = (C.c_int64 * 4)()
+        self._now("gan_jpegdec_block_offsets", int(n), int(nseg), off)
+        return tuple(int(v) for v in off)
+
+    def jpegdec_bounds(self, imgs) -> int:
+        """imgs: a ctypes array of _lib.GanJpegdecImage; fills their coef_off / plane_off and returns the workspace bytes."""
+        ws = C.c_int64(0)
+        self._now("gan_jpegdec_bounds", C.cast(imgs, C.c_void_p), len(imgs), C.byref(ws))
+        return int(ws.value)
+
+    def _jpegdec_args(self, blk_dev, blk_host, nbytes, n, nseg, ws):
+        assert blk_dev.dtype == torch.uint8 and blk_host.dtype == torch.uint8 and ws.dtype == torch.uint8 and blk_host.device.type == "cpu"
+        assert blk_dev.is_contiguous() and blk_host.is_contiguous() and ws.is_contiguous() and nbytes <= min(blk_dev.numel(), blk_host.numel())
+        return (C.c_void_p(blk_dev.data_ptr()), C.c_void_p(blk_host.data_ptr()), int(nbytes), int(n), int(nseg), C.c_void_p(ws.data_ptr()), ws.numel())
+
+    def jpegdec_tables(self, blk_dev, blk_host, nbytes, n, nseg, ws):
+        """DHT tables of the block -> decode tables in ws; zeroes the error words and the coefficients."""
+        self._now("gan_jpegdec_tables", *self._jpegdec_args(blk_dev, blk_host, nbytes, n, nseg, ws), self._s())
+
+    def jpegdec_entropy(self, blk_dev, blk_host, nbytes, n, nseg, ws):
+        """The scans -> int16 coefficients in ws, one workgroup per image, one lane per restart segment."""
+        self._now("gan_jpegdec_entropy", *self._jpegdec_args(blk_dev, blk_host, nbytes, n, nseg, ws), self._s())
+
+    def jpegdec_idct(self, blk_dev, blk_host, nbytes, n, nseg, ws):
+        """Coefficients -> uint8 component planes in ws."""
+        self._now("gan_jpegdec_idct", *self._jpegdec_args(blk_dev, blk_host, nbytes, n, nseg, ws), self._s())
+
+    def jpegdec_pixels(self, blk_dev, blk_host, nbytes, n, nseg, ws, out, err):
+        """Planes -> packed (H, W, 3) at every image's out_off in `out`; err (int32 [n]) receives the error words."""
+        assert out.dtype == torch.uint8 and out.is_contiguous() and err.dtype == torch.int32 and err.is_contiguous() and err.numel() >= n
+        self._now("gan_jpegdec_pixels", *self._jpegdec_args(blk_dev, blk_host, nbytes, n, nseg, ws), C.c_void_p(out.data_ptr()), out.numel(),
+                  C.c_void_p(err.data_ptr()), self._s())
+
     def view_copy(self, src: View, dst: View, halo_mode) -> Op:
         return self._call("gan_view_copy", self._v(src), self._v(dst), halo_mode, self._s())
 

@@ -480,6 +480,69 @@ int gan_jpeg_tables(const uint32_t* hist, int n, uint8_t* dht, uint32_t* codes, 
 int gan_jpeg_scan(void* ws, int64_t ws_bytes, int B, int H, int W, const uint32_t* codes, uint8_t* out, int64_t out_bytes, int64_t* offsets,
                   void* stream);
 
+/* ---- Baseline JPEG decoder on the device: the pixels Image.open(p).convert("RGB") gives (libjpeg-turbo's 8-bit path: Huffman decode,
+ *      jidctint.c's jpeg_idct_islow, jdsample.c's fancy h2v1 / h2v2 upsampling, jdcolor.c's YCbCr -> RGB), for the files a host parser
+ *      accepted: SOF0, 8 bit, one interleaved scan, 1 component (1x1) or 3 components with chroma 1x1 and luma 1x1 / 2x1 / 2x2, no Adobe
+ *      marker; restart markers are supported.  Integer arithmetic only.  The scan is untrusted: every loop of the kernels is bounded by
+ *      a count from the descriptors, every load is clamped to its segment, every store goes to an address computed from counters, and
+ *      an irregularity sets bits of the image's error word (GAN_JPEGDEC_ERR_*) and ends that lane's work; the caller sends such a file
+ *      to the host decoder.
+ *
+ *      One upload block carries everything (all offsets from its start, n images, nseg segments):
+ *        gan_jpegdec_image [n] | gan_jpegdec_segment [nseg] | uint8 dht [n][4][272] | uint16 qt [n][4][64] | scan bytes
+ *      dht[i][t]: 16 counts then the symbols of table t = DC0, DC1, AC0, AC1 (zeros when absent); qt[i][s]: quantisation table s in
+ *      natural (row-major) order.  gan_jpegdec_block_offsets gives the byte offsets; qt and the scan bytes start at multiples of 16.
+ *      Workspace (16-byte aligned, gan_jpegdec_bounds bytes): decode tables [n][4] | error words int32 [n] | int16 coefficients in
+ *      natural order, component after component, blocks row-major over the MCU-padded component | uint8 component planes, padded alike.
+ *      Refused with a message, before any launch: a NULL pointer, n or nseg below 1, n above 65535, H or W outside 1 .. 65535, a
+ *      component layout outside the class above, MCU counts that do not belong to H and W, table slots outside 0 .. 3, a workspace that
+ *      is too small or not 16-byte aligned, coefficient / plane / output offsets that leave their buffers, a segment that names no image,
+ *      MCUs beyond its image or bytes outside the block's scan area. */
+typedef struct gan_jpegdec_image {
+  int32_t ncomp, H, W, hmax, vmax;   /* components 1 | 3; luma sampling factors 1x1, 2x1 or 2x2 (chroma is 1x1) */
+  int32_t mcux, mcuy;                /* MCUs across and down: ceil(W / (8 hmax)), ceil(H / (8 vmax)) */
+  int32_t seg_first, seg_count;      /* its restart segments in the segment table */
+  int32_t dc_tab[3], ac_tab[3];      /* per component: index into dht[i] (DC: 0 | 1, AC: 2 | 3) */
+  int32_t q_tab[3];                  /* per component: index into qt[i] */
+  int32_t reserved[2];
+  int64_t coef_off, plane_off;      /* bytes into the workspace (filled by gan_jpegdec_bounds) */
+  int64_t out_off;                   /* bytes into `out` of gan_jpegdec_pixels: where the packed (H, W, 3) image goes */
+} gan_jpegdec_image;
+typedef struct gan_jpegdec_segment {
+  int32_t image, mcu_first, mcu_count;   /* MCUs mcu_first .. mcu_first + mcu_count - 1 of the image, raster order */
+  int32_t byte_begin, byte_end;          /* its entropy-coded bytes in the block, the RSTn / EOI marker after them excluded */
+} gan_jpegdec_segment;
+#define GAN_JPEGDEC_ERR_CODE 1       /* no Huffman code within 16 bits, or a DC category above 15 */
+#define GAN_JPEGDEC_ERR_RUN 2        /* a run past coefficient 63 */
+#define GAN_JPEGDEC_ERR_END 4        /* bits needed beyond the segment's end */
+#define GAN_JPEGDEC_ERR_DC 8         /* a DC value outside int16 */
+#define GAN_JPEGDEC_ERR_LEFT 16      /* whole bytes left over at the end of a segment */
+#define GAN_JPEGDEC_ERR_RST 32       /* the marker in front of a segment is not the RSTn its number asks */
+#define GAN_JPEGDEC_ERR_MARKER 64    /* a 0xFF inside a segment that no 0x00 follows */
+#define GAN_JPEGDEC_ERR_RANGE 128    /* IDCT intermediates beyond what libjpeg's C and SIMD code agree on (see gan_jpegdec_idct) */
+/* Host only.  Byte offsets of the block's parts for n images and nseg segments: off[0] segments, off[1] dht, off[2] qt, off[3] scan. */
+int gan_jpegdec_block_offsets(int n, int nseg, int64_t* off);
+/* Host only.  Fills coef_off and plane_off of imgs[0 .. n-1] (host memory) and gives the workspace size. */
+int gan_jpegdec_bounds(gan_jpegdec_image* imgs, int n, int64_t* ws_bytes);
+/* One wave per DHT table: the 9-bit lookahead table (next 9 bits -> length << 8 | symbol, 0 when the code is longer) and the canonical
+ * maxcode / value-offset arrays for the longer codes.  Also zeroes the error words and the coefficient area.  blk_host: the host copy
+ * of the block's descriptors (images and segments), which every entry validates. */
+int gan_jpegdec_tables(const void* blk_dev, const void* blk_host, int64_t blk_bytes, int n, int nseg, void* ws, int64_t ws_bytes, void* stream);
+/* One 64-lane workgroup per image with the image's four tables in LDS; lane s decodes restart segments s, s + 64, ..: DC prediction
+ * per component from 0, the block index from the MCU counter, 0xFF 0x00 read as 0xFF. */
+int gan_jpegdec_entropy(const void* blk_dev, const void* blk_host, int64_t blk_bytes, int n, int nseg, void* ws, int64_t ws_bytes, void* stream);
+/* One thread per 8x8 block: dequantise in int32, jpeg_idct_islow (CONST_BITS 13, PASS1_BITS 2: columns DESCALE(., 11), rows
+ * DESCALE(., 18)), + 128, clamp to 0 .. 255.  Sets GAN_JPEGDEC_ERR_RANGE when a dequantised product or a pass-1 value leaves int16
+ * or a descaled row value leaves -512 .. 511. */
+int gan_jpegdec_idct(const void* blk_dev, const void* blk_host, int64_t blk_bytes, int n, int nseg, void* ws, int64_t ws_bytes, void* stream);
+/* One thread per pixel: fancy upsampling of the chroma planes (h2v1: (3 cur + prev + 1) >> 2, (3 cur + next + 2) >> 2; h2v2: 3 cur +
+ * above / below, then (3 cur + prev + 8) >> 4, (3 cur + next + 7) >> 4; the edges repeat the sample; plain replication when the
+ * downsampled width is at most 2, as libjpeg chooses), then R = Y + ((91881 cr + 32768) >> 16), B = Y + ((116130 cb + 32768) >> 16),
+ * G = Y + ((-22554 cb - 46802 cr + 32768) >> 16), clamped; R = G = B = Y for one component.  Image i goes to out + out_off, packed
+ * (H, W, 3).  err (may be NULL): int32 [n] on the device, receives a copy of the error words. */
+int gan_jpegdec_pixels(const void* blk_dev, const void* blk_host, int64_t blk_bytes, int n, int nseg, void* ws, int64_t ws_bytes, uint8_t* out,
+                       int64_t out_bytes, int32_t* err, void* stream);
+
 /* ---- losses.  Every loss writes its value to *loss (device fp32, overwritten) and the gradient wrt its input.
  *      hinge: adv_hinge.py:6-62 (mode 0: mean relu(1-x), 1: mean relu(1+x), 2: -mean x), scaled by `scale`;
  *      lsgan/bce: Basic_GAN/src/losses.py:5-22 (mode 3: mse vs target, 4: bce-with-logits vs target in {0,1});

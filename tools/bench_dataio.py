@@ -8,13 +8,15 @@
     resident+overlap    the same, batch k+1 prepared while step k runs                   (what the driver runs on folders)
     streaming           dataio.ImageStore decoding every batch on its thread pool, in series
     streaming+overlap   the same, overlapped
+    streaming+dd, streaming+dd+overlap   (--device-decode) the streaming store with device_decode=True: dataio.JpegDecoder decodes every batch
+
 
 over N random 256x256 JPEGs per domain written with Pillow into a temporary folder.  Every mode is warmed up, then timed in ROUNDS
 alternating rounds of STEPS steps (a multiple of the lazy-R1 period, so every window holds the same work); one JSON line per mode with
 the median round and [min .. max], one line per store build, and what the resident store adds to the synthetic and to the fixed rounds
 against those rounds' own spread (the overlap was decided by it).
 
-usage: bench_dataio.py [--n 512] [--steps 32] [--rounds 5]
+usage: bench_dataio.py [--n 512] [--steps 32] [--rounds 5] [--device-decode]
 """
 import argparse
 import itertools
@@ -60,6 +62,7 @@ def main():
     ap.add_argument("--n", type=int, default=512, help="JPEGs per domain")
     ap.add_argument("--steps", type=int, default=32, help="steps per timed window")
     ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--device-decode", action="store_true", help="also build both stores with device_decode=True and time the streaming one")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "bench_dataio needs the GPU"
     dev = torch.device("cuda")
@@ -73,12 +76,15 @@ def main():
         paths = {d: write_jpegs(os.path.join(tmp, d), args.n, k) for k, d in enumerate(("photos", "monet"))}
         print(json.dumps({"wrote": f"2 x {args.n} JPEGs {S}x{S}", "seconds": round(time.perf_counter() - t0, 2)}), flush=True)
         stores = {}
-        for kind, budget in (("resident", None), ("streaming", 1)):
+        kinds = [("resident", None, False), ("streaming", 1, False)] + ([("resident+dd", None, True), ("streaming+dd", 1, True)] if args.device_decode else [])
+        for kind, budget, dd in kinds:
             t0 = time.perf_counter()
-            stores[kind] = [dataio.ImageStore(paths[d], dev, budget_bytes=budget) for d in ("photos", "monet")]
+            stores[kind] = [dataio.ImageStore(paths[d], dev, budget_bytes=budget, **({"device_decode": True} if dd else {})) for d in ("photos", "monet")]
             torch.cuda.synchronize()
             st = stores[kind][0]
-            assert st.resident == (kind == "resident")
+            assert st.resident == kind.startswith("resident")
+            if dd:
+                assert st._decoder.stats["unsupported"] == st._decoder.stats["flagged"] == 0
             print(json.dumps({"store": kind, "images": 2 * args.n, "decoded_MB": round(2 * st.nbytes / 1e6, 1), "workers": st.workers,
                               "build_seconds": round(time.perf_counter() - t0, 3)}), flush=True)
 
@@ -87,7 +93,9 @@ def main():
         sources = {"synthetic": (T.synthetic_batches(B, S, dev, 1234), T.synthetic_batches(B, S, dev, 4321))}
         sources["fixed"] = tuple(itertools.repeat(next(it).clone()) for it in sources["synthetic"])
         modes = [("fixed", "fixed", False), ("synthetic", "synthetic", False)]
-        for kind in ("resident", "streaming"):
+        if args.device_decode:
+            assert all(torch.equal(a[i], b[i]) for a, b in zip(stores["resident"], stores["resident+dd"]) for i in range(0, args.n, 37))
+        for kind in ("resident", "streaming") + (("streaming+dd",) if args.device_decode else ()):
             sources[kind] = folder_source(kind)
             modes += [(kind, kind, False), (kind + "+overlap", kind, True)]
 

@@ -4,11 +4,13 @@
 (b) folder path: inference.stylize_folder on 64 seeded PNGs of mixed sizes, host I/O vs device I/O (images/s, decode and JPEG encode included)
 (c) JPEG encode (--jpeg): the folder path at batch 16 on two folders (the mixed PNGs; 256 JPEGs of 256 x 256), device I/O with serial PIL
     against PIL on a thread pool (io_threads 4, 16) against the device encoder (device_jpeg, io_threads 1, 4, 16); same files every mode
+(d) JPEG decode (--decode): the same two folders at batch 16 with device_jpeg: PIL decoding serially and on a pool (io_threads 4, 16)
+    against the device decoder (device_decode, decode_chunk 16 / 64 / 256; other formats still go through PIL); same files every mode
 
 Every shape is warmed up; the two paths are then timed in rotation for --rounds rounds (a host clock around work that ends in a device
 synchronise: each call ends in a download); the median round and the spread (min .. max) are reported.  The outputs of the two paths
 are compared before anything is timed.
-usage: bench_stylize.py [--size 256] [--batches 1,4,16] [--calls 40] [--rounds 5] [--photos 64] [--out FILE] [--jpeg] [--only-jpeg]
+usage: bench_stylize.py [--size 256] [--batches 1,4,16] [--calls 40] [--rounds 5] [--photos 64] [--out FILE] [--jpeg] [--only-jpeg] [--decode] [--only-decode]
 """
 import argparse
 import os
@@ -53,6 +55,45 @@ def make_jpeg_folder(root: Path, n: int, size: int = 256, seed: int = 1):
 JPEG_MODES = (("a  device_io, serial PIL", dict()), ("b  PIL pool, io_threads 4", dict(io_threads=4)), ("b  PIL pool, io_threads 16", dict(io_threads=16)),
               ("c  device_jpeg, io_threads 1", dict(device_jpeg=True)), ("c  device_jpeg, io_threads 4", dict(device_jpeg=True, io_threads=4)),
               ("c  device_jpeg, io_threads 16", dict(device_jpeg=True, io_threads=16)))
+
+
+DECODE_MODES = (("a  PIL serial", dict()), ("b  PIL pool, io_threads 4", dict(io_threads=4)), ("b  PIL pool, io_threads 16", dict(io_threads=16)),
+                ("d  device_decode, chunk 16", dict(device_decode=True, decode_chunk=16)), ("d  device_decode, chunk 64", dict(device_decode=True, decode_chunk=64)),
+                ("d  device_decode, chunk 256", dict(device_decode=True, decode_chunk=256)),
+                ("d  device_decode, chunk 256, io_threads 4", dict(device_decode=True, decode_chunk=256, io_threads=4)))
+
+
+def decode_section(G, dev, S, rounds, photos, tmp: Path):
+    """(d): every mode writes the same files (checked first), then the modes run in rotation; images/s, median [min .. max]."""
+    lines = [f"# (d) images/s over one pass of a folder, batch 16, {S}x{S}, device_jpeg, decode and encode included; median of {rounds} alternating rounds [min .. max]"]
+    if not (tmp / "jpegs").exists():
+        make_jpeg_folder(tmp / "jpegs", 256, S)
+    for label, src, n in ((f"{photos} PNGs of mixed sizes", tmp / "photos", photos), (f"256 JPEGs of {S}x{S}", tmp / "jpegs", 256)):
+        def mode(i, kw):
+            def run():
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                assert I.stylize_folder(G, str(src), str(tmp / f"d_{src.name}_{i}"), device=str(dev), img_size=S, batch=16, device_io=True, device_jpeg=True, **kw) == n
+                torch.cuda.synchronize()
+                return n / (time.perf_counter() - t0)
+            return run
+        paths = {name: mode(i, kw) for i, (name, kw) in enumerate(DECODE_MODES)}
+        for fn in paths.values():
+            fn()
+        outs = [{p.name: p.read_bytes() for p in (tmp / f"d_{src.name}_{i}").rglob("*.jpg")} for i in range(len(DECODE_MODES))]
+        assert len(outs[0]) == n and all(o == outs[0] for o in outs), "the modes wrote different files"
+        times = rotate(paths, rounds)
+        lines.append(f"# {label}; the device decoder's counts since the start of the section: {G._jpeg_dec.stats}")
+        for name, v in times.items():
+            lines.append(f"(d) {name:44s} {statistics.median(v):8.1f} images/s [{min(v):8.1f} .. {max(v):8.1f}]")
+        best_pool = max(max(times[k]) for k in times if k.startswith("b"))
+        for name, v in times.items():
+            if name.startswith("d"):
+                verdict = "beats" if min(v) > best_pool else "does not beat"
+                lines.append(f"(d) {name[3:]}: {verdict} the PIL pools beyond both spreads (its min {min(v):.1f} vs their max {best_pool:.1f})")
+        for ln in lines[-(2 * len(DECODE_MODES) - 2):]:
+            print(ln, flush=True)
+    return lines
 
 
 def jpeg_section(G, dev, S, rounds, photos, tmp: Path):
@@ -114,7 +155,10 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--jpeg", action="store_true", help="also run section (c)")
     ap.add_argument("--only-jpeg", action="store_true", help="run section (c) alone")
+    ap.add_argument("--decode", action="store_true", help="also run section (d)")
+    ap.add_argument("--only-decode", action="store_true", help="run section (d) alone")
     a = ap.parse_args()
+    a.decode = a.decode or a.only_decode
     assert torch.cuda.is_available(), "bench_stylize.py measures on the GPU"
     dev, S = torch.device("cuda:0"), a.size
     C.set_seed(0)
@@ -123,13 +167,14 @@ def main():
         p.requires_grad_(False)
     G.compute_dtype = BF16
     lines = [f"# tools/bench_stylize.py --size {S} --batches {a.batches} --calls {a.calls} --rounds {a.rounds} --photos {a.photos}"
-             + (" --only-jpeg" if a.only_jpeg else " --jpeg" if a.jpeg else ""),
+             + (" --only-jpeg" if a.only_jpeg else " --jpeg" if a.jpeg else "") + (" --only-decode" if a.only_decode else " --decode" if a.decode else ""),
              f"# generator ngf 64, 9 blocks, bf16 operands, eager launches; median of {a.rounds} alternating rounds [min .. max]"]
-    if not a.only_jpeg:
+    only = a.only_jpeg or a.only_decode
+    if not only:
         lines.append(f"# (a) ms per call of {a.calls} consecutive calls, each ending in the download of the uint8 HWC batch to the host")
     old_out = lambda x: I.stylize(G, x).cpu().permute(0, 2, 3, 1).contiguous()
     new_out = lambda x: I.stylize_hwc(G, x).cpu()
-    batches = [] if a.only_jpeg else [int(v) for v in a.batches.split(",")]
+    batches = [] if only else [int(v) for v in a.batches.split(",")]
     for B in batches:
         x = (torch.rand(B, 3, S, S) * 2 - 1).to(dev)
         for _ in range(3):
@@ -147,7 +192,7 @@ def main():
             return run
         lines.append(line(f"(a) B={B:2d} {S}x{S}", "ms", rotate({"old": timed(old_out), "new": timed(new_out)}, a.rounds), True))
         print(lines[-1], flush=True)
-    if not a.only_jpeg:
+    if not only:
         lines.append(f"# (b) images/s over one pass of a folder of {a.photos} PNGs (120 .. 640 pixels a side), PNG decode and JPEG encode included")
     with tempfile.TemporaryDirectory() as tmp:
         tmp = Path(tmp)
@@ -171,6 +216,8 @@ def main():
             print(lines[-1], flush=True)
         if a.jpeg or a.only_jpeg:
             lines += jpeg_section(G, dev, S, a.rounds, a.photos, tmp)
+        if a.decode:
+            lines += decode_section(G, dev, S, a.rounds, a.photos, tmp)
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
         with open(a.out, "w") as f:
