@@ -65,6 +65,18 @@ JPEGDEC_ERR = {1: "no Huffman code", 2: "run past coefficient 63", 4: "bits beyo
                32: "wrong RSTn", 64: "marker inside a segment", 128: "IDCT range"}
 
 
+class GanPngdecImage(C.Structure):
+    _fields_ = [("H", i32), ("W", i32), ("color", i32), ("depth", i32), ("bpp", i32), ("rowbytes", i32), ("pal_count", i32), ("wbits", i32),
+                ("stream_off", i32), ("stream_len", i32), ("reserved", i32 * 2), ("raw_off", i64), ("out_off", i64)]
+
+
+PNGDEC_MAX_ROWBYTES = 16384      # GAN_PNGDEC_MAX_ROWBYTES: the rows of the unfilter kernel, 4096 pixels of RGBA
+PNGDEC_ERR = {1: "block type 3", 2: "stored LEN is not ~NLEN", 4: "too many code lengths", 8: "bad code-length repeat", 16: "over-subscribed code",
+              32: "incomplete code", 64: "no end-of-block code", 128: "invalid symbol", 256: "distance too far back", 512: "bits beyond the stream",
+              1024: "more output than the image has", 2048: "less output than the image has", 4096: "bytes between the final block and the Adler-32",
+              8192: "filter byte above 4", 16384: "Adler-32 mismatch"}
+
+
 class GanSnDesc(C.Structure):
     _fields_ = [("W", vp), ("u", vp), ("v", vp), ("sigma", vp), ("u_snap", vp), ("v_snap", vp), ("G", vp), ("dW", vp), ("ws", vp),
                 ("h", i32), ("w", i32), ("first_block", i32), ("nblocks", i32)]
@@ -144,6 +156,10 @@ PROTOTYPES = {
     "gan_jpegdec_entropy": (C.c_int, [vp, vp, i64, C.c_int, C.c_int, vp, i64, vp]),
     "gan_jpegdec_idct": (C.c_int, [vp, vp, i64, C.c_int, C.c_int, vp, i64, vp]),
     "gan_jpegdec_pixels": (C.c_int, [vp, vp, i64, C.c_int, C.c_int, vp, i64, vp, i64, vp, vp]),
+    "gan_pngdec_block_offsets": (C.c_int, [C.c_int, C.POINTER(i64)]),
+    "gan_pngdec_bounds": (C.c_int, [vp, C.c_int, C.POINTER(i64)]),
+    "gan_pngdec_inflate": (C.c_int, [vp, vp, i64, C.c_int, vp, i64, vp]),
+    "gan_pngdec_pixels": (C.c_int, [vp, vp, i64, C.c_int, vp, i64, vp, i64, vp, vp]),
     "gan_spectral_norm_ws_floats": (C.c_int64, [C.c_int, C.c_int]),
     "gan_spectral_norm_fwd": (C.c_int, [vp, C.c_int, C.c_int, vp, vp, C.c_int, C.c_float, vp, vp, vp, vp]),
     "gan_spectral_norm_bwd": (C.c_int, [vp, vp, vp, vp, vp, C.c_int, C.c_int, vp, vp, vp]),

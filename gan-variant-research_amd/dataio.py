@@ -378,12 +378,9 @@ def parse_jpeg(data: bytes) -> Optional[Dict]:
             "dc_tab": dc_tab, "ac_tab": ac_tab, "q_tab": q_tab, "scan": (sb, end), "seg_begin": begins, "seg_end": ends, "per": per, "data": data}
 
 
-class JpegDecoder:
-    """Baseline JPEG files -> packed uint8 (H, W, 3) tensors on `device`, pixel-identical to `_decode` (Pillow) for every source.  The
-    files `parse` accepts are decoded by csrc/jpegdec.hip: their descriptors, tables and scan bytes go up in one copy from one pinned
-    staging buffer, four launches decode any number of files together, and the host reads one error word per file.  Every other
-    source, and every file the kernels flagged, goes through `_decode` -- which returns Pillow's pixels or raises its OSError, as
-    without the decoder.  Owns and grows its buffers, like InputPipeline.  `stats` counts which way the sources went."""
+class _DecoderBase:
+    """What the device decoders share: the buffers, and a `decode` that sends every source to the decoder whose parser takes it and
+    everything else, and every file a kernel flagged, through `_decode` (Pillow)."""
 
     def __init__(self, device, ops=None):
         from . import autograd as AG
@@ -396,10 +393,6 @@ class JpegDecoder:
         self.last_block = None
         self._host = self._dev = self._ws = self._err = None
 
-    @staticmethod
-    def parse(data: bytes) -> Optional[Dict]:
-        return parse_jpeg(data)
-
     def _grow(self, name: str, nbytes: int, dtype=torch.uint8, host=False):
         t = getattr(self, name)
         if t is None or t.numel() < nbytes:
@@ -407,6 +400,98 @@ class JpegDecoder:
             t = torch.zeros(n, dtype=dtype, pin_memory=True) if host and self.device.type == "cuda" else torch.zeros(n, dtype=dtype, device="cpu" if host else self.device)
             setattr(self, name, t)
         return t
+
+    def load(self, source):
+        """(bytes, plan or None) of a path or of bytes: the part of `decode` that a thread pool can do ahead."""
+        data = bytes(source) if isinstance(source, (bytes, bytearray, memoryview)) else open(os.fspath(source), "rb").read()
+        return data, self.parse(data)
+
+    def _groups(self, plans):
+        """[(decoder, indices of the sources it takes)]."""
+        return [(self, [i for i, p in enumerate(plans) if p is not None])]
+
+    def _count(self, groups, loaded, rest):
+        for d, idx in groups:
+            d.stats["device"] += len(idx) - len(d.last_errors)
+            d.stats["flagged"] += len(d.last_errors)
+        self.stats["unsupported"] += len(rest)
+
+    def _upload(self, total: int):
+        """The staging buffer's first `total` bytes on the device (the buffer itself on a CPU device)."""
+        if self.device.type != "cuda":
+            return self._host
+        dev = self._grow("_dev", total)
+        dev[:total].copy_(self._host[:total], non_blocking=True)
+        return dev
+
+    def _launched(self, launches):
+        try:
+            launches()
+        except GanError:
+            if self.device.type == "cuda":
+                torch.cuda.current_stream(self.device).synchronize()      # the upload has left the staging buffer before it is reused
+            raise
+
+    @torch.inference_mode()
+    def decode(self, sources: Sequence, out: Optional[torch.Tensor] = None, offsets: Optional[Sequence[int]] = None, each=None) -> List[torch.Tensor]:
+        """sources: paths or bytes, any number.  out / offsets: a flat uint8 tensor on the decoder's device and the byte offset of every
+        image in it (the store's arena); None: one new buffer, every image at a multiple of ARENA_ALIGN.  each: a `map` for the host work
+        per file (reading and parsing; Pillow's decode of what is not the device's), e.g. a thread pool's.  Returns (H, W, 3) views."""
+        import io
+        each = map if each is None else each
+        sources = list(sources)
+        is_bytes = lambda s: isinstance(s, (bytes, bytearray, memoryview))
+        host_decode = lambda i: _decode(io.BytesIO(bytes(sources[i])) if is_bytes(sources[i]) else sources[i])
+        loaded = list(each(self.load, sources))
+        plans = [p for _, p in loaded]
+        every = self._groups(plans)
+        groups = [(d, idx) for d, idx in every if idx]
+        rest = [i for i, p in enumerate(plans) if p is None]
+        arrs = dict(zip(rest, each(host_decode, rest)))
+        shapes = [(plans[i]["H"], plans[i]["W"]) if plans[i] is not None else arrs[i].shape[:2] for i in range(len(sources))]
+        if out is None:
+            offsets, end = [], 0
+            for h, w in shapes:
+                offsets.append(end)
+                end += -(-(h * w * 3) // ARENA_ALIGN) * ARENA_ALIGN
+            out = torch.empty(max(end, 1), dtype=torch.uint8, device=self.device)
+        elif offsets is None or len(offsets) != len(sources) or out.dtype != torch.uint8 or out.dim() != 1 or not out.is_contiguous() or out.device != self.device:
+            raise GanError(f"{type(self).__name__}.decode: `out` must be a flat contiguous uint8 tensor on {self.device} with one offset per source")
+        self.last_errors = {}
+        for d, _ in every:
+            if d is not None:
+                d.last_errors = {}
+        if groups:                                               # every launch of the call, then one download of all error words
+            err, at = self._grow("_err", sum(len(idx) for _, idx in groups), torch.int32), 0
+            for d, idx in groups:
+                d._launch([plans[i] for i in idx], [offsets[i] for i in idx], out, err[at:at + len(idx)])
+                at += len(idx)
+            words = err[:at].cpu().tolist()                      # it also orders the staging buffers' reuse
+            for d, idx in groups:
+                d.last_errors = {i: int(w) for i, w in zip(idx, words[:len(idx)]) if w}
+                self.last_errors.update(d.last_errors)
+                words = words[len(idx):]
+        flagged = sorted(self.last_errors)
+        for i, a in zip(flagged, each(host_decode, flagged)):    # Pillow's pixels, or its OSError
+            if a.shape[:2] != shapes[i]:
+                raise OSError(f"image {sources[i]!r} decoded to {a.shape[:2]}, its header said {shapes[i]}")
+            arrs[i] = a
+        for i, a in arrs.items():
+            out[offsets[i]:offsets[i] + a.size].copy_(torch.from_numpy(a).reshape(-1))
+        self._count(groups, loaded, rest)
+        return [out[o:o + h * w * 3].view(h, w, 3) for o, (h, w) in zip(offsets, shapes)]
+
+
+class JpegDecoder(_DecoderBase):
+    """Baseline JPEG files -> packed uint8 (H, W, 3) tensors on `device`, pixel-identical to `_decode` (Pillow) for every source.  The
+    files `parse` accepts are decoded by csrc/jpegdec.hip: their descriptors, tables and scan bytes go up in one copy from one pinned
+    staging buffer, four launches decode any number of files together, and the host reads one error word per file.  Every other
+    source, and every file the kernels flagged, goes through `_decode` -- which returns Pillow's pixels or raises its OSError, as
+    without the decoder.  Owns and grows its buffers, like InputPipeline.  `stats` counts which way the sources went."""
+
+    @staticmethod
+    def parse(data: bytes) -> Optional[Dict]:
+        return parse_jpeg(data)
 
     def _pack(self, plans: Sequence[Dict], out_offsets: Sequence[int]):
         """The upload block of `plans` in the staging buffer -> (block bytes, images, segments, workspace bytes)."""
@@ -442,68 +527,186 @@ class JpegDecoder:
         host[o_seg:o_dht].view(np.int32)[:] = segs.reshape(-1)
         return total, n, nseg, ws_bytes
 
-    def load(self, source):
-        """(bytes, plan or None) of a path or of bytes: the part of `decode` that a thread pool can do ahead."""
-        data = bytes(source) if isinstance(source, (bytes, bytearray, memoryview)) else open(os.fspath(source), "rb").read()
-        return data, parse_jpeg(data)
+    def _launch(self, plans: Sequence[Dict], offsets: Sequence[int], out: torch.Tensor, err: torch.Tensor) -> None:
+        """Packs, uploads and launches the decode of `plans` into `out`; err (int32, one per plan, on the device) receives the error words."""
+        total, n, nseg, ws_bytes = self._pack(plans, offsets)
+        self.last_block = (total, n, nseg)                   # the staging buffer and the workspace still hold this call (tests locate a difference there)
+        ws = self._grow("_ws", ws_bytes)
+        dev, o = self._upload(total), self.ops
 
-    @torch.inference_mode()
-    def decode(self, sources: Sequence, out: Optional[torch.Tensor] = None, offsets: Optional[Sequence[int]] = None, each=None) -> List[torch.Tensor]:
-        """sources: paths or bytes, any number.  out / offsets: a flat uint8 tensor on the decoder's device and the byte offset of every
-        image in it (the store's arena); None: one new buffer, every image at a multiple of ARENA_ALIGN.  each: a `map` for the host work
-        per file (reading and parsing; Pillow's decode of what is not the device's), e.g. a thread pool's.  Returns (H, W, 3) views."""
-        import io
-        each = map if each is None else each
-        sources = list(sources)
-        is_bytes = lambda s: isinstance(s, (bytes, bytearray, memoryview))
-        host_decode = lambda i: _decode(io.BytesIO(bytes(sources[i])) if is_bytes(sources[i]) else sources[i])
-        loaded = list(each(self.load, sources))
-        plans = [p for _, p in loaded]
-        mine = [i for i, p in enumerate(plans) if p is not None]
-        rest = [i for i, p in enumerate(plans) if p is None]
-        arrs = dict(zip(rest, each(host_decode, rest)))
-        shapes = [(plans[i]["H"], plans[i]["W"]) if plans[i] is not None else arrs[i].shape[:2] for i in range(len(sources))]
-        if out is None:
-            offsets, end = [], 0
-            for h, w in shapes:
-                offsets.append(end)
-                end += -(-(h * w * 3) // ARENA_ALIGN) * ARENA_ALIGN
-            out = torch.empty(max(end, 1), dtype=torch.uint8, device=self.device)
-        elif offsets is None or len(offsets) != len(sources) or out.dtype != torch.uint8 or out.dim() != 1 or not out.is_contiguous() or out.device != self.device:
-            raise GanError(f"JpegDecoder.decode: `out` must be a flat contiguous uint8 tensor on {self.device} with one offset per source")
-        self.last_errors = {}
-        if mine:
-            total, n, nseg, ws_bytes = self._pack([plans[i] for i in mine], [offsets[i] for i in mine])
-            self.last_block = (total, n, nseg)                   # the staging buffer and the workspace still hold this call (tests locate a difference there)
-            ws, err = self._grow("_ws", ws_bytes), self._grow("_err", n, torch.int32)
-            if self.device.type == "cuda":
-                dev = self._grow("_dev", total)
-                dev[:total].copy_(self._host[:total], non_blocking=True)
-            else:
-                dev = self._host
-            o = self.ops
-            try:
-                o.jpegdec_tables(dev, self._host, total, n, nseg, ws)
-                o.jpegdec_entropy(dev, self._host, total, n, nseg, ws)
-                o.jpegdec_idct(dev, self._host, total, n, nseg, ws)
-                o.jpegdec_pixels(dev, self._host, total, n, nseg, ws, out, err)
-            except GanError:
-                if self.device.type == "cuda":
-                    torch.cuda.current_stream(self.device).synchronize()      # the upload has left the staging buffer before it is reused
-                raise
-            words = err[:n].cpu().tolist()                       # one download per call; it also orders the staging buffer's reuse
-            self.last_errors = {i: int(w) for i, w in zip(mine, words) if w}
-            flagged = sorted(self.last_errors)
-            for i, a in zip(flagged, each(host_decode, flagged)):      # Pillow's pixels, or its OSError
-                if a.shape[:2] != shapes[i]:
-                    raise OSError(f"image {sources[i]!r} decoded to {a.shape[:2]}, its header said {shapes[i]}")
-                arrs[i] = a
-        for i, a in arrs.items():
-            out[offsets[i]:offsets[i] + a.size].copy_(torch.from_numpy(a).reshape(-1))
-        self.stats["device"] += len(mine) - len(self.last_errors)
+        def launches():
+            o.jpegdec_tables(dev, self._host, total, n, nseg, ws)
+            o.jpegdec_entropy(dev, self._host, total, n, nseg, ws)
+            o.jpegdec_idct(dev, self._host, total, n, nseg, ws)
+            o.jpegdec_pixels(dev, self._host, total, n, nseg, ws, out, err)
+        self._launched(launches)
+
+
+# ------------------------------------------------------------------------------------------------ PNGs decoded on the device
+_PNG_SIGNATURE = b"\x89PNG\r\n\x1a\n"
+_PNG_CHANNELS = {0: 1, 2: 3, 3: 1, 4: 2, 6: 4}
+# Ancillary chunks that Pillow itself parses.  It raises for one that is shorter than it needs, and for text and profiles it has limits of
+# its own, so the parser passes over only what cannot change Pillow's outcome: these four at exactly their length, a tRNS of the right
+# length for its colour type, a little plain text; every chunk type Pillow has no handler for is read and dropped by it whatever it holds.
+_PNG_FIXED_LENGTH = {b"gAMA": 4, b"cHRM": 32, b"sRGB": 1, b"pHYs": 9}
+_PNG_NOT_MINE = (b"acTL", b"fcTL", b"fdAT", b"iCCP", b"zTXt", b"iTXt", b"eXIf")
+_PNG_MAX_TEXT = 1 << 16         # bytes of tEXt chunks in one file (Pillow's own limit on text is 64 MiB)
+PNG_MAX_PIXELS = 89478485       # Pillow's Image.MAX_IMAGE_PIXELS: above it Pillow warns or raises, so such a file stays Pillow's
+
+
+def parse_png(data: bytes) -> Optional[Dict]:
+    """The plan of a file the device decoder takes, or None ("not mine": Pillow decodes it).  Accepted: no interlace, compression and
+    filter method 0; colour type 0, 2, 4 or 6 at 8 bits, or colour type 3 at 1, 2, 4 or 8 bits with a PLTE of at least 1 << depth
+    entries (no index can leave it); every chunk's type four letters and its CRC right; IHDR first, PLTE before the IDATs, the IDATs in one
+    run, IEND last and nothing behind it; no unknown critical chunk; a zlib header with CM = 8, CINFO <= 7, FDICT = 0 and a valid FCHECK; rows of
+    at most _lib.PNGDEC_MAX_ROWBYTES bytes; raw and output bytes below 2^31.  The IDAT payloads are concatenated (empty and 1-byte ones
+    included) to the one zlib stream the device reads.  Anything else -- 16-bit samples, grey below 8 bits, Adam7, APNG, a truncated
+    file, another format -- is None.  Of the ancillary chunks Pillow parses, gAMA, cHRM, sRGB and pHYs pass at exactly their length, a
+    tRNS before the IDATs at the length of its colour type (RGB: 6; palette: 1 .. PLTE entries; none in grey or with alpha) and up to 64 KiB of
+    tEXt; acTL, fcTL, fdAT, iCCP, zTXt, iTXt and eXIf are None (Pillow raises for malformed ones and has limits of its own for the compressed
+    ones).  Chunk types Pillow has no handler for are passed over, as Pillow drops them unread.  None of these changes convert("RGB")."""
+    import zlib
+    n = len(data)
+    if n < 8 or data[:8] != _PNG_SIGNATURE:
+        return None
+    view = memoryview(data)
+    pos, ihdr, plte, idat, state, trns, text = 8, None, None, [], 0, False, 0      # state: 0 before the IDATs, 1 among them, 2 behind them
+    while True:
+        if pos + 12 > n:
+            return None
+        L, typ = int.from_bytes(data[pos:pos + 4], "big"), bytes(data[pos + 4:pos + 8])
+        if not typ.isalpha() or pos + 12 + L > n or zlib.crc32(view[pos + 4:pos + 8 + L]) != int.from_bytes(data[pos + 8 + L:pos + 12 + L], "big"):
+            return None
+        if ihdr is None:
+            if typ != b"IHDR" or L != 13:
+                return None
+            ihdr = (int.from_bytes(data[pos + 8:pos + 12], "big"), int.from_bytes(data[pos + 12:pos + 16], "big")) + tuple(data[pos + 16:pos + 21])
+        elif typ == b"IDAT":
+            if state == 2:
+                return None
+            state = 1
+            idat.append(view[pos + 8:pos + 8 + L])
+        else:
+            state = 2 if state else 0
+            if typ == b"IEND":
+                if L != 0 or pos + 12 != n:
+                    return None
+                break
+            if typ == b"PLTE":
+                if plte is not None or state != 0 or L == 0 or L % 3 or L > 768:
+                    return None
+                plte = bytes(view[pos + 8:pos + 8 + L])
+            elif not typ[0] & 0x20 or typ in _PNG_NOT_MINE:      # IHDR again or a critical chunk this parser does not know; APNG, compressed text, profiles
+                return None
+            elif typ in _PNG_FIXED_LENGTH:
+                if L != _PNG_FIXED_LENGTH[typ]:
+                    return None
+            elif typ == b"tRNS":                                 # before the IDATs, once; six bytes in an RGB file, at most one per PLTE entry in a palette file
+                if trns or state != 0 or not (L == 6 if ihdr[3] == 2 else ihdr[3] == 3 and plte is not None and 1 <= L <= len(plte) // 3):
+                    return None
+                trns = True
+            elif typ == b"tEXt":
+                text += L
+                if text > _PNG_MAX_TEXT:
+                    return None
+        pos += 12 + L
+    W, H, depth, color, compression, filtering, interlace = ihdr
+    if not idat or W < 1 or H < 1 or compression or filtering or interlace or color not in _PNG_CHANNELS:
+        return None
+    if depth != 8 and not (color == 3 and depth in (1, 2, 4)):
+        return None
+    if (color == 3 and (plte is None or len(plte) // 3 < 1 << depth)) or (color in (0, 4) and plte is not None):
+        return None
+    channels = _PNG_CHANNELS[color]
+    rowbytes = (W * channels * depth + 7) // 8
+    if rowbytes > _lib.PNGDEC_MAX_ROWBYTES or H * (1 + rowbytes) >= 1 << 31 or H * W * 3 >= 1 << 31 or H * W > PNG_MAX_PIXELS:
+        return None
+    stream = b"".join(idat)
+    if not 7 <= len(stream) < 1 << 31:
+        return None
+    cmf, flg = stream[0], stream[1]
+    if cmf & 15 != 8 or cmf >> 4 > 7 or flg & 0x20 or (cmf << 8 | flg) % 31:
+        return None
+    return {"format": "png", "H": H, "W": W, "color": color, "depth": depth, "bpp": max(1, channels * depth // 8), "rowbytes": rowbytes,
+            "palette": plte if color == 3 else b"", "wbits": (cmf >> 4) + 8, "stream": stream}
+
+
+class PngDecoder(_DecoderBase):
+    """PNG files -> packed uint8 (H, W, 3) tensors on `device`, pixel-identical to `_decode` (Pillow) for every source; the interface
+    and the guarantees of `JpegDecoder`.  The files `parse` accepts are decoded by csrc/pngdec.hip: their descriptors, palettes and zlib
+    streams go up in one copy from one pinned staging buffer, two launches (inflate; unfilter and convert) decode any number of files
+    together, one workgroup per file, and the host reads one error word per file.  Every other source, and every file the kernels
+    flagged (a stream zlib would reject, a filter byte above 4, a wrong Adler-32), goes through `_decode`."""
+
+    @staticmethod
+    def parse(data: bytes) -> Optional[Dict]:
+        return parse_png(data)
+
+    def _pack(self, plans: Sequence[Dict], out_offsets: Sequence[int]):
+        """The upload block of `plans` in the staging buffer -> (block bytes, files, workspace bytes)."""
+        n = len(plans)
+        imgs = (_lib.GanPngdecImage * n)()
+        o_pal, o_stream = self.ops.pngdec_block_offsets(n)
+        total = o_stream + sum(-(-len(p["stream"]) // 16) * 16 for p in plans)
+        host = self._grow("_host", total, host=True).numpy()
+        host[o_pal:o_stream] = 0
+        at = o_stream
+        for i, (p, im) in enumerate(zip(plans, imgs)):
+            im.H, im.W, im.color, im.depth, im.bpp, im.rowbytes, im.wbits = p["H"], p["W"], p["color"], p["depth"], p["bpp"], p["rowbytes"], p["wbits"]
+            im.pal_count, im.stream_off, im.stream_len, im.out_off = len(p["palette"]) // 3, at, len(p["stream"]), int(out_offsets[i])
+            end = at + -(-len(p["stream"]) // 16) * 16
+            host[at:at + len(p["stream"])] = np.frombuffer(p["stream"], np.uint8)
+            host[at + len(p["stream"]):end] = 0
+            host[o_pal + 768 * i:o_pal + 768 * i + len(p["palette"])] = np.frombuffer(p["palette"], np.uint8)
+            at = end
+        ws_bytes = self.ops.pngdec_bounds(imgs)
+        host[:o_pal] = np.frombuffer(imgs, np.uint8)
+        return total, n, ws_bytes
+
+    def _launch(self, plans: Sequence[Dict], offsets: Sequence[int], out: torch.Tensor, err: torch.Tensor) -> None:
+        total, n, ws_bytes = self._pack(plans, offsets)
+        self.last_block = (total, n)
+        ws = self._grow("_ws", ws_bytes)
+        dev, o = self._upload(total), self.ops
+
+        def launches():
+            o.pngdec_inflate(dev, self._host, total, n, ws)
+            o.pngdec_pixels(dev, self._host, total, n, ws, out, err)
+        self._launched(launches)
+
+
+class DeviceDecoder(_DecoderBase):
+    """Both device decoders behind one `decode`: every source is read once and goes by its content, not its suffix, to `self.jpeg`
+    (a JpegDecoder) or `self.png` (a PngDecoder); everything lands in one arena in one call, and the error words of both come back in one
+    download.  The sub-decoders keep their own `stats`
+    (`unsupported`: files of their format that their parser refused); `self.stats` counts all sources."""
+
+    def __init__(self, device, jpeg: bool = True, png: bool = True, ops=None):
+        if not (jpeg or png):
+            raise ValueError("DeviceDecoder: at least one of jpeg and png")
+        super().__init__(device, ops)
+        self.jpeg = JpegDecoder(self.device, ops=self.ops) if jpeg else None
+        self.png = PngDecoder(self.device, ops=self.ops) if png else None
+
+    def parse(self, data: bytes) -> Optional[Dict]:
+        plan = parse_jpeg(data) if self.jpeg is not None else None
+        return parse_png(data) if plan is None and self.png is not None else plan
+
+    def _groups(self, plans):
+        is_png = lambda p: p.get("format") == "png"
+        return [(self.jpeg, [i for i, p in enumerate(plans) if p is not None and not is_png(p)]),
+                (self.png, [i for i, p in enumerate(plans) if p is not None and is_png(p)])]
+
+    def _count(self, groups, loaded, rest):
+        super()._count(groups, loaded, rest)
+        self.stats["device"] += sum(len(idx) - len(d.last_errors) for d, idx in groups)
         self.stats["flagged"] += len(self.last_errors)
-        self.stats["unsupported"] += len(rest)
-        return [out[o:o + h * w * 3].view(h, w, 3) for o, (h, w) in zip(offsets, shapes)]
+        for i in rest:
+            head = loaded[i][0][:8]
+            if self.png is not None and head == _PNG_SIGNATURE:
+                self.png.stats["unsupported"] += 1
+            elif self.jpeg is not None and head[:2] == b"\xff\xd8":
+                self.jpeg.stats["unsupported"] += 1
 
 
 class ImageStore:
@@ -518,18 +721,21 @@ class ImageStore:
     `folder` only names the place in the error an empty list raises.
     device_decode: the baseline JPEGs among the files are decoded by a `JpegDecoder` on the device -- resident: read and parsed on the
     pool and decoded chunk by chunk (DECODE_CHUNK files) straight into the arena; streaming: `fetch` decodes its batch there.  Every
-    other file, and every file the decoder flags, still goes through Pillow; the store holds the same bytes either way."""
+    other file, and every file the decoder flags, still goes through Pillow; the store holds the same bytes either way.
+    device_png: the same for the PNGs among the files, with a `PngDecoder`; with both switches one `DeviceDecoder` takes both formats.
+    decoder: any object with JpegDecoder's `decode`, used instead of a new one when a switch is on."""
 
     def __init__(self, paths: Sequence, device, budget_bytes: Optional[int] = None, workers: Optional[int] = None, folder=None,
-                 device_decode: bool = False, decoder: Optional[JpegDecoder] = None):
+                 device_decode: bool = False, decoder=None, device_png: bool = False):
         self._pool = None
         self._decoder = None
         self.paths = [os.fspath(p) for p in paths]
         if not self.paths:
             raise FileNotFoundError(f"no images found in {os.fspath(folder) if folder is not None else 'the given (empty) list of paths'}")
         self.device = normalize_device(device)
-        if device_decode:
-            self._decoder = decoder if decoder is not None else JpegDecoder(self.device)
+        if device_decode or device_png:
+            make = (lambda dev: DeviceDecoder(dev)) if device_decode and device_png else PngDecoder if device_png else JpegDecoder
+            self._decoder = decoder if decoder is not None else make(self.device)
         self.workers = max(1, min(16, int(workers) if workers is not None else (os.cpu_count() or 1)))
         self._pool = ThreadPoolExecutor(self.workers)
         self._stage = self._stage_event = None

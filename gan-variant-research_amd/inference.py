@@ -210,9 +210,25 @@ def _jpeg_decoder(G, device):
     return dec
 
 
+def _folder_decoder(G, device, jpeg: bool, png: bool):
+    """The decoder of the folder path for the switches that are on, cached on the generator: a JpegDecoder, a PngDecoder, or one
+    DeviceDecoder for both formats."""
+    from . import dataio
+    if not png:
+        return _jpeg_decoder(G, device)
+    dev = dataio.normalize_device(device)
+    name, make = ("_device_dec", dataio.DeviceDecoder) if jpeg else ("_png_dec", dataio.PngDecoder)
+    dec = getattr(G, name, None)
+    if dec is None or dec.device != dev:
+        dec = make(dev)
+        object.__setattr__(G, name, dec)
+    return dec
+
+
 @torch.inference_mode()
 def stylize_folder(G, src_dir: str, out_dir: str, device: str = "cuda", img_size: int = 256, batch: int = 16, limit: Optional[int] = None,
-                   device_io: bool = False, device_jpeg: bool = False, io_threads: int = 1, device_decode: bool = False, decode_chunk: int = 256) -> int:
+                   device_io: bool = False, device_jpeg: bool = False, io_threads: int = 1, device_decode: bool = False, decode_chunk: int = 256,
+                   device_png: bool = False) -> int:
     """generate_folder.py:207-252 with PIL doing what torchvision's Resize(BILINEAR) / ToTensor / Normalize / ToPILImage do there.
     device_io: PIL only decodes and encodes; each photo is uploaded as uint8 HWC, `stylize_images` resizes, normalises, runs the
     generator and converts on the device, and one contiguous HWC download feeds PIL.  The files written are byte-identical.
@@ -221,13 +237,17 @@ def stylize_folder(G, src_dir: str, out_dir: str, device: str = "cuda", img_size
     at most 16 workers, as dataio.ImageStore's does.  device_decode (needs device_io): `dataio.JpegDecoder` decodes the baseline JPEGs
     on the device, `decode_chunk` files per call whatever `batch` is (its entropy stage has one lane per restart segment: many files in
     flight are its throughput), one chunk ahead on a side stream while the generator works on the previous one; other files, and files
-    the decoder flags, still go through PIL.  Same files either way."""
+    the decoder flags, still go through PIL.  device_png (needs device_io; independent of device_decode): the same for the PNGs, with
+    `dataio.PngDecoder` (one workgroup per file: again the files in flight are its throughput); with both switches one
+    `dataio.DeviceDecoder` reads every file once and sends it by its content.  Same files either way."""
     import numpy as np
     from PIL import Image
     if device_jpeg and not device_io:
         raise ValueError("device_jpeg=True needs device_io=True: the encoder reads the uint8 batch the device epilogue leaves")
     if device_decode and not device_io:
         raise ValueError("device_decode=True needs device_io=True: the decoder leaves the uint8 images the device input pipeline reads")
+    if device_png and not device_io:
+        raise ValueError("device_png=True needs device_io=True: the decoder leaves the uint8 images the device input pipeline reads")
     if decode_chunk < 1:
         raise ValueError(f"decode_chunk = {decode_chunk}: at least 1")
     if io_threads < 1:
@@ -266,7 +286,7 @@ def stylize_folder(G, src_dir: str, out_dir: str, device: str = "cuda", img_size
     def decoded_ahead():
         """The images of `paths` in chunks of decode_chunk files, the next chunk being decoded while the caller works on this one."""
         from concurrent.futures import ThreadPoolExecutor
-        dec = _jpeg_decoder(G, device)
+        dec = _folder_decoder(G, device, device_decode, device_png)
         cuda = dec.device.type == "cuda"
         side = torch.cuda.Stream(dec.device) if cuda else None
         main = torch.cuda.current_stream(dec.device) if cuda else None
@@ -287,11 +307,12 @@ def stylize_folder(G, src_dir: str, out_dir: str, device: str = "cuda", img_size
                 yield imgs
 
     try:
-        ready, chunks = [], decoded_ahead() if device_decode else None
+        on_device = device_decode or device_png
+        ready, chunks = [], decoded_ahead() if on_device else None
         for i in range(0, len(paths), batch):
             chunk = paths[i:i + batch]
             if device_io:
-                if device_decode:
+                if on_device:
                     while len(ready) < min(i + batch, len(paths)):
                         ready.extend(next(chunks))
                     imgs, ready[i:i + batch] = ready[i:i + batch], [None] * len(chunk)

@@ -613,6 +613,34 @@ class HipOps:
         self._now("gan_jpegdec_pixels", *self._jpegdec_args(blk_dev, blk_host, nbytes, n, nseg, ws), C.c_void_p(out.data_ptr()), out.numel(),
                   C.c_void_p(err.data_ptr()), self._s())
 
+    # ---- PNG decoder (csrc/pngdec.hip; dataio.PngDecoder owns the buffers); launched at once, like the JPEG decoder's entries
+    def pngdec_block_offsets(self, n):
+        """Byte offsets (palettes, first stream) of the upload block of n files."""
+        off = (C.c_int64 * 2)()
+        self._now("gan_pngdec_block_offsets", int(n), off)
+        return tuple(int(v) for v in off)
+
+    def pngdec_bounds(self, imgs) -> int:
+        """imgs: a ctypes array of _lib.GanPngdecImage; fills their raw_off and returns the workspace bytes."""
+        ws = C.c_int64(0)
+        self._now("gan_pngdec_bounds", C.cast(imgs, C.c_void_p), len(imgs), C.byref(ws))
+        return int(ws.value)
+
+    def _pngdec_args(self, blk_dev, blk_host, nbytes, n, ws):
+        assert blk_dev.dtype == torch.uint8 and blk_host.dtype == torch.uint8 and ws.dtype == torch.uint8 and blk_host.device.type == "cpu"
+        assert blk_dev.is_contiguous() and blk_host.is_contiguous() and ws.is_contiguous() and nbytes <= min(blk_dev.numel(), blk_host.numel())
+        return (C.c_void_p(blk_dev.data_ptr()), C.c_void_p(blk_host.data_ptr()), int(nbytes), int(n), C.c_void_p(ws.data_ptr()), ws.numel())
+
+    def pngdec_inflate(self, blk_dev, blk_host, nbytes, n, ws):
+        """The zlib streams -> the filtered scanlines in ws, one workgroup per file; overwrites the error words."""
+        self._now("gan_pngdec_inflate", *self._pngdec_args(blk_dev, blk_host, nbytes, n, ws), self._s())
+
+    def pngdec_pixels(self, blk_dev, blk_host, nbytes, n, ws, out, err):
+        """Scanlines -> packed (H, W, 3) at every file's out_off in `out`; err (int32 [n]) receives the error words."""
+        assert out.dtype == torch.uint8 and out.is_contiguous() and err.dtype == torch.int32 and err.is_contiguous() and err.numel() >= n
+        self._now("gan_pngdec_pixels", *self._pngdec_args(blk_dev, blk_host, nbytes, n, ws), C.c_void_p(out.data_ptr()), out.numel(),
+                  C.c_void_p(err.data_ptr()), self._s())
+
     def view_copy(self, src: View, dst: View, halo_mode) -> Op:
         return self._call("gan_view_copy", self._v(src), self._v(dst), halo_mode, self._s())
 

@@ -543,6 +543,74 @@ int gan_jpegdec_idct(const void* blk_dev, const void* blk_host, int64_t blk_byte
 int gan_jpegdec_pixels(const void* blk_dev, const void* blk_host, int64_t blk_bytes, int n, int nseg, void* ws, int64_t ws_bytes, uint8_t* out,
                        int64_t out_bytes, int32_t* err, void* stream);
 
+/* ---- PNG decoder on the device: the pixels Image.open(p).convert("RGB") gives, for the files a host parser accepted: no interlace,
+ *      compression and filter method 0, colour type 0, 2, 4 or 6 at 8 bits (grey is replicated, alpha dropped, no compositing) or colour
+ *      type 3 at 1, 2, 4 or 8 bits with a PLTE that covers every index its depth can give (a plain lookup; tRNS changes nothing).  The
+ *      parser has checked every chunk's CRC, concatenated the IDAT payloads to one zlib stream and checked its two header bytes.
+ *      Integer arithmetic only.  The stream is untrusted: every loop of the kernels is bounded by the stream's bit count or by the raw
+ *      byte count H (1 + rowbytes) of the descriptor, every load lies inside the file's 16-byte-padded stream, every store address comes
+ *      from counters clamped to the descriptor's extent, and an irregularity sets bits of the file's error word (GAN_PNGDEC_ERR_*) and
+ *      ends that file's work; the caller sends such a file to the host decoder.  No atomics: the same bytes come out every time.
+ *
+ *      One upload block carries everything (all offsets from its start, n files):
+ *        gan_pngdec_image [n] | uint8 palettes [n][768] (R, G, B per entry, zeros behind pal_count) | zlib streams, each at a multiple of 16
+ *      gan_pngdec_block_offsets gives the byte offsets.  Workspace (16-byte aligned, gan_pngdec_bounds bytes): error words int32 [n] |
+ *      per file the inflated bytes (the filtered scanlines: H rows of one filter byte and rowbytes bytes), each area at a multiple of 256.
+ *      GAN_PNGDEC_MAX_ROWBYTES: the longest row the unfilter kernel's two LDS rows hold, 4096 pixels of RGBA.
+ *      Refused with a message, before any launch: a NULL pointer, n outside 1 .. 65535, H or W below 1, a colour type / depth outside
+ *      the class above, bpp or rowbytes that do not belong to them, rowbytes above GAN_PNGDEC_MAX_ROWBYTES, H (1 + rowbytes) or H W 3
+ *      at or above 2^31, a palette of fewer entries than 1 << depth or more than 256, window bits outside 8 .. 15, a stream that is
+ *      shorter than 7 bytes, not at a multiple of 16 or not inside the block, a block of 2^31 bytes or more, a workspace that is too
+ *      small or not 16-byte aligned, raw or output offsets that leave their buffers. */
+#define GAN_PNGDEC_MAX_ROWBYTES 16384
+typedef struct gan_pngdec_image {
+  int32_t H, W;
+  int32_t color, depth;              /* PNG colour type 0 | 2 | 3 | 4 | 6 and bit depth (8; 1 | 2 | 4 | 8 for colour type 3) */
+  int32_t bpp, rowbytes;             /* the filters' pixel step in bytes, max(1, channels depth / 8); ceil(W channels depth / 8) */
+  int32_t pal_count;                 /* PLTE entries (colour type 3), else 0 */
+  int32_t wbits;                     /* CINFO + 8 of the zlib header: no distance may exceed 1 << wbits */
+  int32_t stream_off, stream_len;    /* the whole zlib stream in the block: 2 header bytes, deflate data, Adler-32 */
+  int32_t reserved[2];
+  int64_t raw_off;                   /* bytes into the workspace (filled by gan_pngdec_bounds) */
+  int64_t out_off;                   /* bytes into `out` of gan_pngdec_pixels: where the packed (H, W, 3) image goes */
+} gan_pngdec_image;
+#define GAN_PNGDEC_ERR_BTYPE 1       /* block type 3 */
+#define GAN_PNGDEC_ERR_STORED 2      /* a stored block whose LEN is not ~NLEN */
+#define GAN_PNGDEC_ERR_COUNTS 4      /* more than 286 literal/length or more than 30 distance code lengths */
+#define GAN_PNGDEC_ERR_REPEAT 8      /* a code-length repeat with no previous length, or one that runs past HLIT + HDIST */
+#define GAN_PNGDEC_ERR_OVER 16       /* an over-subscribed set of code lengths */
+#define GAN_PNGDEC_ERR_INCOMPLETE 32 /* an incomplete set, other than a single literal/length or distance code of length 1 */
+#define GAN_PNGDEC_ERR_NOEOB 64      /* no end-of-block code */
+#define GAN_PNGDEC_ERR_SYMBOL 128    /* literal/length symbol 286 | 287, distance symbol 30 | 31, or bits that are no code at all */
+#define GAN_PNGDEC_ERR_DIST 256      /* a distance beyond the bytes produced so far, or beyond the window the header declares */
+#define GAN_PNGDEC_ERR_END 512       /* bits needed beyond the stream */
+#define GAN_PNGDEC_ERR_MORE 1024     /* more output than H (1 + rowbytes) */
+#define GAN_PNGDEC_ERR_LESS 2048     /* less output than that at the final block */
+#define GAN_PNGDEC_ERR_LEFT 4096     /* bytes between the final block and the Adler-32 */
+#define GAN_PNGDEC_ERR_FILTER 8192   /* a filter byte above 4 */
+#define GAN_PNGDEC_ERR_ADLER 16384   /* the Adler-32 of the inflated bytes is not the stream's */
+/* Host only.  Byte offsets of the block's parts for n files: off[0] palettes, off[1] the first stream. */
+int gan_pngdec_block_offsets(int n, int64_t* off);
+/* Host only.  Fills raw_off of imgs[0 .. n-1] (host memory) and gives the workspace size. */
+int gan_pngdec_bounds(gan_pngdec_image* imgs, int n, int64_t* ws_bytes);
+/* One 64-lane workgroup per file: RFC 1951 inflate of stored, fixed and dynamic blocks.  The tables of the current block (a 9-bit
+ * lookahead table plus canonical max-code / offset arrays and the symbols in code order) and the 32 KiB window live in LDS; the
+ * wave builds the tables together.  Every lane carries the same 64-bit bit buffer, refilled from aligned 8-byte chunks with the next
+ * chunk already requested, so a symbol, a length and a distance are wave-uniform without an exchange, and the whole wave copies a
+ * match inside the window (byte k of a match comes from k mod distance: an overlapping match reads only bytes that were there before
+ * it).  The window is written to the file's raw area 16 KiB at a time, 16 bytes per lane; nothing is read back from there.
+ * Overwrites the file's error word.  blk_host: the host copy of the block's descriptors, which every entry validates. */
+int gan_pngdec_inflate(const void* blk_dev, const void* blk_host, int64_t blk_bytes, int n, void* ws, int64_t ws_bytes, void* stream);
+/* One 64-lane workgroup per file, the previous and the current row in LDS, rows in order: filter 0 None, 1 Sub, 2 Up, 3 Average
+ * ((left + up) >> 1 in 9 bits), 4 Paeth (ties: left, then up); the row above the first is zero, and so is the pixel left of the
+ * first.  None and Up run over all bytes at once; Sub is a prefix sum per byte of the pixel (every lane sums its own stretch of pixels, then adds what the
+ * stretches in front of it came to); Average and Paeth walk the row with one lane per byte of the pixel.  Then 1, 2
+ * and 4-bit indices are unpacked most significant bit first (the padding bits of a row are not looked at), and palette lookup, grey
+ * replication or alpha drop give image i packed (H, W, 3) at out + out_off.  The Adler-32 is summed row by row over the bytes as they
+ * are read.  A file whose error word is set is left alone.  err (may be NULL): int32 [n] on the device, receives the error words. */
+int gan_pngdec_pixels(const void* blk_dev, const void* blk_host, int64_t blk_bytes, int n, void* ws, int64_t ws_bytes, uint8_t* out,
+                      int64_t out_bytes, int32_t* err, void* stream);
+
 /* ---- losses.  Every loss writes its value to *loss (device fp32, overwritten) and the gradient wrt its input.
  *      hinge: adv_hinge.py:6-62 (mode 0: mean relu(1-x), 1: mean relu(1+x), 2: -mean x), scaled by `scale`;
  *      lsgan/bce: Basic_GAN/src/losses.py:5-22 (mode 3: mse vs target, 4: bce-with-logits vs target in {0,1});

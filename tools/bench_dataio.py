@@ -9,6 +9,7 @@
     streaming           dataio.ImageStore decoding every batch on its thread pool, in series
     streaming+overlap   the same, overlapped
     streaming+dd, streaming+dd+overlap   (--device-decode) the streaming store with device_decode=True: dataio.JpegDecoder decodes every batch
+                        (--device-png: the folders hold the same images as PNGs and the +dd stores are built with device_png=True: dataio.PngDecoder)
 
 
 over N random 256x256 JPEGs per domain written with Pillow into a temporary folder.  Every mode is warmed up, then timed in ROUNDS
@@ -16,7 +17,7 @@ alternating rounds of STEPS steps (a multiple of the lazy-R1 period, so every wi
 the median round and [min .. max], one line per store build, and what the resident store adds to the synthetic and to the fixed rounds
 against those rounds' own spread (the overlap was decided by it).
 
-usage: bench_dataio.py [--n 512] [--steps 32] [--rounds 5] [--device-decode]
+usage: bench_dataio.py [--n 512] [--steps 32] [--rounds 5] [--device-decode | --device-png]
 """
 import argparse
 import itertools
@@ -38,7 +39,7 @@ from gan_variant_research_amd import cut as C, dataio, train_cutpp as T  # noqa:
 B, S = 16, 256
 
 
-def write_jpegs(folder, n, seed):
+def write_jpegs(folder, n, seed, png=False):
     """n photo-like 256x256 JPEGs (low-frequency colour plus noise: a decode cost like a photograph's, not like white noise's)."""
     from PIL import Image
     os.makedirs(folder)
@@ -51,7 +52,8 @@ def write_jpegs(folder, n, seed):
 
     def write(i):
         noise = np.random.default_rng([seed, i]).integers(-20, 21, (S, S, 3), dtype=np.int16)
-        Image.fromarray(np.clip(bases[i % 8] + noise, 0, 255).astype(np.uint8)).save(os.path.join(folder, f"{i:05d}.jpg"), quality=90)
+        img = Image.fromarray(np.clip(bases[i % 8] + noise, 0, 255).astype(np.uint8))
+        img.save(os.path.join(folder, f"{i:05d}.png")) if png else img.save(os.path.join(folder, f"{i:05d}.jpg"), quality=90)
     with ThreadPoolExecutor(min(16, os.cpu_count() or 1)) as pool:
         list(pool.map(write, range(n)))
     return sorted(os.path.join(folder, f) for f in os.listdir(folder))
@@ -63,7 +65,10 @@ def main():
     ap.add_argument("--steps", type=int, default=32, help="steps per timed window")
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--device-decode", action="store_true", help="also build both stores with device_decode=True and time the streaming one")
+    ap.add_argument("--device-png", action="store_true", help="the same over PNG folders, the +dd stores built with device_png=True")
     args = ap.parse_args()
+    switch = "device_png" if args.device_png else "device_decode"
+    args.device_decode = args.device_decode or args.device_png
     assert torch.cuda.is_available(), "bench_dataio needs the GPU"
     dev = torch.device("cuda")
     cfg = default_config()
@@ -73,13 +78,13 @@ def main():
 
     with tempfile.TemporaryDirectory() as tmp:
         t0 = time.perf_counter()
-        paths = {d: write_jpegs(os.path.join(tmp, d), args.n, k) for k, d in enumerate(("photos", "monet"))}
-        print(json.dumps({"wrote": f"2 x {args.n} JPEGs {S}x{S}", "seconds": round(time.perf_counter() - t0, 2)}), flush=True)
+        paths = {d: write_jpegs(os.path.join(tmp, d), args.n, k, png=args.device_png) for k, d in enumerate(("photos", "monet"))}
+        print(json.dumps({"wrote": f"2 x {args.n} {'PNGs' if args.device_png else 'JPEGs'} {S}x{S}", "seconds": round(time.perf_counter() - t0, 2)}), flush=True)
         stores = {}
         kinds = [("resident", None, False), ("streaming", 1, False)] + ([("resident+dd", None, True), ("streaming+dd", 1, True)] if args.device_decode else [])
         for kind, budget, dd in kinds:
             t0 = time.perf_counter()
-            stores[kind] = [dataio.ImageStore(paths[d], dev, budget_bytes=budget, **({"device_decode": True} if dd else {})) for d in ("photos", "monet")]
+            stores[kind] = [dataio.ImageStore(paths[d], dev, budget_bytes=budget, **({switch: True} if dd else {})) for d in ("photos", "monet")]
             torch.cuda.synchronize()
             st = stores[kind][0]
             assert st.resident == kind.startswith("resident")

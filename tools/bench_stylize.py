@@ -7,10 +7,13 @@
 (d) JPEG decode (--decode): the same two folders at batch 16 with device_jpeg: PIL decoding serially and on a pool (io_threads 4, 16)
     against the device decoder (device_decode, decode_chunk 16 / 64 / 256; other formats still go through PIL); same files every mode
 
+(e) PNG decode (--png): the mixed PNGs and 256 PNGs of 256 x 256 (the JPEG folder's images) at batch 16 with device_jpeg: PIL decoding
+    serially and on a pool (io_threads 4, 16) against the device decoder (device_png, decode_chunk 16 / 64 / 256); same files every mode
+
 Every shape is warmed up; the two paths are then timed in rotation for --rounds rounds (a host clock around work that ends in a device
 synchronise: each call ends in a download); the median round and the spread (min .. max) are reported.  The outputs of the two paths
 are compared before anything is timed.
-usage: bench_stylize.py [--size 256] [--batches 1,4,16] [--calls 40] [--rounds 5] [--photos 64] [--out FILE] [--jpeg] [--only-jpeg] [--decode] [--only-decode]
+usage: bench_stylize.py [--size 256] [--batches 1,4,16] [--calls 40] [--rounds 5] [--photos 64] [--out FILE] [--jpeg] [--only-jpeg] [--decode] [--only-decode] [--png] [--only-png]
 """
 import argparse
 import os
@@ -40,8 +43,8 @@ def make_folder(root: Path, n: int, seed: int = 0):
         Image.fromarray(img).save(root / ("sub" if i % 4 == 0 else ".") / f"p{i:03d}.png")
 
 
-def make_jpeg_folder(root: Path, n: int, size: int = 256, seed: int = 1):
-    """n JPEGs of size x size under root: the realistic input (the reference's photo_jpg folder)."""
+def make_jpeg_folder(root: Path, n: int, size: int = 256, seed: int = 1, png: bool = False):
+    """n JPEGs of size x size under root: the realistic input (the reference's photo_jpg folder).  png: the same images as PNGs."""
     from PIL import Image
     rng = np.random.default_rng(seed)
     root.mkdir(parents=True, exist_ok=True)
@@ -49,7 +52,10 @@ def make_jpeg_folder(root: Path, n: int, size: int = 256, seed: int = 1):
     for i in range(n):
         base = np.stack([127 + 120 * np.sin(yy / (11.0 + i % 7) + c + i) * np.cos(xx / (19.0 + i % 5) - c) for c in range(3)], -1)
         img = np.clip(base + rng.integers(-20, 21, (size, size, 3)), 0, 255).astype(np.uint8)
-        Image.fromarray(img).save(root / f"q{i:03d}.jpg", quality=90)
+        if png:
+            Image.fromarray(img).save(root / f"q{i:03d}.png")
+        else:
+            Image.fromarray(img).save(root / f"q{i:03d}.jpg", quality=90)
 
 
 JPEG_MODES = (("a  device_io, serial PIL", dict()), ("b  PIL pool, io_threads 4", dict(io_threads=4)), ("b  PIL pool, io_threads 16", dict(io_threads=16)),
@@ -63,35 +69,43 @@ DECODE_MODES = (("a  PIL serial", dict()), ("b  PIL pool, io_threads 4", dict(io
                 ("d  device_decode, chunk 256, io_threads 4", dict(device_decode=True, decode_chunk=256, io_threads=4)))
 
 
-def decode_section(G, dev, S, rounds, photos, tmp: Path):
-    """(d): every mode writes the same files (checked first), then the modes run in rotation; images/s, median [min .. max]."""
-    lines = [f"# (d) images/s over one pass of a folder, batch 16, {S}x{S}, device_jpeg, decode and encode included; median of {rounds} alternating rounds [min .. max]"]
-    if not (tmp / "jpegs").exists():
-        make_jpeg_folder(tmp / "jpegs", 256, S)
-    for label, src, n in ((f"{photos} PNGs of mixed sizes", tmp / "photos", photos), (f"256 JPEGs of {S}x{S}", tmp / "jpegs", 256)):
+PNG_MODES = tuple((name.replace("device_decode", "device_png").replace("d  ", "e  "), {("device_png" if k == "device_decode" else k): v for k, v in kw.items()})
+                  for name, kw in DECODE_MODES)
+
+
+def decode_section(G, dev, S, rounds, photos, tmp: Path, png: bool = False):
+    """(d), or (e) with png: every mode writes the same files (checked first), then the modes run in rotation; images/s, median [min .. max]."""
+    tag, MODES, attr = ("e", PNG_MODES, "_png_dec") if png else ("d", DECODE_MODES, "_jpeg_dec")
+    lines = [f"# ({tag}) images/s over one pass of a folder, batch 16, {S}x{S}, device_jpeg, decode and encode included; median of {rounds} alternating rounds [min .. max]"]
+    second = (f"256 PNGs of {S}x{S}", tmp / "pngs", 256) if png else (f"256 JPEGs of {S}x{S}", tmp / "jpegs", 256)
+    if not second[1].exists():
+        make_jpeg_folder(second[1], 256, S, png=png)
+    for label, src, n in ((f"{photos} PNGs of mixed sizes", tmp / "photos", photos), second):
+        d = tag
+
         def mode(i, kw):
             def run():
                 torch.cuda.synchronize()
                 t0 = time.perf_counter()
-                assert I.stylize_folder(G, str(src), str(tmp / f"d_{src.name}_{i}"), device=str(dev), img_size=S, batch=16, device_io=True, device_jpeg=True, **kw) == n
+                assert I.stylize_folder(G, str(src), str(tmp / f"{d}_{src.name}_{i}"), device=str(dev), img_size=S, batch=16, device_io=True, device_jpeg=True, **kw) == n
                 torch.cuda.synchronize()
                 return n / (time.perf_counter() - t0)
             return run
-        paths = {name: mode(i, kw) for i, (name, kw) in enumerate(DECODE_MODES)}
+        paths = {name: mode(i, kw) for i, (name, kw) in enumerate(MODES)}
         for fn in paths.values():
             fn()
-        outs = [{p.name: p.read_bytes() for p in (tmp / f"d_{src.name}_{i}").rglob("*.jpg")} for i in range(len(DECODE_MODES))]
+        outs = [{p.name: p.read_bytes() for p in (tmp / f"{d}_{src.name}_{i}").rglob("*.jpg")} for i in range(len(MODES))]
         assert len(outs[0]) == n and all(o == outs[0] for o in outs), "the modes wrote different files"
         times = rotate(paths, rounds)
-        lines.append(f"# {label}; the device decoder's counts since the start of the section: {G._jpeg_dec.stats}")
+        lines.append(f"# {label}; the device decoder's counts since the start of the section: {getattr(G, attr).stats}")
         for name, v in times.items():
-            lines.append(f"(d) {name:44s} {statistics.median(v):8.1f} images/s [{min(v):8.1f} .. {max(v):8.1f}]")
+            lines.append(f"({d}) {name:44s} {statistics.median(v):8.1f} images/s [{min(v):8.1f} .. {max(v):8.1f}]")
         best_pool = max(max(times[k]) for k in times if k.startswith("b"))
         for name, v in times.items():
-            if name.startswith("d"):
+            if name.startswith(d):
                 verdict = "beats" if min(v) > best_pool else "does not beat"
-                lines.append(f"(d) {name[3:]}: {verdict} the PIL pools beyond both spreads (its min {min(v):.1f} vs their max {best_pool:.1f})")
-        for ln in lines[-(2 * len(DECODE_MODES) - 2):]:
+                lines.append(f"({d}) {name[3:]}: {verdict} the PIL pools beyond both spreads (its min {min(v):.1f} vs their max {best_pool:.1f})")
+        for ln in lines[-(2 * len(MODES) - 2):]:
             print(ln, flush=True)
     return lines
 
@@ -157,8 +171,11 @@ def main():
     ap.add_argument("--only-jpeg", action="store_true", help="run section (c) alone")
     ap.add_argument("--decode", action="store_true", help="also run section (d)")
     ap.add_argument("--only-decode", action="store_true", help="run section (d) alone")
+    ap.add_argument("--png", action="store_true", help="also run section (e)")
+    ap.add_argument("--only-png", action="store_true", help="run section (e) alone")
     a = ap.parse_args()
     a.decode = a.decode or a.only_decode
+    a.png = a.png or a.only_png
     assert torch.cuda.is_available(), "bench_stylize.py measures on the GPU"
     dev, S = torch.device("cuda:0"), a.size
     C.set_seed(0)
@@ -167,9 +184,10 @@ def main():
         p.requires_grad_(False)
     G.compute_dtype = BF16
     lines = [f"# tools/bench_stylize.py --size {S} --batches {a.batches} --calls {a.calls} --rounds {a.rounds} --photos {a.photos}"
-             + (" --only-jpeg" if a.only_jpeg else " --jpeg" if a.jpeg else "") + (" --only-decode" if a.only_decode else " --decode" if a.decode else ""),
+             + (" --only-jpeg" if a.only_jpeg else " --jpeg" if a.jpeg else "") + (" --only-decode" if a.only_decode else " --decode" if a.decode else "")
+             + (" --only-png" if a.only_png else " --png" if a.png else ""),
              f"# generator ngf 64, 9 blocks, bf16 operands, eager launches; median of {a.rounds} alternating rounds [min .. max]"]
-    only = a.only_jpeg or a.only_decode
+    only = a.only_jpeg or a.only_decode or a.only_png
     if not only:
         lines.append(f"# (a) ms per call of {a.calls} consecutive calls, each ending in the download of the uint8 HWC batch to the host")
     old_out = lambda x: I.stylize(G, x).cpu().permute(0, 2, 3, 1).contiguous()
@@ -218,6 +236,8 @@ def main():
             lines += jpeg_section(G, dev, S, a.rounds, a.photos, tmp)
         if a.decode:
             lines += decode_section(G, dev, S, a.rounds, a.photos, tmp)
+        if a.png:
+            lines += decode_section(G, dev, S, a.rounds, a.photos, tmp, png=True)
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
         with open(a.out, "w") as f:
