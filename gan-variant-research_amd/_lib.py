@@ -16,6 +16,7 @@ ACT_NONE, ACT_RELU, ACT_LRELU, ACT_TANH = 0, 1, 2, 3
 TAP_PAD = 1 << 30            # GAN_TAP_PAD: the tapoff entry of a padded tap (zero weights; the generic kernel reads zeros for it)
 HALO_NONE, HALO_ZERO, HALO_REFLECT, HALO_REPLICATE = 0, 1, 2, 3
 RESIZE_BILINEAR, RESIZE_BICUBIC = 2, 3      # Pillow's filter ids (Image.BILINEAR, Image.BICUBIC)
+FEAT_F32, FEAT_F64 = 0, 1    # GAN_FEAT_*: element type of a feature matrix of the evaluation kernels
 
 vp, i32, i64, f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_float
 
@@ -146,6 +147,7 @@ PROTOTYPES = {
     "gan_resize_ksize_filter": (C.c_int, [C.c_int, C.c_int, C.c_int]),
     "gan_resize_coeffs_filter": (C.c_int, [C.c_int, C.c_int, C.c_int, vp, vp, C.c_int]),
     "gan_input_pipeline_filter": (C.c_int, [vp, vp, C.c_int, vp, C.c_int, C.c_int, vp, C.c_int, vp, vp, vp, vp]),
+    "gan_input_pipeline_u8": (C.c_int, [vp, vp, C.c_int, vp, C.c_int, C.c_int, vp, C.c_int, vp, vp, vp, vp]),
     "gan_jpeg_bounds": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(i64), C.POINTER(i64)]),
     "gan_jpeg_blocks": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, i64, vp, vp]),
     "gan_jpeg_tables": (C.c_int, [vp, C.c_int, vp, vp, vp]),
@@ -160,6 +162,10 @@ PROTOTYPES = {
     "gan_pngdec_bounds": (C.c_int, [vp, C.c_int, C.POINTER(i64)]),
     "gan_pngdec_inflate": (C.c_int, [vp, vp, i64, C.c_int, vp, i64, vp]),
     "gan_pngdec_pixels": (C.c_int, [vp, vp, i64, C.c_int, vp, i64, vp, i64, vp, vp]),
+    "gan_feat_moments": (C.c_int, [vp, C.c_int, i64, i64, i64, vp, vp, vp, vp, vp, vp, vp]),
+    "gan_gram_f64": (C.c_int, [vp, C.c_int, i64, vp, C.c_int, i64, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, C.c_double, vp, i64, vp]),
+    "gan_cos_rowmin_bounds": (C.c_int, [C.c_int, C.c_int, C.POINTER(i64)]),
+    "gan_cos_rowmin": (C.c_int, [vp, C.c_int, i64, vp, C.c_int, i64, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, C.c_double, C.c_int, vp, i64, vp, vp, vp]),
     "gan_spectral_norm_ws_floats": (C.c_int64, [C.c_int, C.c_int]),
     "gan_spectral_norm_fwd": (C.c_int, [vp, C.c_int, C.c_int, vp, vp, C.c_int, C.c_float, vp, vp, vp, vp]),
     "gan_spectral_norm_bwd": (C.c_int, [vp, vp, vp, vp, vp, C.c_int, C.c_int, vp, vp, vp]),

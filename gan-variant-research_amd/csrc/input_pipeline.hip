@@ -166,6 +166,17 @@ __global__ __launch_bounds__(256) void input_finish_kernel(const gan_input_job* 
   for (int k = 0; k < 3; ++k) o[(int64_t)k * S * S] = __fdiv_rn(__fsub_rn(__fdiv_rn((float)c[k], 255.f), 0.5f), 0.5f);
 }
 
+// ---- the same flip, no normalisation: img [B][S][S][4] -> out uint8 [B][3][S][S] (what a feature extractor takes)
+__global__ __launch_bounds__(256) void input_finish_u8_kernel(const gan_input_job* __restrict__ jobs, const uint8_t* __restrict__ img, int S, uint8_t* __restrict__ out) {
+  const int flip = jobs[blockIdx.y].flip;
+  const int idx = blockIdx.x * 256 + threadIdx.x;
+  if (idx >= S * S) return;
+  const int y = idx / S, x = idx - y * S;
+  const uchar4 v = reinterpret_cast<const uchar4*>(img)[((int64_t)blockIdx.y * S + y) * S + (flip ? S - 1 - x : x)];
+  uint8_t* o = out + (int64_t)blockIdx.y * 3 * S * S + idx;
+  o[0] = v.x; o[(int64_t)S * S] = v.y; o[(int64_t)2 * S * S] = v.z;
+}
+
 // ---- output epilogue: view interior -> packed [B][H][W][C] uint8, the reference's _to_uint8 (generate_folder.py:183-185) fused with the
 // NCHW -> HWC turn PIL needs.  Each lane takes a run of four pixels of one row: four 16-byte loads issued back to back (a whole bf16
 // pixel of 8 channels, or the first four fp32 channels; C <= 4, so nothing past them is needed), then PACKED (C == 3, W % 4 == 0, dst
@@ -287,10 +298,11 @@ extern "C" int gan_resize_coeffs(int in_size, int out_size, int32_t* bounds, int
   return gan_resize_coeffs_filter(in_size, out_size, GAN_RESIZE_BICUBIC, bounds, kk, ksize);
 }
 
-extern "C" int gan_input_pipeline_filter(const gan_input_job* jobs_dev, const gan_input_job* jobs_host, int B, const int32_t* tables_dev, int S,
-                                         int filter, uint8_t* tmp, int tmp_rows, uint8_t* img, int32_t* mean_ws, float* out, void* stream) {
+// The launch sequence of both entries below: `out` (fp32, normalised) or `out_u8` (the bytes), whichever is given.
+static int input_pipeline_launch(const gan_input_job* jobs_dev, const gan_input_job* jobs_host, int B, const int32_t* tables_dev, int S,
+                                 int filter, uint8_t* tmp, int tmp_rows, uint8_t* img, int32_t* mean_ws, float* out, uint8_t* out_u8, void* stream) {
   GAN_CHECK(filter == GAN_RESIZE_BILINEAR || filter == GAN_RESIZE_BICUBIC, "input_pipeline: unknown filter %d (BILINEAR = 2, BICUBIC = 3)", filter);
-  GAN_CHECK(jobs_dev && jobs_host && tables_dev && tmp && img && mean_ws && out && B > 0 && S > 0, "input_pipeline: null pointer or empty batch");
+  GAN_CHECK(jobs_dev && jobs_host && tables_dev && tmp && img && mean_ws && (out || out_u8) && B > 0 && S > 0, "input_pipeline: null pointer or empty batch");
   int max_rows = 0;
   bool slot_used[4] = {false, false, false, false}, slot_mean[4] = {false, false, false, false};
   for (int b = 0; b < B; ++b) {
@@ -318,9 +330,20 @@ extern "C" int gan_input_pipeline_filter(const gan_input_job* jobs_dev, const ga
     if (slot_mean[slot]) hipLaunchKernelGGL(input_gray_mean_kernel, dim3(B), dim3(1024), 0, s, img, S, mean_ws);
     hipLaunchKernelGGL(input_jitter_kernel, dim3(gp, B), dim3(256), 0, s, jobs_dev, img, S, slot, mean_ws);
   }
-  hipLaunchKernelGGL(input_finish_kernel, dim3(gp, B), dim3(256), 0, s, jobs_dev, img, S, out);
+  if (out) hipLaunchKernelGGL(input_finish_kernel, dim3(gp, B), dim3(256), 0, s, jobs_dev, img, S, out);
+  else hipLaunchKernelGGL(input_finish_u8_kernel, dim3(gp, B), dim3(256), 0, s, jobs_dev, img, S, out_u8);
   GAN_LAUNCH_CHECK();
   return 0;
+}
+
+extern "C" int gan_input_pipeline_filter(const gan_input_job* jobs_dev, const gan_input_job* jobs_host, int B, const int32_t* tables_dev, int S,
+                                         int filter, uint8_t* tmp, int tmp_rows, uint8_t* img, int32_t* mean_ws, float* out, void* stream) {
+  return input_pipeline_launch(jobs_dev, jobs_host, B, tables_dev, S, filter, tmp, tmp_rows, img, mean_ws, out, nullptr, stream);
+}
+
+extern "C" int gan_input_pipeline_u8(const gan_input_job* jobs_dev, const gan_input_job* jobs_host, int B, const int32_t* tables_dev, int S,
+                                     int filter, uint8_t* tmp, int tmp_rows, uint8_t* img, int32_t* mean_ws, uint8_t* out, void* stream) {
+  return input_pipeline_launch(jobs_dev, jobs_host, B, tables_dev, S, filter, tmp, tmp_rows, img, mean_ws, nullptr, out, stream);
 }
 
 extern "C" int gan_input_pipeline(const gan_input_job* jobs_dev, const gan_input_job* jobs_host, int B, const int32_t* tables_dev, int S,

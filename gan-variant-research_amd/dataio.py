@@ -144,6 +144,14 @@ class InputPipeline:
         return t
 
     def run(self, images: Sequence[torch.Tensor], jobs: Sequence[Dict], out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        return self._run(images, jobs, out, torch.float32, "gan_input_pipeline_filter")
+
+    def run_u8(self, images: Sequence[torch.Tensor], jobs: Sequence[Dict], out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The same transform, left as bytes: (B, 3, S, S) uint8, what PIL's image holds after the jobs' crop, resize, flip and jitter
+        (the evaluation loader's `to_tensor(img) * 255` as uint8, EVAL/eval/datasets.py:52-66)."""
+        return self._run(images, jobs, out, torch.uint8, "gan_input_pipeline_u8")
+
+    def _run(self, images, jobs, out, dtype, entry) -> torch.Tensor:
         B, S = len(jobs), self.S
         if B == 0 or B != len(images) or B > self.max_batch:
             raise GanError(f"input pipeline: {len(images)} images, {B} jobs, max_batch {self.max_batch}")
@@ -204,12 +212,12 @@ class InputPipeline:
             self._events[t] = torch.cuda.Event()
         self._events[t].record()
         if out is None:
-            out = torch.empty(B, 3, S, S, dtype=torch.float32, device=self.device)
-        assert out.shape == (B, 3, S, S) and out.dtype == torch.float32 and out.is_contiguous() and out.device == self.device
-        rc = self.lib.gan_input_pipeline_filter(self._dev.data_ptr(), hv.ctypes.data, B, self._dev.data_ptr() + jbytes, S, self.filter,
-                                                self._tmp.data_ptr(), self.max_rows, self._img.data_ptr(), self._mean.data_ptr(), out.data_ptr(),
-                                                ts.cuda_stream)
-        _lib.check(rc, "gan_input_pipeline_filter")
+            out = torch.empty(B, 3, S, S, dtype=dtype, device=self.device)
+        assert out.shape == (B, 3, S, S) and out.dtype == dtype and out.is_contiguous() and out.device == self.device
+        rc = getattr(self.lib, entry)(self._dev.data_ptr(), hv.ctypes.data, B, self._dev.data_ptr() + jbytes, S, self.filter,
+                                      self._tmp.data_ptr(), self.max_rows, self._img.data_ptr(), self._mean.data_ptr(), out.data_ptr(),
+                                      ts.cuda_stream)
+        _lib.check(rc, entry)
         return out
 
 

@@ -641,6 +641,75 @@ class HipOps:
         self._now("gan_pngdec_pixels", *self._pngdec_args(blk_dev, blk_host, nbytes, n, ws), C.c_void_p(out.data_ptr()), out.numel(),
                   C.c_void_p(err.data_ptr()), self._s())
 
+    # ---- evaluation (csrc/mifid.hip; evaluate.py is the caller).  Feature matrices are 2-D float32 / float64 tensors whose rows may be
+    #      strided (stride(1) == 1); results are float64 tensors on the same device.  Launched at once, like the decoders' entries.
+    @staticmethod
+    def _feat(x: torch.Tensor):
+        assert x.dim() == 2 and x.dtype in (torch.float32, torch.float64) and (x.shape[1] == 1 or x.stride(1) == 1), "feature matrix: 2-D fp32/fp64, unit column stride"
+        ld = x.stride(0) if x.shape[0] > 1 else max(x.stride(0), x.shape[1])
+        return C.c_void_p(x.data_ptr()), (_lib.FEAT_F64 if x.dtype == torch.float64 else _lib.FEAT_F32), int(ld)
+
+    @staticmethod
+    def _f64(t: Optional[torch.Tensor], n: int):
+        if t is None:
+            return C.c_void_p(0)
+        assert t.dtype == torch.float64 and t.is_contiguous() and t.numel() == n
+        return C.c_void_p(t.data_ptr())
+
+    def feat_moments(self, x: torch.Tensor, out: Optional[dict] = None) -> dict:
+        """x (n, D) -> mean [D], colcss [D] (centred sums of squares per column, second pass), norm [n], rowsum [n], css [1], flag (int32 [1],
+        non-zero when x holds a NaN or an Inf).  out: the same keys as contiguous buffers of at least those sizes; their heads are written
+        and returned, nothing behind them."""
+        p, dt, ld = self._feat(x)
+        n, D = x.shape
+        sizes = {"mean": D, "colcss": D, "norm": n, "rowsum": n, "css": 1, "flag": 1}
+        if out is None:
+            out = {k: torch.empty(v, dtype=torch.int32 if k == "flag" else torch.float64, device=x.device) for k, v in sizes.items()}
+        for k, v in sizes.items():
+            t = out[k]
+            assert t.dtype == (torch.int32 if k == "flag" else torch.float64) and t.is_contiguous() and t.numel() >= v and t.device == x.device, k
+        self._now("gan_feat_moments", p, dt, n, D, ld, *(C.c_void_p(out[k].data_ptr()) for k in ("mean", "colcss", "norm", "rowsum", "css", "flag")), self._s())
+        return {k: out[k].reshape(-1)[:v] for k, v in sizes.items()}
+
+    def _gram_args(self, a, b, trans, ca, cb, ra, rb):
+        (pa, da, lda), (pb, db, ldb) = self._feat(a), self._feat(b)
+        M, N, K = (a.shape[1], b.shape[1], a.shape[0]) if trans else (a.shape[0], b.shape[0], a.shape[1])
+        assert (b.shape[0] if trans else b.shape[1]) == K, "gram: contraction lengths differ"
+        cen = (M, N) if trans else (K, K)
+        return (pa, da, lda, pb, db, ldb), (M, N, K), (self._f64(ca, cen[0]), self._f64(cb, cen[1]), self._f64(ra, M), self._f64(rb, N))
+
+    def gram_f64(self, a, b, trans=0, ca=None, cb=None, ra=None, rb=None, alpha=1.0, out=None) -> torch.Tensor:
+        """trans = 0: out[i][j] = alpha ra[i] rb[j] sum_k (a[i][k] - ca[k]) (b[j][k] - cb[k]); trans = 1: out[p][q] = alpha sum_i (a[i][p] - ca[p])
+        (b[i][q] - cb[q]).  out: float64 (M, N), rows may be strided."""
+        ops, (M, N, K), cs = self._gram_args(a, b, int(trans), ca, cb, ra, rb)
+        if out is None:
+            out = torch.empty(M, N, dtype=torch.float64, device=a.device)
+        assert out.dtype == torch.float64 and tuple(out.shape) == (M, N) and (N == 1 or out.stride(1) == 1)
+        ldc = out.stride(0) if M > 1 else max(out.stride(0), N)
+        self._now("gan_gram_f64", *ops[:6], int(trans), M, N, K, *cs, C.c_double(alpha), C.c_void_p(out.data_ptr()), int(ldc), self._s())
+        return out
+
+    def cos_rowmin_bounds(self, M, N) -> int:
+        ws = C.c_int64(0)
+        self._now("gan_cos_rowmin_bounds", int(M), int(N), C.byref(ws))
+        return int(ws.value)
+
+    def cos_rowmin(self, a, b, ca=None, cb=None, ra=None, rb=None, alpha=1.0, absolute=False, ws=None, dmin=None, imin=None):
+        """Per row i of a: (min_j d_ij, lowest such j), d = 1 - s or 1 - |s|, s the trans = 0 product of gram_f64; rows / columns of scale 0
+        are left out (+inf, -1 for a row with nothing to compare against).  ws: uint8 workspace of cos_rowmin_bounds bytes."""
+        ops, (M, N, K), cs = self._gram_args(a, b, 0, ca, cb, ra, rb)
+        if ws is None:
+            ws = torch.empty(self.cos_rowmin_bounds(M, N), dtype=torch.uint8, device=a.device)
+        if dmin is None:
+            dmin = torch.empty(M, dtype=torch.float64, device=a.device)
+        if imin is None:
+            imin = torch.empty(M, dtype=torch.int32, device=a.device)
+        assert ws.dtype == torch.uint8 and ws.is_contiguous() and dmin.dtype == torch.float64 and imin.dtype == torch.int32
+        assert dmin.numel() >= M and imin.numel() >= M and dmin.is_contiguous() and imin.is_contiguous()
+        self._now("gan_cos_rowmin", *ops, M, N, K, *cs, C.c_double(alpha), int(bool(absolute)), C.c_void_p(ws.data_ptr()), ws.numel(),
+                  C.c_void_p(dmin.data_ptr()), C.c_void_p(imin.data_ptr()), self._s())
+        return dmin, imin
+
     def view_copy(self, src: View, dst: View, halo_mode) -> Op:
         return self._call("gan_view_copy", self._v(src), self._v(dst), halo_mode, self._s())
 

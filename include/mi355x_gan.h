@@ -441,6 +441,10 @@ int gan_input_pipeline(const gan_input_job* jobs_dev, const gan_input_job* jobs_
  * The resize kernels read tables, so nothing else differs; the entry above is the BICUBIC case. */
 int gan_input_pipeline_filter(const gan_input_job* jobs_dev, const gan_input_job* jobs_host, int B, const int32_t* tables_dev, int S,
                               int filter, uint8_t* tmp, int tmp_rows, uint8_t* img, int32_t* mean_ws, float* out, void* stream);
+/* The same launches with another finish: out is uint8 [B][3][S][S], the bytes of the transformed image (what the reference's evaluation
+ * loader, EVAL/eval/datasets.py:52-66, hands the feature extractor after Image.resize and ToTensor * 255). */
+int gan_input_pipeline_u8(const gan_input_job* jobs_dev, const gan_input_job* jobs_host, int B, const int32_t* tables_dev, int S,
+                          int filter, uint8_t* tmp, int tmp_rows, uint8_t* img, int32_t* mean_ws, uint8_t* out, void* stream);
 
 /* ---- Baseline JPEG encoder on the device: the file the reference writes with pil.save(..., format="JPEG", quality=95, subsampling=0,
  *      optimize=True) (GAN_Variant1/generate_folder.py:252), byte for byte -- libjpeg's 8-bit JDCT_ISLOW path, 4:4:4, one interleaved
@@ -611,7 +615,35 @@ int gan_pngdec_inflate(const void* blk_dev, const void* blk_host, int64_t blk_by
 int gan_pngdec_pixels(const void* blk_dev, const void* blk_host, int64_t blk_bytes, int n, void* ws, int64_t ws_bytes, uint8_t* out,
                       int64_t out_bytes, int32_t* err, void* stream);
 
-/* ---- losses.  Every loss writes its value to *loss (device fp32, overwritten) and the gradient wrt its input.
+/* ---- Evaluation (csrc/mifid.hip): the float64 work of FID / MiFID over feature matrices (the reference's EVAL/eval/mifid.py does it
+ *      with numpy on the host and a float32 torch loop).  A feature matrix is row-major GAN_FEAT_F32 or GAN_FEAT_F64 with a row stride
+ *      ld >= cols, in elements.  Values are promoted to float64 when loaded, every sum is float64 and runs in a fixed order, nothing
+ *      uses a floating-point atomic: a repeated call repeats its bits.  Outputs are float64 unless stated.  Nothing past an output's
+ *      extent (or inside the padding of its rows) is written.  Every entry validates first and launches nothing when it refuses. */
+enum { GAN_FEAT_F32 = 0, GAN_FEAT_F64 = 1 };
+/* X (n x D) -> mean [D] (column means), colcss [D] (sum_i (x_ij - mean_j)^2, from a second pass over the data, never sum x^2 - n mean^2),
+ * norm [n] (row L2 norms), rowsum [n], css [1] (the sum of colcss: the centred sum of squares, (n - 1) tr cov), flag (int32 [1]):
+ * non-zero when any element is NaN or Inf. */
+int gan_feat_moments(const void* X, int dtype, int64_t n, int64_t D, int64_t ld, double* mean, double* colcss, double* norm, double* rowsum,
+                     double* css, int32_t* flag, void* stream);
+/* One contraction on v_mfma_f64_16x16x4_f64, 64 x 64 output tiles, any positive extents up to INT_MAX - 64 (M at most 65535 tiles):
+ *   trans = 0: A is M x K, B is N x K:  C[i][j] = alpha * sum_k ((A[i][k] - ca[k]) ra[i]) ((B[j][k] - cb[k]) rb[j])
+ *   trans = 1: A is K x M, B is K x N:  C[a][b] = alpha * sum_i (A[i][a] - ca[a]) (B[i][b] - cb[b])        (ra, rb must be NULL)
+ * ca / cb NULL: no centring; ra / rb NULL: scale 1.  Centring, scaling and the conversion to float64 happen on the way into LDS.
+ * C is M x N float64 with row stride ldc >= N.  A and B may be the same matrix. */
+int gan_gram_f64(const void* A, int a_dtype, int64_t lda, const void* B, int b_dtype, int64_t ldb, int trans, int M, int N, int K,
+                 const double* ca, const double* cb, const double* ra, const double* rb, double alpha, double* C, int64_t ldc, void* stream);
+/* For every row i of A: dmin[i] = min_j d_ij and imin[i] (int32) = the lowest j that attains it, d_ij = 1 - s_ij (absolute = 1:
+ * 1 - |s_ij|), s the trans = 0 product above.  Rows and columns whose scale is exactly 0 are left out: such a row, or a row with no
+ * column left, gets +inf and -1.  The M x N matrix is never written: every workgroup reduces its tile to per-row (min, index) pairs in
+ * ws ([column tiles][M] float64, then the same as int32, gan_cos_rowmin_bounds bytes, 16-byte aligned) and a second launch folds the
+ * column tiles in ascending order. */
+int gan_cos_rowmin_bounds(int M, int N, int64_t* ws_bytes);
+int gan_cos_rowmin(const void* A, int a_dtype, int64_t lda, const void* B, int b_dtype, int64_t ldb, int M, int N, int K, const double* ca,
+                   const double* cb, const double* ra, const double* rb, double alpha, int absolute, void* ws, int64_t ws_bytes, double* dmin,
+                   int32_t* imin, void* stream);
+
+/* ---- losses. Every loss writes its value to *loss (device fp32, overwritten) and the gradient wrt its input.
  *      hinge: adv_hinge.py:6-62 (mode 0: mean relu(1-x), 1: mean relu(1+x), 2: -mean x), scaled by `scale`;
  *      lsgan/bce: Basic_GAN/src/losses.py:5-22 (mode 3: mse vs target, 4: bce-with-logits vs target in {0,1});
  *      l1: identity_l1.py:18-20 and Basic_GAN/src/losses.py:24-30 (target given as NCHW fp32).
