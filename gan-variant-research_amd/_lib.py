@@ -166,6 +166,9 @@ PROTOTYPES = {
     "gan_gram_f64": (C.c_int, [vp, C.c_int, i64, vp, C.c_int, i64, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, C.c_double, vp, i64, vp]),
     "gan_cos_rowmin_bounds": (C.c_int, [C.c_int, C.c_int, C.POINTER(i64)]),
     "gan_cos_rowmin": (C.c_int, [vp, C.c_int, i64, vp, C.c_int, i64, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, C.c_double, C.c_int, vp, i64, vp, vp, vp]),
+    "gan_sqdist_rowmin_bounds": (C.c_int, [C.c_int, C.c_int, C.POINTER(i64)]),
+    "gan_sqdist_rowmin": (C.c_int, [vp, C.c_int, i64, vp, C.c_int, i64, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, i64, vp, vp, vp]),
+    "gan_kmeans_update": (C.c_int, [vp, C.c_int, i64, i64, i64, vp, vp, vp, C.c_int, vp, i64, vp, vp, vp]),
     "gan_spectral_norm_ws_floats": (C.c_int64, [C.c_int, C.c_int]),
     "gan_spectral_norm_fwd": (C.c_int, [vp, C.c_int, C.c_int, vp, vp, C.c_int, C.c_float, vp, vp, vp, vp]),
     "gan_spectral_norm_bwd": (C.c_int, [vp, vp, vp, vp, vp, C.c_int, C.c_int, vp, vp, vp]),

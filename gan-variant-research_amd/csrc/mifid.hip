@@ -1,5 +1,6 @@
 // Evaluation kernels (FID / MiFID over feature matrices): float64 moments, one float64 contraction on v_mfma_f64_16x16x4_f64 with
-// two operand walks, and the cosine row minimum that never writes the n_a x n_b matrix.
+// two operand walks, and the cosine row minimum that never writes the n_a x n_b matrix.  The selection step (select_7k.py) adds a
+// column transform (x - c[k]) * s[k] in the operand load, the squared-Euclidean row minimum on the same tile, and the k-means update.
 //
 // Replaces, on the reference's side (EVAL/eval/mifid.py), numpy's np.mean / np.cov over the Inception features and the batched
 // float32 cosine loop of compute_cosine_distances_batched; the Frechet term itself is restated through the identity
@@ -112,6 +113,8 @@ __global__ __launch_bounds__(256) void feat_rows_kernel(const void* __restrict__
 struct GramArgs {
   const void* A; const void* B;
   const double* ca; const double* cb; const double* ra; const double* rb;
+  const double* sa; const double* sb;      // MODE 2: column scales (trans = 0: indexed by k), applied after the centre
+  const double* na; const double* nb;      // MODE 2: squared norms of the transformed rows, [M] and [N]
   int64_t lda, ldb, ldc;
   int M, N, K, a_f64, b_f64, trans, absolute, ntn;
   double alpha;
@@ -122,8 +125,9 @@ struct GramArgs {
 
 // Four elements of one operand's 64 x 16 slab at k0, as this lane stores them to LDS: trans = 0 lane -> row t >> 2, k 4 (t & 3) .. + 3;
 // trans = 1 lane -> k t >> 4, rows 4 (t & 15) .. + 3.  (m: index along the tile's output extent, k: along the contraction)
-__device__ __forceinline__ void slab_load(const void* P, int f64, int64_t ld, const double* cen, const double* scl, int trans, int m0, int ext,
-                                          int k0, int K, double v[4]) {
+// cs (column scale, trans = 0 only): the element becomes (x - cen[k]) * cs[k], two rounded operations in that order.
+__device__ __forceinline__ void slab_load(const void* P, int f64, int64_t ld, const double* cen, const double* cs, const double* scl, int trans,
+                                          int m0, int ext, int k0, int K, double v[4]) {
   const int t = threadIdx.x;
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
@@ -133,6 +137,7 @@ __device__ __forceinline__ void slab_load(const void* P, int f64, int64_t ld, co
     if (m < ext && k < K) {
       x = ldf(P, f64, trans ? (int64_t)k * ld + m : (int64_t)m * ld + k);
       if (cen) x -= cen[trans ? m : k];
+      if (cs) x *= cs[k];
       if (scl) x *= scl[m];
     }
     v[j] = x;
@@ -149,8 +154,11 @@ __device__ __forceinline__ void slab_store(double (*S)[LDS_LD], int trans, const
 }
 
 // MODE 0: C = alpha * sum.  MODE 1: per row of the tile, the minimum of d = 1 - s (or 1 - |s|) over the tile's columns and its column.
+// MODE 2: the same minimum of d = max(0, na[i] + nb[j] - 2 s) over operands with the column transform; no row or column is left out.
 template <int MODE>
 __global__ __launch_bounds__(256) void gram_kernel(GramArgs p) {
+  const double* const sa = MODE == 2 ? p.sa : nullptr;
+  const double* const sb = MODE == 2 ? p.sb : nullptr;
   __shared__ double As[TK][LDS_LD], Bs[TK][LDS_LD];
   __shared__ double red_min[2][TM];
   __shared__ int32_t red_idx[2][TM];
@@ -163,16 +171,16 @@ __global__ __launch_bounds__(256) void gram_kernel(GramArgs p) {
     for (int j = 0; j < 2; ++j) acc[i][j] = f64x4_t{0.0, 0.0, 0.0, 0.0};
 
   double va[4], vb[4];
-  slab_load(p.A, p.a_f64, p.lda, p.ca, p.ra, p.trans, m0, p.M, 0, p.K, va);
-  slab_load(p.B, p.b_f64, p.ldb, p.cb, p.rb, p.trans, n0, p.N, 0, p.K, vb);
+  slab_load(p.A, p.a_f64, p.lda, p.ca, sa, p.ra, p.trans, m0, p.M, 0, p.K, va);
+  slab_load(p.B, p.b_f64, p.ldb, p.cb, sb, p.rb, p.trans, n0, p.N, 0, p.K, vb);
   for (int k0 = 0; k0 < p.K; k0 += TK) {
     __syncthreads();                       // the previous slab's MFMAs have read LDS
     slab_store(As, p.trans, va);
     slab_store(Bs, p.trans, vb);
     __syncthreads();
     if (k0 + TK < p.K) {
-      slab_load(p.A, p.a_f64, p.lda, p.ca, p.ra, p.trans, m0, p.M, k0 + TK, p.K, va);
-      slab_load(p.B, p.b_f64, p.ldb, p.cb, p.rb, p.trans, n0, p.N, k0 + TK, p.K, vb);
+      slab_load(p.A, p.a_f64, p.lda, p.ca, sa, p.ra, p.trans, m0, p.M, k0 + TK, p.K, va);
+      slab_load(p.B, p.b_f64, p.ldb, p.cb, sb, p.rb, p.trans, n0, p.N, k0 + TK, p.K, vb);
     }
 #pragma unroll
     for (int kk = 0; kk < TK / 4; ++kk) {
@@ -203,10 +211,16 @@ __global__ __launch_bounds__(256) void gram_kernel(GramArgs p) {
   const double inf = __builtin_huge_val();
   bool col_in[2];
   int colj[2];
+  double nbj[2] = {0.0, 0.0};
 #pragma unroll
   for (int ni = 0; ni < 2; ++ni) {
     colj[ni] = n0 + wn * 32 + ni * 16 + (lane & 15);
-    col_in[ni] = colj[ni] < p.N && (!p.rb || p.rb[colj[ni]] != 0.0);
+    if (MODE == 2) {
+      col_in[ni] = colj[ni] < p.N;
+      if (col_in[ni]) nbj[ni] = p.nb[colj[ni]];
+    } else {
+      col_in[ni] = colj[ni] < p.N && (!p.rb || p.rb[colj[ni]] != 0.0);
+    }
   }
 #pragma unroll
   for (int mi = 0; mi < 2; ++mi)
@@ -214,10 +228,21 @@ __global__ __launch_bounds__(256) void gram_kernel(GramArgs p) {
     for (int r = 0; r < 4; ++r) {
       double best = inf;
       int bj = 0x7fffffff;
+      double nai = 0.0;
+      if (MODE == 2) {
+        const int row = m0 + wm * 32 + mi * 16 + (lane >> 4) + 4 * r;
+        if (row < p.M) nai = p.na[row];
+      }
 #pragma unroll
       for (int ni = 0; ni < 2; ++ni) {          // ascending columns: a strict < keeps the lowest index of a tie
-        const double s = p.alpha * acc[mi][ni][r];
-        const double d = 1.0 - (p.absolute ? fabs(s) : s);
+        double d;
+        if (MODE == 2) {
+          d = (nai + nbj[ni]) - 2.0 * acc[mi][ni][r];
+          d = d < 0.0 ? 0.0 : d;                // not fmax: a NaN stays a NaN and loses every comparison
+        } else {
+          const double s = p.alpha * acc[mi][ni][r];
+          d = 1.0 - (p.absolute ? fabs(s) : s);
+        }
         if (col_in[ni] && d < best) { best = d; bj = colj[ni]; }
       }
 #pragma unroll
@@ -239,7 +264,7 @@ __global__ __launch_bounds__(256) void gram_kernel(GramArgs p) {
       double best = red_min[0][rl];
       int bj = red_idx[0][rl];
       if (red_min[1][rl] < best) { best = red_min[1][rl]; bj = red_idx[1][rl]; }
-      if (p.ra && p.ra[row] == 0.0) { best = inf; bj = 0x7fffffff; }
+      if (MODE != 2 && p.ra && p.ra[row] == 0.0) { best = inf; bj = 0x7fffffff; }
       p.ws_min[(int64_t)blockIdx.x * p.M + row] = best;
       p.ws_idx[(int64_t)blockIdx.x * p.M + row] = bj;
     }
@@ -288,11 +313,97 @@ int gram_args(const char* who, GramArgs* g, const void* A, int a_dtype, int64_t 
   g->lda = lda; g->ldb = ldb; g->ldc = 0;
   g->M = M; g->N = N; g->K = K; g->a_f64 = a_dtype == GAN_FEAT_F64; g->b_f64 = b_dtype == GAN_FEAT_F64; g->trans = trans;
   g->absolute = 0; g->ntn = tiles(N); g->alpha = alpha;
+  g->sa = nullptr; g->sb = nullptr; g->na = nullptr; g->nb = nullptr;
   g->C = nullptr; g->ws_min = nullptr; g->ws_idx = nullptr;
   return 0;
 }
 
 int64_t rowmin_idx_off(int M, int N) { return (((int64_t)(tiles(N)) * M * 8) + 15) / 16 * 16; }
+
+// ---- the column transform outside the contraction: the same two rounded operations as slab_load (never one fused multiply-add with
+// what follows, so a host restatement of x' repeats its bits)
+__device__ __forceinline__ double xform(double x, const double* cen, const double* cs, int64_t k) {
+#pragma clang fp contract(off)
+  if (cen) x = x - cen[k];
+  if (cs) x = x * cs[k];
+  return x;
+}
+
+// ---- squared norms of the transformed rows: one wave per row, lane l sums columns l, l + 64, ... in order, then the xor tree
+__global__ __launch_bounds__(256) void sqnorm_rows_kernel(const void* __restrict__ X, int f64, int64_t n, int64_t D, int64_t ld,
+                                                          const double* __restrict__ cen, const double* __restrict__ cs, double* __restrict__ out) {
+  const int lane = threadIdx.x & 63;
+  const int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (r >= n) return;
+  double q = 0.0;
+  for (int64_t c = lane; c < D; c += 64) {
+    const double v = xform(ldf(X, f64, r * ld + c), cen, cs, c);
+    q += v * v;
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) q += __shfl_xor(q, o, 64);
+  if (lane == 0) out[r] = q;
+}
+
+// ---- k-means update.  Workgroup (cluster c, column strip of 256): the labels are scanned 256 at a time, the rows of cluster c are
+// compacted in ascending order into LDS (ballot + prefix over the four waves), and lane t adds x'[row][strip + t] for those rows in
+// that order -- per cluster and column one fixed, ascending-row sum, whatever the scheduling.  LDS is 1 KiB for the row list and 16
+// bytes of wave counts, independent of k: k is bounded by the grid alone.  Strip 0 stores the count; cluster 0, strip 0 also raises
+// the error word for a label outside [0, k) (such rows match no cluster and are skipped).
+constexpr int KU = 256;
+__global__ __launch_bounds__(KU) void kmeans_update_kernel(const void* __restrict__ X, int f64, int64_t n, int64_t D, int64_t ld,
+                                                           const double* __restrict__ cen, const double* __restrict__ cs,
+                                                           const int32_t* __restrict__ labels, int k, double* __restrict__ sums, int64_t lds,
+                                                           int32_t* __restrict__ counts, int32_t* __restrict__ err) {
+  __shared__ int32_t rows[KU];
+  __shared__ int32_t wave_n[4];
+  const int t = threadIdx.x, lane = t & 63, w = t >> 6;
+  const int c = blockIdx.x;
+  const int64_t col = (int64_t)blockIdx.y * KU + t;
+  const bool col_in = col < D;
+  const bool police = blockIdx.x == 0 && blockIdx.y == 0;
+  double acc = 0.0;
+  int32_t total = 0;
+  bool bad = false;
+  for (int64_t r0 = 0; r0 < n; r0 += KU) {
+    const int64_t r = r0 + t;
+    int32_t lab = -1;
+    if (r < n) {
+      lab = labels[r];
+      bad |= lab < 0 || lab >= k;
+    }
+    const bool mine = r < n && lab == c;
+    const unsigned long long b = __ballot(mine);
+    if (lane == 0) wave_n[w] = __popcll(b);
+    __syncthreads();
+    int base = 0, cnt = 0;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      if (i < w) base += wave_n[i];
+      cnt += wave_n[i];
+    }
+    if (mine) rows[base + __popcll(b & ((1ull << lane) - 1ull))] = (int32_t)(r - r0);
+    __syncthreads();
+    if (col_in)
+      for (int i = 0; i < cnt; ++i) acc += xform(ldf(X, f64, (r0 + rows[i]) * ld + col), cen, cs, col);
+    total += cnt;
+    __syncthreads();                       // the list and the wave counts are rewritten by the next chunk
+  }
+  if (col_in) sums[(int64_t)c * lds + col] = acc;
+  if (blockIdx.y == 0 && t == 0) counts[c] = total;
+  if (police && bad) atomicOr(err, 1);
+}
+
+struct SqdistLayout { int64_t nb, wmin, widx, total; };
+SqdistLayout sqdist_layout(int M, int N) {
+  SqdistLayout l;
+  const int64_t pairs = (int64_t)tiles(N) * M;
+  l.nb = (int64_t)M * 8;
+  l.wmin = (((int64_t)M + N) * 8 + 15) / 16 * 16;
+  l.widx = l.wmin + (pairs * 8 + 15) / 16 * 16;
+  l.total = l.widx + pairs * 4;
+  return l;
+}
 }  // namespace
 
 extern "C" int gan_feat_moments(const void* X, int dtype, int64_t n, int64_t D, int64_t ld, double* mean, double* colcss, double* norm,
@@ -347,6 +458,57 @@ extern "C" int gan_cos_rowmin(const void* A, int a_dtype, int64_t lda, const voi
   hipStream_t s = (hipStream_t)stream;
   hipLaunchKernelGGL(gram_kernel<1>, dim3(g.ntn, tiles(M)), dim3(256), 0, s, g);
   hipLaunchKernelGGL(rowmin_fold_kernel, dim3((unsigned)(((int64_t)M + 255) / 256)), dim3(256), 0, s, g.ws_min, g.ws_idx, M, g.ntn, dmin, imin);
+  GAN_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int gan_sqdist_rowmin_bounds(int M, int N, int64_t* ws_bytes) {
+  GAN_CHECK(ws_bytes, "sqdist_rowmin_bounds: null output");
+  GAN_CHECK(M > 0 && N > 0, "sqdist_rowmin_bounds: extents must be positive (M=%d N=%d)", M, N);
+  GAN_CHECK(M <= MAX_EXTENT && N <= MAX_EXTENT, "sqdist_rowmin_bounds: extents above %d are refused (M=%d N=%d)", MAX_EXTENT, M, N);
+  *ws_bytes = sqdist_layout(M, N).total;
+  return 0;
+}
+
+extern "C" int gan_sqdist_rowmin(const void* A, int a_dtype, int64_t lda, const void* B, int b_dtype, int64_t ldb, int M, int N, int K,
+                                 const double* ca, const double* sa, const double* cb, const double* sb, void* ws, int64_t ws_bytes,
+                                 double* dmin, int32_t* imin, void* stream) {
+  GramArgs g;
+  if (gram_args("sqdist_rowmin", &g, A, a_dtype, lda, B, b_dtype, ldb, 0, M, N, K, ca, cb, nullptr, nullptr, 1.0)) return -1;
+  GAN_CHECK(dmin && imin, "sqdist_rowmin: null output");
+  int64_t need = 0;
+  if (gan_sqdist_rowmin_bounds(M, N, &need)) return -1;
+  GAN_CHECK(ws && (uintptr_t)ws % 16 == 0 && ws_bytes >= need, "sqdist_rowmin: workspace of %lld bytes, gan_sqdist_rowmin_bounds asks %lld (16-byte aligned)",
+            (long long)ws_bytes, (long long)need);
+  const SqdistLayout l = sqdist_layout(M, N);
+  char* base = reinterpret_cast<char*>(ws);
+  double* na = reinterpret_cast<double*>(base);
+  double* nb = reinterpret_cast<double*>(base + l.nb);
+  g.sa = sa; g.sb = sb; g.na = na; g.nb = nb;
+  g.ws_min = reinterpret_cast<double*>(base + l.wmin);
+  g.ws_idx = reinterpret_cast<int32_t*>(base + l.widx);
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(sqnorm_rows_kernel, dim3((unsigned)(((int64_t)M + 3) / 4)), dim3(256), 0, s, A, g.a_f64, (int64_t)M, (int64_t)K, lda, ca, sa, na);
+  hipLaunchKernelGGL(sqnorm_rows_kernel, dim3((unsigned)(((int64_t)N + 3) / 4)), dim3(256), 0, s, B, g.b_f64, (int64_t)N, (int64_t)K, ldb, cb, sb, nb);
+  hipLaunchKernelGGL(gram_kernel<2>, dim3(g.ntn, tiles(M)), dim3(256), 0, s, g);
+  hipLaunchKernelGGL(rowmin_fold_kernel, dim3((unsigned)(((int64_t)M + 255) / 256)), dim3(256), 0, s, g.ws_min, g.ws_idx, M, g.ntn, dmin, imin);
+  GAN_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int gan_kmeans_update(const void* X, int dtype, int64_t n, int64_t D, int64_t ld, const double* c, const double* s,
+                                 const int32_t* labels, int k, double* sums, int64_t lds, int32_t* counts, int32_t* err, void* stream) {
+  if (feat_args("kmeans_update", X, dtype, n, D, ld)) return -1;
+  GAN_CHECK(labels && sums && counts && err, "kmeans_update: null labels or output");
+  GAN_CHECK((uintptr_t)sums % 8 == 0 && (uintptr_t)labels % 4 == 0 && (uintptr_t)counts % 4 == 0 && (uintptr_t)err % 4 == 0, "kmeans_update: misaligned buffer");
+  GAN_CHECK(k > 0 && k <= MAX_EXTENT, "kmeans_update: k = %d: between 1 and %d", k, MAX_EXTENT);
+  GAN_CHECK(lds >= D, "kmeans_update: sums row stride %lld below the %lld columns", (long long)lds, (long long)D);
+  const int64_t strips = (D + KU - 1) / KU;
+  GAN_CHECK(strips <= 65535, "kmeans_update: D=%lld beyond 65535 column strips", (long long)D);
+  hipStream_t st = (hipStream_t)stream;
+  if (hipMemsetAsync(err, 0, sizeof(int32_t), st) != hipSuccess) return gan_set_error(-2, "kmeans_update: clearing the error word failed");
+  hipLaunchKernelGGL(kmeans_update_kernel, dim3((unsigned)k, (unsigned)strips), dim3(KU), 0, st, X, dtype == GAN_FEAT_F64, n, D, ld, c, s, labels, k, sums,
+                     lds, counts, err);
   GAN_LAUNCH_CHECK();
   return 0;
 }

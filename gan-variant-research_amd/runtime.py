@@ -710,6 +710,50 @@ class HipOps:
                   C.c_void_p(dmin.data_ptr()), C.c_void_p(imin.data_ptr()), self._s())
         return dmin, imin
 
+    # ---- selection (csrc/mifid.hip; select_7k.py is the caller).  Column transform: x' = (x - c[k]) * s[k], c and s float64 [K] or None.
+    def sqdist_rowmin_bounds(self, M, N) -> int:
+        ws = C.c_int64(0)
+        self._now("gan_sqdist_rowmin_bounds", int(M), int(N), C.byref(ws))
+        return int(ws.value)
+
+    def sqdist_rowmin(self, a, b, ca=None, sa=None, cb=None, sb=None, ws=None, dmin=None, imin=None):
+        """Per row i of a: (min_j d_ij, lowest such j), d_ij = max(0, |a'_i|^2 + |b'_j|^2 - 2 a'_i . b'_j) over the transformed rows.
+        ws: uint8 workspace of sqdist_rowmin_bounds bytes."""
+        (pa, da, lda), (pb, db, ldb) = self._feat(a), self._feat(b)
+        M, N, K = a.shape[0], b.shape[0], a.shape[1]
+        assert b.shape[1] == K, "sqdist_rowmin: row lengths differ"
+        if ws is None:
+            ws = torch.empty(self.sqdist_rowmin_bounds(M, N), dtype=torch.uint8, device=a.device)
+        if dmin is None:
+            dmin = torch.empty(M, dtype=torch.float64, device=a.device)
+        if imin is None:
+            imin = torch.empty(M, dtype=torch.int32, device=a.device)
+        assert ws.dtype == torch.uint8 and ws.is_contiguous() and dmin.dtype == torch.float64 and imin.dtype == torch.int32
+        assert dmin.numel() >= M and imin.numel() >= M and dmin.is_contiguous() and imin.is_contiguous()
+        self._now("gan_sqdist_rowmin", pa, da, lda, pb, db, ldb, M, N, K, self._f64(ca, K), self._f64(sa, K), self._f64(cb, K), self._f64(sb, K),
+                  C.c_void_p(ws.data_ptr()), ws.numel(), C.c_void_p(dmin.data_ptr()), C.c_void_p(imin.data_ptr()), self._s())
+        return dmin, imin
+
+    def kmeans_update(self, x, labels, k, c=None, s=None, sums=None, counts=None, err=None):
+        """sums (k, D) float64 (rows may be strided): per cluster the sum of the transformed rows in ascending row order; counts int32 [k];
+        err int32 [1], non-zero when a label lies outside [0, k) (those rows are skipped)."""
+        p, dt, ld = self._feat(x)
+        n, D = x.shape
+        k = int(k)
+        assert labels.dtype == torch.int32 and labels.is_contiguous() and labels.numel() == n and labels.device == x.device
+        if sums is None:
+            sums = torch.empty(k, D, dtype=torch.float64, device=x.device)
+        if counts is None:
+            counts = torch.empty(k, dtype=torch.int32, device=x.device)
+        if err is None:
+            err = torch.empty(1, dtype=torch.int32, device=x.device)
+        assert sums.dtype == torch.float64 and tuple(sums.shape) == (k, D) and (D == 1 or sums.stride(1) == 1)
+        assert counts.dtype == torch.int32 and counts.is_contiguous() and counts.numel() >= k and err.dtype == torch.int32 and err.numel() >= 1
+        lds = sums.stride(0) if k > 1 else max(sums.stride(0), D)
+        self._now("gan_kmeans_update", p, dt, n, D, ld, self._f64(c, D), self._f64(s, D), C.c_void_p(labels.data_ptr()), k,
+                  C.c_void_p(sums.data_ptr()), int(lds), C.c_void_p(counts.data_ptr()), C.c_void_p(err.data_ptr()), self._s())
+        return sums, counts, err
+
     def view_copy(self, src: View, dst: View, halo_mode) -> Op:
         return self._call("gan_view_copy", self._v(src), self._v(dst), halo_mode, self._s())
 

@@ -642,6 +642,25 @@ int gan_cos_rowmin_bounds(int M, int N, int64_t* ws_bytes);
 int gan_cos_rowmin(const void* A, int a_dtype, int64_t lda, const void* B, int b_dtype, int64_t ldb, int M, int N, int K, const double* ca,
                    const double* cb, const double* ra, const double* rb, double alpha, int absolute, void* ws, int64_t ws_bytes, double* dmin,
                    int32_t* imin, void* stream);
+/* The selection step (the reference's EVAL/scripts/select_7k.py).  Column transform: an element x of column k becomes (x - c[k]) * s[k]
+ * on its way into LDS or into a sum, two rounded float64 operations in that order; c and s are float64 [K], each may be NULL (no
+ * centre, scale 1), per operand.
+ * For every row i of A (M x K): dmin[i] = min_j d_ij and imin[i] (int32) = the lowest j that attains it,
+ *   d_ij = max(0, na_i + nb_j - 2 a'_i . b'_j),  a' / b' the transformed rows of A / B (N x K), na / nb their squared norms,
+ * the norms from a row kernel (one wave per row, fixed order) into the head of ws, the products on the contraction tile above.  No row
+ * or column is left out.  The M x N matrix is never written: ws holds na [M], nb [N], then per-tile (min, index) pairs as for
+ * gan_cos_rowmin (gan_sqdist_rowmin_bounds bytes, 16-byte aligned); a last launch folds the column tiles in ascending order.
+ * Extents as for gan_cos_rowmin. */
+int gan_sqdist_rowmin_bounds(int M, int N, int64_t* ws_bytes);
+int gan_sqdist_rowmin(const void* A, int a_dtype, int64_t lda, const void* B, int b_dtype, int64_t ldb, int M, int N, int K, const double* ca,
+                      const double* sa, const double* cb, const double* sb, void* ws, int64_t ws_bytes, double* dmin, int32_t* imin,
+                      void* stream);
+/* k-means update: sums[j][d] = sum over the rows i with labels[i] == j, in ascending i, of the transformed x'_id (float64 [k][D], row
+ * stride lds >= D; a cluster without rows gets exact zeros), counts[j] (int32 [k]) their number, *err (int32) non-zero when a label
+ * lies outside [0, k); such rows are skipped.  One workgroup per (cluster, 256 columns); the member rows are compacted in order into
+ * 1 KiB of LDS whatever k is, so k is bounded only by INT_MAX - 64 and D by 65535 strips of 256 columns. */
+int gan_kmeans_update(const void* X, int dtype, int64_t n, int64_t D, int64_t ld, const double* c, const double* s, const int32_t* labels,
+                      int k, double* sums, int64_t lds, int32_t* counts, int32_t* err, void* stream);
 
 /* ---- losses. Every loss writes its value to *loss (device fp32, overwritten) and the gradient wrt its input.
  *      hinge: adv_hinge.py:6-62 (mode 0: mean relu(1-x), 1: mean relu(1+x), 2: -mean x), scaled by `scale`;
