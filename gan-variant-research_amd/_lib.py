@@ -158,6 +158,12 @@ PROTOTYPES = {
     "gan_jpegdec_entropy": (C.c_int, [vp, vp, i64, C.c_int, C.c_int, vp, i64, vp]),
     "gan_jpegdec_idct": (C.c_int, [vp, vp, i64, C.c_int, C.c_int, vp, i64, vp]),
     "gan_jpegdec_pixels": (C.c_int, [vp, vp, i64, C.c_int, C.c_int, vp, i64, vp, i64, vp, vp]),
+    "gan_jpegprog_block_offsets": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(i64)]),
+    "gan_jpegprog_bounds": (C.c_int, [vp, C.c_int, C.c_int, C.POINTER(i64)]),
+    "gan_jpegprog_tables": (C.c_int, [vp, vp, i64, C.c_int, C.c_int, C.c_int, C.c_int, vp, i64, vp]),
+    "gan_jpegprog_entropy": (C.c_int, [vp, vp, i64, C.c_int, C.c_int, C.c_int, C.c_int, vp, i64, vp]),
+    "gan_jpegprog_idct": (C.c_int, [vp, vp, i64, C.c_int, C.c_int, C.c_int, C.c_int, vp, i64, vp]),
+    "gan_jpegprog_pixels": (C.c_int, [vp, vp, i64, C.c_int, C.c_int, C.c_int, C.c_int, vp, i64, vp, i64, vp, vp]),
     "gan_pngdec_block_offsets": (C.c_int, [C.c_int, C.POINTER(i64)]),
     "gan_pngdec_bounds": (C.c_int, [vp, C.c_int, C.POINTER(i64)]),
     "gan_pngdec_inflate": (C.c_int, [vp, vp, i64, C.c_int, vp, i64, vp]),

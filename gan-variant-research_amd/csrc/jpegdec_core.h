@@ -278,3 +278,70 @@ JD_FN void jd_pixel(const gan_jpegdec_image* im, const uint8_t* planes, int y, i
   rgb[1] = (uint8_t)jd_clamp8(Y + ((-22554 * cb - 46802 * cr + 32768) >> 16));
   rgb[2] = (uint8_t)jd_clamp8(Y + ((116130 * cb + 32768) >> 16));
 }
+
+// ---- the bodies of the kernels behind the coefficients, shared by jpegdec.hip and jpegprog.hip (both upload blocks begin with
+// gan_jpegdec_image [n] and both workspaces lay out coefficients and planes alike).  Device only; the includer has common.h.
+#if defined(__HIPCC__)
+constexpr int JD_DHT_BYTES = 272;
+
+// workgroup b of 64 lanes: raw table b -> decode table b.  t: one JdTable in LDS.
+__device__ __forceinline__ void jd_tables_body(const uint8_t* __restrict__ dht, JdTable* __restrict__ tabs, JdTable* t) {
+  const uint8_t* raw = dht + (int64_t)blockIdx.x * JD_DHT_BYTES;
+  if (threadIdx.x == 0) jd_table_head(raw, t);
+  __syncthreads();
+  for (int i = threadIdx.x; i < (1 << JD_LOOK); i += 64) jd_table_entry(raw, t, i);
+  __syncthreads();
+  const uint32_t* s = reinterpret_cast<const uint32_t*>(t);
+  uint32_t* d = reinterpret_cast<uint32_t*>(tabs + blockIdx.x);
+  for (int i = threadIdx.x; i < (int)(sizeof(JdTable) / 4); i += 64) d[i] = s[i];
+}
+
+// one thread per 8x8 block of image blockIdx.y (workgroups of 256)
+__device__ __forceinline__ void jd_idct_body(const uint8_t* __restrict__ blk, int64_t off_qt, char* __restrict__ ws, int32_t* __restrict__ errw) {
+  const int b = blockIdx.y, g = blockIdx.x * 256 + threadIdx.x;
+  const gan_jpegdec_image& im = reinterpret_cast<const gan_jpegdec_image*>(blk)[b];      // uniform over the workgroup: scalar loads
+  if (g >= jd_blocks(&im)) return;
+  const JdComp c1 = jd_comp(&im, 1), c2 = jd_comp(&im, 2);
+  const int c = im.ncomp == 1 || g < c1.first ? 0 : g < c2.first ? 1 : 2;
+  const JdComp cp = jd_comp(&im, c);
+  const int r = g - cp.first, by = r / cp.bw, bx = r - by * cp.bw;
+  const uint16_t* q = reinterpret_cast<const uint16_t*>(blk + off_qt) + ((int64_t)b * 4 + im.q_tab[c]) * 64;
+  const u32x4_t* p = reinterpret_cast<const u32x4_t*>(ws + im.coef_off + (int64_t)g * 128);
+  int d[64];
+#pragma unroll
+  for (int v = 0; v < 8; ++v) {
+    const u32x4_t w = p[v];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      d[8 * v + 2 * j] = (int)(int16_t)(w[j] & 0xffffu);
+      d[8 * v + 2 * j + 1] = (int)w[j] >> 16;
+    }
+  }
+  const int e = jd_idct(d, q);
+  if (e) atomicOr(&errw[b], e);
+  const int stride = cp.bw * 8;
+  char* o = ws + im.plane_off + (int64_t)cp.first * 64 + (int64_t)by * 8 * stride + bx * 8;
+#pragma unroll
+  for (int y = 0; y < 8; ++y) {
+    u32x2_t w;
+    w[0] = (uint32_t)d[8 * y] | (uint32_t)d[8 * y + 1] << 8 | (uint32_t)d[8 * y + 2] << 16 | (uint32_t)d[8 * y + 3] << 24;
+    w[1] = (uint32_t)d[8 * y + 4] | (uint32_t)d[8 * y + 5] << 8 | (uint32_t)d[8 * y + 6] << 16 | (uint32_t)d[8 * y + 7] << 24;
+    *reinterpret_cast<u32x2_t*>(o + (int64_t)y * stride) = w;
+  }
+}
+
+// one thread per pixel of image blockIdx.y (workgroups of 256)
+__device__ __forceinline__ void jd_pixels_body(const uint8_t* __restrict__ blk, const char* __restrict__ ws, uint8_t* __restrict__ out,
+                                               const int32_t* __restrict__ errw, int32_t* __restrict__ err) {
+  const int b = blockIdx.y;
+  const uint32_t g = blockIdx.x * 256u + threadIdx.x;
+  const gan_jpegdec_image& im = reinterpret_cast<const gan_jpegdec_image*>(blk)[b];
+  if (g == 0 && err) err[b] = errw[b];
+  if (g >= (uint32_t)im.H * (uint32_t)im.W) return;
+  const int y = (int)(g / (uint32_t)im.W), x = (int)(g - (uint32_t)y * (uint32_t)im.W);
+  uint8_t rgb[3];
+  jd_pixel(&im, reinterpret_cast<const uint8_t*>(ws + im.plane_off), y, x, rgb);
+  uint8_t* o = out + im.out_off + (int64_t)g * 3;
+  o[0] = rgb[0]; o[1] = rgb[1]; o[2] = rgb[2];
+}
+#endif

@@ -386,6 +386,185 @@ def parse_jpeg(data: bytes) -> Optional[Dict]:
             "dc_tab": dc_tab, "ac_tab": ac_tab, "q_tab": q_tab, "scan": (sb, end), "seg_begin": begins, "seg_end": ends, "per": per, "data": data}
 
 
+def _huffman_counts_legal(body) -> Optional[int]:
+    """Symbols of the DHT table at the head of `body`, or None when its counts over-subscribe the code space or exceed 256 / the body."""
+    counts = body[1:17]
+    total, code = sum(counts), 0
+    for l in range(16):
+        code += counts[l]
+        if code > (1 << (l + 1)):
+            return None
+        code <<= 1
+    return None if total > 256 or len(body) < 17 + total else total
+
+
+PROG_MAX_SCANS = PROG_MAX_TABLES = 64           # GAN_JPEGPROG_MAX_SCANS, GAN_JPEGPROG_MAX_TABLES
+
+
+def parse_jpeg_progressive(data: bytes) -> Optional[Dict]:
+    """The plan of a progressive file the device decoder takes, or None ("not mine": Pillow decodes it).  Accepted: SOF2, 8-bit samples,
+    8-bit quantisation tables (all before the first scan), the component classes of `parse_jpeg`, no Adobe APP14, DHT ids 0 .. 3 with
+    `parse_jpeg`'s legality checks; between scans only DHT, DRI, APPn and COM, which take effect for the following scans -- a DHT that
+    is defined again is a new table *version*, and a scan names versions.  The scan script must be one libjpeg decodes without a
+    warning and without work for its block smoothing: a DC scan (Ss = Se = 0) holds all components interleaved or one component; an AC
+    scan (1 <= Ss <= Se <= 63) holds one component and comes after that component's first DC scan; Al <= 13; the first scan that
+    touches a (component, coefficient) has Ah = 0, every later one Ah = the previous Al and Al = Ah - 1; at EOI every coefficient of
+    every component has reached Al = 0.  Every scan has exactly the RSTn its restart interval and its own MCU / block count ask for,
+    EOI follows the last scan, and there are at most PROG_MAX_SCANS scans and PROG_MAX_TABLES table versions.
+    Per scan the plan carries comp (-1: all interleaved), Ss, Se, Ah, Al, tab (table version per component, -1: none), per (restart
+    interval in the scan's units), units, seg_begin / seg_end, dep (the latest earlier scan that touches one of its (component,
+    coefficient) pairs, -1: none) and level (1 + the largest level among all earlier scans that touch one of its pairs)."""
+    n = len(data)
+    if n < 4 or data[0] != 0xFF or data[1] != 0xD8:
+        return None
+    arr = np.frombuffer(data, np.uint8)
+    pos, qt, slots, versions, sof, ri, scans = 2, {}, {}, [], None, 0, []
+    mpos = mk = None
+    state = touch = None                       # per (component, coefficient): the Al reached (-1: untouched), the last scan that touched it
+    while True:
+        if pos + 2 > n or data[pos] != 0xFF:
+            return None
+        m = data[pos + 1]
+        if m == 0xD9:
+            break
+        if pos + 4 > n:
+            return None
+        L = (data[pos + 2] << 8) | data[pos + 3]
+        if L < 2 or pos + 2 + L > n:
+            return None
+        body = data[pos + 4:pos + 2 + L]
+        if m == 0xDB:
+            if scans:
+                return None
+            while body:
+                if body[0] >> 4 != 0 or (body[0] & 15) > 3 or len(body) < 65:
+                    return None
+                q = np.zeros(64, np.uint16)
+                q[list(_JPEG_ZIGZAG)] = np.frombuffer(body[1:65], np.uint8)
+                qt[body[0] & 15] = q
+                body = body[65:]
+        elif m == 0xC4:
+            while body:
+                if len(body) < 17 or body[0] >> 4 > 1 or (body[0] & 15) > 3:
+                    return None
+                total = _huffman_counts_legal(body)
+                if total is None or len(versions) == PROG_MAX_TABLES:
+                    return None
+                slots[(body[0] >> 4, body[0] & 15)] = len(versions)
+                versions.append(body[1:17 + total])
+                body = body[17 + total:]
+        elif m == 0xC2:
+            if sof is not None or len(body) < 6 or body[0] != 8 or len(body) != 6 + 3 * body[5]:
+                return None
+            sof = ((body[1] << 8) | body[2], (body[3] << 8) | body[4], [(body[6 + 3 * c], body[7 + 3 * c] >> 4, body[7 + 3 * c] & 15, body[8 + 3 * c]) for c in range(body[5])])
+            H, W, comps = sof
+            if H < 1 or W < 1 or len(comps) not in (1, 3):
+                return None
+            if len(comps) == 1:
+                if comps[0][1:3] != (1, 1):
+                    return None
+                hmax = vmax = 1
+            else:
+                if tuple(c[0] for c in comps) != (1, 2, 3) or comps[1][1:3] != (1, 1) or comps[2][1:3] != (1, 1) or comps[0][1:3] not in ((1, 1), (2, 1), (2, 2)):
+                    return None
+                hmax, vmax = comps[0][1:3]
+            mcux, mcuy = -(-W // (8 * hmax)), -(-H // (8 * vmax))
+            state, touch = np.full((len(comps), 64), -1, np.int64), np.full((len(comps), 64), -1, np.int64)
+        elif m == 0xDD:
+            if L != 4:
+                return None
+            ri = (body[0] << 8) | body[1]
+        elif m == 0xEE:
+            if body[:5] == b"Adobe":
+                return None
+        elif m == 0xDA:
+            if sof is None or len(scans) == PROG_MAX_SCANS or not body or len(body) != 4 + 2 * body[0]:
+                return None
+            ns, (Ss, Se, AhAl) = body[0], body[-3:]
+            Ah, Al = AhAl >> 4, AhAl & 15
+            ids = [body[1 + 2 * j] for j in range(ns)]
+            if ns == 1 and ids[0] in [c[0] for c in comps]:
+                comp = [c[0] for c in comps].index(ids[0])
+                members = [comp]
+            elif ns == len(comps) and ids == [c[0] for c in comps]:
+                comp, members = -1, list(range(ns))
+            else:
+                return None
+            if not ((Ss == 0 and Se == 0) or (1 <= Ss <= Se <= 63 and comp >= 0)) or Al > 13:
+                return None
+            before = state[members, Ss:Se + 1]
+            if Ah == 0:
+                if (before != -1).any():
+                    return None
+            elif Al != Ah - 1 or (before != Ah).any():
+                return None
+            if Ss > 0 and state[comp, 0] < 0:
+                return None
+            tab = [-1, -1, -1]
+            for j, c in enumerate(members):
+                sel = body[2 + 2 * j]
+                key = (0, sel >> 4) if Ss == 0 else (1, sel & 15)
+                if Ss == 0 and Ah:                     # DC refinement reads raw bits
+                    continue
+                if key[1] > 3 or key not in slots:
+                    return None
+                tab[c] = slots[key]
+            earlier = touch[members, Ss:Se + 1]
+            dep = int(earlier.max())
+            level = 1 + max(scans[int(t)]["level"] for t in np.unique(earlier) if t >= 0) if dep >= 0 else 0
+            state[members, Ss:Se + 1], touch[members, Ss:Se + 1] = Al, len(scans)
+            sb = pos + 2 + L
+            if mpos is None:                           # one vectorised search for every scan: stuffed bytes, RSTn and the markers behind the scans
+                ff = np.flatnonzero(arr[:n - 1] == 0xFF)
+                nxt = arr[ff + 1]
+                mpos, mk = ff[nxt != 0], nxt[nxt != 0]
+            i0 = int(np.searchsorted(mpos, sb))
+            other = np.flatnonzero((mk[i0:] & 0xF8) != 0xD0)
+            if other.size == 0:
+                return None
+            e = i0 + int(other[0])
+            rst, end = mpos[i0:e], int(mpos[e])
+            if comp < 0:
+                units = mcux * mcuy
+            else:
+                h, v = comps[comp][1:3]
+                units = -(-(-(-W * h // hmax)) // 8) * -(-(-(-H * v // vmax)) // 8)
+            per = ri if ri else units
+            if rst.size != -(-units // per) - 1:
+                return None
+            scans.append({"comp": comp, "Ss": Ss, "Se": Se, "Ah": Ah, "Al": Al, "tab": tab, "dep": dep, "level": level, "per": per, "units": units,
+                          "seg_begin": np.concatenate([[sb], rst + 2]).astype(np.int64), "seg_end": np.concatenate([rst, [end]]).astype(np.int64)})
+            pos = end
+            continue
+        elif not (0xE0 <= m <= 0xEF or m == 0xFE):
+            return None
+        pos += 2 + L
+    if not scans or (state != 0).any():
+        return None
+    q_tab = [0, 0, 0]
+    for c, (_, _, _, tq) in enumerate(comps):
+        if tq not in qt:
+            return None
+        q_tab[c] = tq
+    return {"format": "jpegprog", "H": H, "W": W, "ncomp": len(comps), "hmax": hmax, "vmax": vmax, "mcux": mcux, "mcuy": mcuy, "qt": qt, "q_tab": q_tab,
+            "versions": versions, "scans": scans, "nlevel": 1 + max(s["level"] for s in scans), "data": data}
+
+
+def _is_progressive(data: bytes) -> bool:
+    """Whether a JPEG's frame header is SOF2 (a walk over its marker segments up to the frame or the first scan)."""
+    pos, n = 2, len(data)
+    if data[:2] != b"\xff\xd8":
+        return False
+    while pos + 4 <= n and data[pos] == 0xFF:
+        m = data[pos + 1]
+        if m == 0xC2:
+            return True
+        if m in (0xDA, 0xD9) or 0xC0 <= m <= 0xCF and m not in (0xC4, 0xC8, 0xCC):
+            return False
+        pos += 2 + ((data[pos + 2] << 8) | data[pos + 3])
+    return False
+
+
 class _DecoderBase:
     """What the device decoders share: the buffers, and a `decode` that sends every source to the decoder whose parser takes it and
     everything else, and every file a kernel flagged, through `_decode` (Pillow)."""
@@ -420,8 +599,9 @@ class _DecoderBase:
 
     def _count(self, groups, loaded, rest):
         for d, idx in groups:
-            d.stats["device"] += len(idx) - len(d.last_errors)
-            d.stats["flagged"] += len(d.last_errors)
+            bad = sum(1 for i in idx if i in d.last_errors)
+            d.stats["device"] += len(idx) - bad
+            d.stats["flagged"] += bad
         self.stats["unsupported"] += len(rest)
 
     def _upload(self, total: int):
@@ -495,11 +675,48 @@ class JpegDecoder(_DecoderBase):
     files `parse` accepts are decoded by csrc/jpegdec.hip: their descriptors, tables and scan bytes go up in one copy from one pinned
     staging buffer, four launches decode any number of files together, and the host reads one error word per file.  Every other
     source, and every file the kernels flagged, goes through `_decode` -- which returns Pillow's pixels or raises its OSError, as
-    without the decoder.  Owns and grows its buffers, like InputPipeline.  `stats` counts which way the sources went."""
+    without the decoder.  Owns and grows its buffers, like InputPipeline.  `stats` counts which way the sources went.
+    progressive: the progressive files `parse_jpeg_progressive` accepts are decoded on the device too (csrc/jpegprog.hip), in the same
+    call and into the same `out`, with one launch sequence of their own; they count under `stats` like the baseline ones, and
+    `progressive_stats` says how many of each count were progressive (`unsupported`: SOF2 files the parser refused)."""
+
+    def __init__(self, device, ops=None, progressive: bool = False):
+        super().__init__(device, ops)
+        self.progressive = bool(progressive)
+        self._prog = _ProgressiveJpeg(self.device, self.ops) if self.progressive else None
+        self.progressive_stats = self._prog.stats if self._prog is not None else {"device": 0, "unsupported": 0, "flagged": 0}
 
     @staticmethod
     def parse(data: bytes) -> Optional[Dict]:
         return parse_jpeg(data)
+
+    def load(self, source):
+        data, plan = super().load(source)
+        if plan is None and self.progressive:
+            plan = parse_jpeg_progressive(data)
+        return data, plan
+
+    def _groups(self, plans):
+        if self._prog is None:
+            return super()._groups(plans)
+        is_prog = lambda p: p.get("format") == "jpegprog"
+        return [(self, [i for i, p in enumerate(plans) if p is not None and not is_prog(p)]),
+                (self._prog, [i for i, p in enumerate(plans) if p is not None and is_prog(p)])]
+
+    def _count(self, groups, loaded, rest):
+        super()._count(groups, loaded, rest)
+        self._count_progressive(groups, loaded, rest)
+
+    def _count_progressive(self, groups, loaded, rest):
+        """The progressive group's counts into this decoder's `stats`; the refused SOF2 files into `progressive_stats`."""
+        if self._prog is None:
+            return
+        for d, idx in groups:
+            if d is self._prog:
+                bad = sum(1 for i in idx if i in d.last_errors)
+                self.stats["device"] += len(idx) - bad
+                self.stats["flagged"] += bad
+        self._prog.stats["unsupported"] += sum(1 for i in rest if _is_progressive(loaded[i][0]))
 
     def _pack(self, plans: Sequence[Dict], out_offsets: Sequence[int]):
         """The upload block of `plans` in the staging buffer -> (block bytes, images, segments, workspace bytes)."""
@@ -547,6 +764,75 @@ class JpegDecoder(_DecoderBase):
             o.jpegdec_entropy(dev, self._host, total, n, nseg, ws)
             o.jpegdec_idct(dev, self._host, total, n, nseg, ws)
             o.jpegdec_pixels(dev, self._host, total, n, nseg, ws, out, err)
+        self._launched(launches)
+
+
+class _ProgressiveJpeg(_DecoderBase):
+    """The progressive group of a JpegDecoder: its own staging buffer and workspace (both groups are in flight in one call), the packing
+    of `parse_jpeg_progressive`'s plans into the block of csrc/jpegprog.hip, and its four launches.  `stats` is the owner's
+    `progressive_stats`."""
+
+    def _pack(self, plans: Sequence[Dict], out_offsets: Sequence[int]):
+        """The upload block of `plans` in the staging buffer -> (block bytes, images, scans, segments, table versions, workspace bytes)."""
+        n = len(plans)
+        imgs = (_lib.GanJpegdecImage * n)()
+        nscan = sum(len(p["scans"]) for p in plans)
+        nseg = sum(len(sc["seg_begin"]) for p in plans for sc in p["scans"])
+        nver = sum(len(p["versions"]) for p in plans)
+        o_pimg, o_scan, o_seg, o_dht, o_qt, o_data = self.ops.jpegprog_block_offsets(n, nscan, nseg, nver)
+        span = lambda p: (int(p["scans"][0]["seg_begin"][0]), int(p["scans"][-1]["seg_end"][-1]))      # first scan byte .. last scan's end
+        total = o_data + sum(-(-(span(p)[1] - span(p)[0]) // 16) * 16 for p in plans)
+        pimg, scans, segs = np.zeros((n, 8), np.int32), np.zeros((nscan, 16), np.int32), np.zeros((nseg, 8), np.int32)
+        host = self._grow("_host", total, host=True).numpy()
+        host[:o_pimg] = 0
+        host[o_dht:o_data] = 0
+        c0 = s0 = v0 = 0
+        at = o_data
+        for i, (p, im) in enumerate(zip(plans, imgs)):
+            im.ncomp, im.H, im.W, im.hmax, im.vmax, im.mcux, im.mcuy = p["ncomp"], p["H"], p["W"], p["hmax"], p["vmax"], p["mcux"], p["mcuy"]
+            for c in range(3):
+                im.dc_tab[c], im.ac_tab[c], im.q_tab[c] = 0, 2, p["q_tab"][c]
+            im.out_off = int(out_offsets[i])
+            sb, se = span(p)
+            shift = at - sb
+            k = sum(len(sc["seg_begin"]) for sc in p["scans"])
+            pimg[i] = (c0, len(p["scans"]), s0, k, v0, len(p["versions"]), p["nlevel"], 0)
+            for j, sc in enumerate(p["scans"]):
+                scans[c0 + j, :11] = (i, sc["comp"], sc["Ss"], sc["Se"], sc["Ah"], sc["Al"], sc["tab"][0], sc["tab"][1], sc["tab"][2], sc["dep"], sc["level"])
+            for j in sorted(range(len(p["scans"])), key=lambda j: p["scans"][j]["level"]):              # stable: file order inside a level
+                sc = p["scans"][j]
+                m = len(sc["seg_begin"])
+                rows = segs[s0:s0 + m]
+                rows[:, 0], rows[:, 1], rows[:, 2] = i, c0 + j, np.arange(m)
+                rows[:, 3] = np.arange(m) * sc["per"]
+                rows[:, 4] = np.minimum(sc["per"], sc["units"] - rows[:, 3])
+                rows[:, 5], rows[:, 6] = sc["seg_begin"] + shift, sc["seg_end"] + shift
+                s0 += m
+            host[at:at + se - sb] = np.frombuffer(p["data"], np.uint8, se - sb, sb)
+            for t, raw in enumerate(p["versions"]):
+                host[o_dht + (v0 + t) * 272:o_dht + (v0 + t) * 272 + len(raw)] = np.frombuffer(raw, np.uint8)
+            for t, q in p["qt"].items():
+                host[o_qt + (4 * i + t) * 128:o_qt + (4 * i + t + 1) * 128].view(np.uint16)[:] = q
+            c0, v0, at = c0 + len(p["scans"]), v0 + len(p["versions"]), at + -(-(se - sb) // 16) * 16
+        ws_bytes = self.ops.jpegprog_bounds(imgs, nver)
+        host[:n * C.sizeof(_lib.GanJpegdecImage)] = np.frombuffer(imgs, np.uint8)
+        host[o_pimg:o_scan].view(np.int32)[:] = pimg.reshape(-1)
+        host[o_scan:o_seg].view(np.int32)[:] = scans.reshape(-1)
+        host[o_seg:o_dht].view(np.int32)[:] = segs.reshape(-1)
+        return total, n, nscan, nseg, nver, ws_bytes
+
+    def _launch(self, plans: Sequence[Dict], offsets: Sequence[int], out: torch.Tensor, err: torch.Tensor) -> None:
+        total, n, nscan, nseg, nver, ws_bytes = self._pack(plans, offsets)
+        self.last_block = (total, n, nscan, nseg, nver)
+        ws = self._grow("_ws", ws_bytes)
+        dev, o = self._upload(total), self.ops
+        counts = (n, nscan, nseg, nver)
+
+        def launches():
+            o.jpegprog_tables(dev, self._host, total, counts, ws)
+            o.jpegprog_entropy(dev, self._host, total, counts, ws)
+            o.jpegprog_idct(dev, self._host, total, counts, ws)
+            o.jpegprog_pixels(dev, self._host, total, counts, ws, out, err)
         self._launched(launches)
 
 
@@ -687,26 +973,41 @@ class DeviceDecoder(_DecoderBase):
     """Both device decoders behind one `decode`: every source is read once and goes by its content, not its suffix, to `self.jpeg`
     (a JpegDecoder) or `self.png` (a PngDecoder); everything lands in one arena in one call, and the error words of both come back in one
     download.  The sub-decoders keep their own `stats`
-    (`unsupported`: files of their format that their parser refused); `self.stats` counts all sources."""
+    (`unsupported`: files of their format that their parser refused); `self.stats` counts all sources.
+    progressive: `self.jpeg` is a JpegDecoder(progressive=True); its progressive group launches in the same call."""
 
-    def __init__(self, device, jpeg: bool = True, png: bool = True, ops=None):
+    def __init__(self, device, jpeg: bool = True, png: bool = True, ops=None, progressive: bool = False):
         if not (jpeg or png):
             raise ValueError("DeviceDecoder: at least one of jpeg and png")
+        if progressive and not jpeg:
+            raise ValueError("DeviceDecoder: progressive needs jpeg")
         super().__init__(device, ops)
-        self.jpeg = JpegDecoder(self.device, ops=self.ops) if jpeg else None
+        self.jpeg = JpegDecoder(self.device, ops=self.ops, progressive=progressive) if jpeg else None
         self.png = PngDecoder(self.device, ops=self.ops) if png else None
+        self.progressive = bool(progressive)
+
+    @property
+    def progressive_stats(self):
+        return self.jpeg.progressive_stats
 
     def parse(self, data: bytes) -> Optional[Dict]:
         plan = parse_jpeg(data) if self.jpeg is not None else None
+        if plan is None and self.progressive:
+            plan = parse_jpeg_progressive(data)
         return parse_png(data) if plan is None and self.png is not None else plan
 
     def _groups(self, plans):
-        is_png = lambda p: p.get("format") == "png"
-        return [(self.jpeg, [i for i, p in enumerate(plans) if p is not None and not is_png(p)]),
-                (self.png, [i for i, p in enumerate(plans) if p is not None and is_png(p)])]
+        fmt = lambda p: p.get("format", "jpeg")
+        groups = [(self.jpeg, [i for i, p in enumerate(plans) if p is not None and fmt(p) == "jpeg"]),
+                  (self.png, [i for i, p in enumerate(plans) if p is not None and fmt(p) == "png"])]
+        if self.progressive:
+            groups.insert(1, (self.jpeg._prog, [i for i, p in enumerate(plans) if p is not None and fmt(p) == "jpegprog"]))
+        return groups
 
     def _count(self, groups, loaded, rest):
         super()._count(groups, loaded, rest)
+        if self.progressive:
+            self.jpeg._count_progressive(groups, loaded, rest)
         self.stats["device"] += sum(len(idx) - len(d.last_errors) for d, idx in groups)
         self.stats["flagged"] += len(self.last_errors)
         for i in rest:
@@ -731,18 +1032,22 @@ class ImageStore:
     pool and decoded chunk by chunk (DECODE_CHUNK files) straight into the arena; streaming: `fetch` decodes its batch there.  Every
     other file, and every file the decoder flags, still goes through Pillow; the store holds the same bytes either way.
     device_png: the same for the PNGs among the files, with a `PngDecoder`; with both switches one `DeviceDecoder` takes both formats.
+    device_progressive (needs device_decode): the progressive JPEGs the device decoder takes are decoded there too.
     decoder: any object with JpegDecoder's `decode`, used instead of a new one when a switch is on."""
 
     def __init__(self, paths: Sequence, device, budget_bytes: Optional[int] = None, workers: Optional[int] = None, folder=None,
-                 device_decode: bool = False, decoder=None, device_png: bool = False):
+                 device_decode: bool = False, decoder=None, device_png: bool = False, device_progressive: bool = False):
         self._pool = None
         self._decoder = None
+        if device_progressive and not device_decode:
+            raise ValueError("device_progressive needs device_decode")
         self.paths = [os.fspath(p) for p in paths]
         if not self.paths:
             raise FileNotFoundError(f"no images found in {os.fspath(folder) if folder is not None else 'the given (empty) list of paths'}")
         self.device = normalize_device(device)
         if device_decode or device_png:
-            make = (lambda dev: DeviceDecoder(dev)) if device_decode and device_png else PngDecoder if device_png else JpegDecoder
+            prog = bool(device_progressive)
+            make = (lambda dev: DeviceDecoder(dev, progressive=prog)) if device_decode and device_png else PngDecoder if device_png else (lambda dev: JpegDecoder(dev, progressive=prog))
             self._decoder = decoder if decoder is not None else make(self.device)
         self.workers = max(1, min(16, int(workers) if workers is not None else (os.cpu_count() or 1)))
         self._pool = ThreadPoolExecutor(self.workers)

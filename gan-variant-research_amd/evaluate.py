@@ -286,7 +286,7 @@ def check_dataset_overlap(fake_paths: Sequence[Path], real_paths: Sequence[Path]
 # ------------------------------------------------------------------------------------------------ images -> features
 @torch.inference_mode()
 def extract_features(paths: Sequence, extractor: Callable, device, batch: int = 64, img_size: int = 299, io_threads: int = 8,
-                     device_decode: bool = False, device_png: bool = False) -> torch.Tensor:
+                     device_decode: bool = False, device_png: bool = False, device_progressive: bool = False) -> torch.Tensor:
     """The reference's loader and feature loop (datasets.py:52-66, features.py:44-77) on the device: decode (DeviceDecoder for the formats
     asked, Pillow on a pool of io_threads otherwise), `Image.resize((S, S), BILINEAR)` as InputPipeline.run_u8, then
     extractor(uint8 (B, 3, S, S)) -> (B, D).  Returns the (N, D) features, on the device."""
@@ -297,7 +297,9 @@ def extract_features(paths: Sequence, extractor: Callable, device, batch: int = 
     if batch < 1 or io_threads < 1:
         raise ValueError(f"extract_features: batch = {batch}, io_threads = {io_threads}: at least 1 each")
     pipe = dataio.InputPipeline(img_size, device, max_batch=batch, filter=dataio.BILINEAR)
-    dec = dataio.DeviceDecoder(device, jpeg=device_decode, png=device_png) if device_decode or device_png else None
+    if device_progressive and not device_decode:
+        raise ValueError("device_progressive needs device_decode")
+    dec = dataio.DeviceDecoder(device, jpeg=device_decode, png=device_png, progressive=device_progressive) if device_decode or device_png else None
     feats = []
     with ThreadPoolExecutor(min(io_threads, 16)) as pool:
         for at in range(0, len(paths), batch):
@@ -408,6 +410,7 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--real-features", type=str, default=None, help="Real features (.npy, or the cache .npz): skips extraction for that side")
     p.add_argument("--fake-features", type=str, default=None, help="Fake features (.npy, or the cache .npz): skips extraction for that side")
     p.add_argument("--device-decode", action="store_true", help="Decode baseline JPEGs on the device")
+    p.add_argument("--device-progressive", action="store_true", help="With --device-decode: decode progressive JPEGs on the device too")
     p.add_argument("--device-png", action="store_true", help="Decode PNGs on the device")
     p.add_argument("--io-threads", type=int, default=8, help="Threads that read and (without the device decoders) decode files")
     return p
@@ -427,7 +430,10 @@ def _side(name: str, folder: Optional[str], feature_file: Optional[str], recursi
 
 
 def main(argv: Optional[Sequence[str]] = None) -> int:
-    a = build_parser().parse_args(argv)
+    parser = build_parser()
+    a = parser.parse_args(argv)
+    if a.device_progressive and not a.device_decode:
+        parser.error("--device-progressive needs --device-decode")
     cfg: Dict = {"name": "default_run", "real": {"mode": "folder"}}
     if a.config:
         import yaml
@@ -468,7 +474,8 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     print(f"Fake dataset hash: {fake_hash}\nReal dataset hash: {real_hash}")
 
     extractor = None
-    kw = dict(device=device, batch=batch, img_size=img_size, io_threads=a.io_threads, device_decode=a.device_decode, device_png=a.device_png)
+    kw = dict(device=device, batch=batch, img_size=img_size, io_threads=a.io_threads, device_decode=a.device_decode, device_png=a.device_png,
+              **(dict(device_progressive=True) if a.device_progressive else {}))
     real_cache = cache_dir / "real_feats"
     if real_feats is None and not a.no_cache:
         cached = load_cached_stats(real_hash, real_cache)

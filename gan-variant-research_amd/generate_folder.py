@@ -9,6 +9,7 @@ Build-only flags: --ngf / --n-blocks (the reference reads the architecture from 
 reference's autocast by default), --graph (one hipGraph replay per batch shape), --host-io (resize and convert with PIL / torch on the host),
 --device-jpeg (the JPEG files are encoded on the device as well, byte-identical to PIL's), --io-threads N (PIL decodes / saves on a thread pool),
 --device-decode [--decode-chunk N] (baseline JPEGs are decoded on the device, N files at a time ahead of the generator, pixel-identical to PIL's),
+--device-progressive (with --device-decode, progressive JPEGs are decoded on the device too),
 --device-png (PNGs are decoded on the device the same way, --decode-chunk files at a time; with --device-decode one decoder takes both formats),
 --which G_A2B|G_B2A (a CycleGAN checkpoint of train_basic is recognised by its keys; this picks the generator, architecture read from the keys).
 """
@@ -40,11 +41,14 @@ def parse_args(argv=None) -> argparse.Namespace:
     ap.add_argument("--device-jpeg", action="store_true", help="encode the JPEGs on the device, byte-identical to PIL's (build-only flag)")
     ap.add_argument("--io-threads", type=int, default=1, help="threads for the PIL decodes (and the PIL saves without --device-jpeg), at most 16 (build-only flag)")
     ap.add_argument("--device-decode", action="store_true", help="decode baseline JPEGs on the device, pixel-identical to PIL's (build-only flag)")
+    ap.add_argument("--device-progressive", action="store_true", help="with --device-decode: decode progressive JPEGs on the device too (build-only flag)")
     ap.add_argument("--decode-chunk", type=int, default=256, help="files per device decode, independent of --batch (build-only flag)")
     ap.add_argument("--device-png", action="store_true", help="decode PNGs on the device, pixel-identical to PIL's (build-only flag)")
     args = ap.parse_args(argv)
     if args.device_png and (args.host_io or args.device == "cpu"):
         ap.error("--device-png feeds the device I/O path on the GPU: not with --host-io or --device cpu")
+    if args.device_progressive and not args.device_decode:
+        ap.error("--device-progressive widens what --device-decode takes: it needs --device-decode")
     if args.device_decode and (args.host_io or args.device == "cpu"):
         ap.error("--device-decode feeds the device I/O path on the GPU: not with --host-io or --device cpu")
     if args.decode_chunk < 1:
@@ -79,7 +83,8 @@ def main(argv=None) -> int:
     n = I.stylize_folder(G, src_dir=args.photos, out_dir=args.out, device=args.device, img_size=args.size, batch=args.batch, limit=args.limit,
                          device_io=args.device == "cuda" and not args.host_io, device_jpeg=args.device_jpeg,
                          io_threads=args.io_threads, **(dict(decode_chunk=args.decode_chunk) if args.device_decode or args.device_png else {}),
-                         **(dict(device_decode=True) if args.device_decode else {}), **(dict(device_png=True) if args.device_png else {}))
+                         **(dict(device_decode=True) if args.device_decode else {}), **(dict(device_png=True) if args.device_png else {}),
+                         **(dict(device_progressive=True) if args.device_progressive else {}))
     print("Done.")
     return n
 

@@ -199,27 +199,27 @@ def _jpeg_encoder(G, device, batch: int, H: int, W: int) -> JpegEncoder:
     return enc
 
 
-def _jpeg_decoder(G, device):
+def _jpeg_decoder(G, device, progressive: bool = False):
     """The decoder cached on the generator, like `_infer_pipe`."""
     from . import dataio
     dev = dataio.normalize_device(device)
     dec = getattr(G, "_jpeg_dec", None)
-    if dec is None or dec.device != dev:
-        dec = dataio.JpegDecoder(dev)
+    if dec is None or dec.device != dev or dec.progressive != bool(progressive):
+        dec = dataio.JpegDecoder(dev, progressive=progressive)
         object.__setattr__(G, "_jpeg_dec", dec)
     return dec
 
 
-def _folder_decoder(G, device, jpeg: bool, png: bool):
+def _folder_decoder(G, device, jpeg: bool, png: bool, progressive: bool = False):
     """The decoder of the folder path for the switches that are on, cached on the generator: a JpegDecoder, a PngDecoder, or one
     DeviceDecoder for both formats."""
     from . import dataio
     if not png:
-        return _jpeg_decoder(G, device)
+        return _jpeg_decoder(G, device, progressive)
     dev = dataio.normalize_device(device)
-    name, make = ("_device_dec", dataio.DeviceDecoder) if jpeg else ("_png_dec", dataio.PngDecoder)
+    name, make = ("_device_dec", lambda d: dataio.DeviceDecoder(d, progressive=progressive)) if jpeg else ("_png_dec", dataio.PngDecoder)
     dec = getattr(G, name, None)
-    if dec is None or dec.device != dev:
+    if dec is None or dec.device != dev or getattr(dec, "progressive", False) != bool(progressive and jpeg):
         dec = make(dev)
         object.__setattr__(G, name, dec)
     return dec
@@ -228,7 +228,7 @@ def _folder_decoder(G, device, jpeg: bool, png: bool):
 @torch.inference_mode()
 def stylize_folder(G, src_dir: str, out_dir: str, device: str = "cuda", img_size: int = 256, batch: int = 16, limit: Optional[int] = None,
                    device_io: bool = False, device_jpeg: bool = False, io_threads: int = 1, device_decode: bool = False, decode_chunk: int = 256,
-                   device_png: bool = False) -> int:
+                   device_png: bool = False, device_progressive: bool = False) -> int:
     """generate_folder.py:207-252 with PIL doing what torchvision's Resize(BILINEAR) / ToTensor / Normalize / ToPILImage do there.
     device_io: PIL only decodes and encodes; each photo is uploaded as uint8 HWC, `stylize_images` resizes, normalises, runs the
     generator and converts on the device, and one contiguous HWC download feeds PIL.  The files written are byte-identical.
@@ -239,13 +239,16 @@ def stylize_folder(G, src_dir: str, out_dir: str, device: str = "cuda", img_size
     flight are its throughput), one chunk ahead on a side stream while the generator works on the previous one; other files, and files
     the decoder flags, still go through PIL.  device_png (needs device_io; independent of device_decode): the same for the PNGs, with
     `dataio.PngDecoder` (one workgroup per file: again the files in flight are its throughput); with both switches one
-    `dataio.DeviceDecoder` reads every file once and sends it by its content.  Same files either way."""
+    `dataio.DeviceDecoder` reads every file once and sends it by its content.  device_progressive (needs device_decode): the
+    progressive JPEGs `dataio.parse_jpeg_progressive` accepts are decoded on the device too, in the same calls.  Same files either way."""
     import numpy as np
     from PIL import Image
     if device_jpeg and not device_io:
         raise ValueError("device_jpeg=True needs device_io=True: the encoder reads the uint8 batch the device epilogue leaves")
     if device_decode and not device_io:
         raise ValueError("device_decode=True needs device_io=True: the decoder leaves the uint8 images the device input pipeline reads")
+    if device_progressive and not device_decode:
+        raise ValueError("device_progressive=True needs device_decode=True: it widens the class of JPEGs the device decoder takes")
     if device_png and not device_io:
         raise ValueError("device_png=True needs device_io=True: the decoder leaves the uint8 images the device input pipeline reads")
     if decode_chunk < 1:
@@ -286,7 +289,7 @@ def stylize_folder(G, src_dir: str, out_dir: str, device: str = "cuda", img_size
     def decoded_ahead():
         """The images of `paths` in chunks of decode_chunk files, the next chunk being decoded while the caller works on this one."""
         from concurrent.futures import ThreadPoolExecutor
-        dec = _folder_decoder(G, device, device_decode, device_png)
+        dec = _folder_decoder(G, device, device_decode, device_png, device_progressive)
         cuda = dec.device.type == "cuda"
         side = torch.cuda.Stream(dec.device) if cuda else None
         main = torch.cuda.current_stream(dec.device) if cuda else None

@@ -613,6 +613,39 @@ class HipOps:
         self._now("gan_jpegdec_pixels", *self._jpegdec_args(blk_dev, blk_host, nbytes, n, nseg, ws), C.c_void_p(out.data_ptr()), out.numel(),
                   C.c_void_p(err.data_ptr()), self._s())
 
+    # ---- progressive JPEG decoder (csrc/jpegprog.hip).  counts = (images, scans, segments, table versions) of the block.
+    def jpegprog_block_offsets(self, n, nscan, nseg, nver):
+        """Byte offsets (progressive image descriptors, scans, segments, dht, qt, scan bytes) of the upload block."""
+        off = (C.c_int64 * 6)()
+        self._now("gan_jpegprog_block_offsets", int(n), int(nscan), int(nseg), int(nver), off)
+        return tuple(int(v) for v in off)
+
+    def jpegprog_bounds(self, imgs, nver) -> int:
+        """imgs: a ctypes array of _lib.GanJpegdecImage; fills their coef_off / plane_off and returns the workspace bytes."""
+        ws = C.c_int64(0)
+        self._now("gan_jpegprog_bounds", C.cast(imgs, C.c_void_p), len(imgs), int(nver), C.byref(ws))
+        return int(ws.value)
+
+    def _jpegprog_args(self, blk_dev, blk_host, nbytes, counts, ws):
+        a = self._jpegdec_args(blk_dev, blk_host, nbytes, counts[0], counts[2], ws)
+        return a[:3] + tuple(int(v) for v in counts) + a[5:]
+
+    def jpegprog_tables(self, blk_dev, blk_host, nbytes, counts, ws):
+        """DHT versions of the block -> decode tables in ws; zeroes the error words and the coefficients."""
+        self._now("gan_jpegprog_tables", *self._jpegprog_args(blk_dev, blk_host, nbytes, counts, ws), self._s())
+
+    def jpegprog_entropy(self, blk_dev, blk_host, nbytes, counts, ws):
+        """The scans -> int16 coefficients in ws: one workgroup per image, one lane per (scan, restart segment), level after level."""
+        self._now("gan_jpegprog_entropy", *self._jpegprog_args(blk_dev, blk_host, nbytes, counts, ws), self._s())
+
+    def jpegprog_idct(self, blk_dev, blk_host, nbytes, counts, ws):
+        self._now("gan_jpegprog_idct", *self._jpegprog_args(blk_dev, blk_host, nbytes, counts, ws), self._s())
+
+    def jpegprog_pixels(self, blk_dev, blk_host, nbytes, counts, ws, out, err):
+        assert out.dtype == torch.uint8 and out.is_contiguous() and err.dtype == torch.int32 and err.is_contiguous() and err.numel() >= counts[0]
+        self._now("gan_jpegprog_pixels", *self._jpegprog_args(blk_dev, blk_host, nbytes, counts, ws), C.c_void_p(out.data_ptr()), out.numel(),
+                  C.c_void_p(err.data_ptr()), self._s())
+
     # ---- PNG decoder (csrc/pngdec.hip; dataio.PngDecoder owns the buffers); launched at once, like the JPEG decoder's entries
     def pngdec_block_offsets(self, n):
         """Byte offsets (palettes, first stream) of the upload block of n files."""

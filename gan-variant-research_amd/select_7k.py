@@ -236,6 +236,7 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--img-size", type=int, default=299)
     p.add_argument("--io-threads", type=int, default=8)
     p.add_argument("--device-decode", action="store_true", help="Decode baseline JPEGs on the device")
+    p.add_argument("--device-progressive", action="store_true", help="With --device-decode: decode progressive JPEGs on the device too")
     p.add_argument("--device-png", action="store_true", help="Decode PNGs on the device")
     p.add_argument("--device", type=str, default=None, help="Device: cuda or cuda:N")
     p.add_argument("--no-copy", action="store_true", help="Write the meta file and the table, copy no image")
@@ -243,14 +244,18 @@ def build_parser() -> argparse.ArgumentParser:
 
 
 def main(argv: Optional[Sequence[str]] = None) -> int:
-    a = build_parser().parse_args(argv)
+    parser = build_parser()
+    a = parser.parse_args(argv)
+    if a.device_progressive and not a.device_decode:
+        parser.error("--device-progressive needs --device-decode")
     device = dataio.normalize_device(a.device or "cuda")
     if a.cand_features is not None and len(a.cand_features) != len(a.cand_roots):
         raise SystemExit(f"Error: {len(a.cand_features)} --cand-features files for {len(a.cand_roots)} --cand_roots")
     if not a.real and not a.real_features:
         raise SystemExit("Error: --real path (or --real-features FILE) is required")
     os.makedirs(a.outdir, exist_ok=True)
-    kw = dict(device=device, batch=a.batch, img_size=a.img_size, io_threads=a.io_threads, device_decode=a.device_decode, device_png=a.device_png)
+    kw = dict(device=device, batch=a.batch, img_size=a.img_size, io_threads=a.io_threads, device_decode=a.device_decode, device_png=a.device_png,
+              **(dict(device_progressive=True) if a.device_progressive else {}))
     extractor = None
 
     def side(folder, feature_file, what):

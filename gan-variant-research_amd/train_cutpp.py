@@ -11,6 +11,7 @@ transform); with `--synthetic` uniform noise batches of the right shape stand in
 that do not exist are an error.  Build-only keys live under `mi355x:` (amp dtype, synthetic data, dataset_cache_gb,
 device_decode: the stores decode their baseline JPEGs on the device with dataio.JpegDecoder, default false;
 device_png: the same for their PNGs with dataio.PngDecoder, default false;
+device_progressive: with device_decode, the progressive JPEGs are decoded on the device too, default false;
 decoupled_weight_decay: `optim.{G,D}.weight_decay` as AdamW's decay instead of torch.optim.Adam's L2 term).
 
 `--gpus N` (build-only flag; launch.py) trains data-parallel on N GPUs of one node: `batch_size` stays the per-GPU batch, and at every
@@ -88,14 +89,15 @@ def _list_images(folder) -> List[Path]:
 def build_store(paths: List[Path], device, config: dict, name: str, folder=None, workers: Optional[int] = None, quiet: bool = False):
     """One `dataio.ImageStore` per domain, decoded at start-up; `mi355x.dataset_cache_gb` (default 8) is what may stay on the device;
     `mi355x.device_decode` (default false) decodes the baseline JPEGs on the device instead of with Pillow (same bytes), and
-    `mi355x.device_png` (default false) the PNGs.
+    `mi355x.device_png` (default false) the PNGs; `mi355x.device_progressive` (default false, needs device_decode) the progressive JPEGs too.
     workers: decode threads (data parallel: 16 // N per rank, every rank holds its own store)."""
     import time
     from .dataio import DEFAULT_CACHE_GB, ImageStore
     build = config.get("mi355x", {}) or {}
     t0 = time.perf_counter()
     store = ImageStore(paths, device, budget_bytes=int(float(build.get("dataset_cache_gb", DEFAULT_CACHE_GB)) * (1 << 30)), workers=workers, folder=folder,
-                       device_decode=bool(build.get("device_decode", False)), **({"device_png": True} if build.get("device_png", False) else {}))
+                       device_decode=bool(build.get("device_decode", False)), **({"device_png": True} if build.get("device_png", False) else {}),
+                       **({"device_progressive": True} if build.get("device_progressive", False) else {}))
     mode = f"resident on {store.device}" if store.resident else "streaming (decoded per batch)"
     if not quiet:
         print(f"[data] {name}: {len(store)} images, {store.nbytes / 1e6:.1f} MB decoded, {mode}, {time.perf_counter() - t0:.2f} s")

@@ -547,6 +547,80 @@ int gan_jpegdec_idct(const void* blk_dev, const void* blk_host, int64_t blk_byte
 int gan_jpegdec_pixels(const void* blk_dev, const void* blk_host, int64_t blk_bytes, int n, int nseg, void* ws, int64_t ws_bytes, uint8_t* out,
                        int64_t out_bytes, int32_t* err, void* stream);
 
+/* ---- Progressive JPEG decoder on the device (SOF2, Huffman): the same pixels, for the files a host parser accepted: the component
+ *      classes of the baseline decoder, and a scan script that libjpeg decodes without a warning and that brings every coefficient of
+ *      every component to its last bit (nothing is left to libjpeg's block smoothing).  A DC scan (Ss = Se = 0) holds all components
+ *      interleaved or one component; an AC scan (1 <= Ss <= Se <= 63) holds one component; Al <= 13.  The scans are untrusted in the
+ *      same way as the baseline decoder's, and an irregularity sets bits of the image's error word.
+ *
+ *      One upload block (all offsets from its start; n images, nscan scans, nseg restart segments, nver Huffman table versions):
+ *        gan_jpegdec_image [n] | gan_jpegprog_image [n] | gan_jpegprog_scan [nscan] | gan_jpegprog_segment [nseg] | uint8 dht [nver][272]
+ *        | uint16 qt [n][4][64] | scan bytes
+ *      The gan_jpegdec_image of a file carries its geometry, q_tab, coef_off / plane_off / out_off exactly as for the baseline decoder
+ *      (seg_first, seg_count, dc_tab and ac_tab are not read), so the stages behind the coefficients are the baseline decoder's own code
+ *      over the same workspace layout.  A DHT that a file redefines is a new version: scans name versions (counted inside their file),
+ *      not slots.  gan_jpegprog_block_offsets gives the byte offsets; every part starts at a multiple of 16.
+ *      Workspace (16-byte aligned, gan_jpegprog_bounds bytes): decode tables [nver] | error words int32 [n] | int16 coefficients |
+ *      uint8 component planes, the last two as in the baseline decoder.
+ *      A single-component scan walks the component's real blocks in raster order, ceil(cw / 8) x ceil(ch / 8) with
+ *      cw = ceil(W h_c / hmax), ch = ceil(H v_c / vmax), and its restart interval counts those blocks; an interleaved DC scan walks
+ *      the MCUs.  Both store into the MCU-padded grid.
+ *      Refused with a message, before any launch: everything the baseline entries refuse; counts below 1; more than
+ *      GAN_JPEGPROG_MAX_SCANS scans or GAN_JPEGPROG_MAX_TABLES table versions in one file; scan, segment or version ranges outside
+ *      their tables; a scan whose component, band, Ah / Al, table versions, dependency index or level is out of range; an earlier scan
+ *      of the same file that touches one of its coefficients on the same or a later level; a segment that names no scan of its
+ *      image, units beyond its scan or bytes outside the block's scan area; segments of a scan that are out of order, overlap or do
+ *      not cover all of its units. */
+#define GAN_JPEGPROG_MAX_SCANS 64
+#define GAN_JPEGPROG_MAX_TABLES 64
+typedef struct gan_jpegprog_image {
+  int32_t scan_first, scan_count;    /* its scans in the scan table, file order */
+  int32_t seg_first, seg_count;      /* its restart segments in the segment table, ordered by the level of their scan */
+  int32_t ver_first, ver_count;      /* its Huffman table versions in dht */
+  int32_t nlevel;                    /* 1 + the largest level of its scans */
+  int32_t reserved;
+} gan_jpegprog_image;
+typedef struct gan_jpegprog_scan {
+  int32_t image;
+  int32_t comp;                      /* 0 .. ncomp - 1: that component alone; -1: all components interleaved (DC scans only) */
+  int32_t Ss, Se, Ah, Al;
+  int32_t tab[3];                    /* per component: the table version its symbols are coded with, counted inside the file; -1: none
+                                        (components outside the scan; DC refinement reads raw bits) */
+  int32_t dep;                       /* the latest earlier scan of the file (counted inside the file) that touches one of this scan's
+                                        (component, coefficient) pairs, -1: none */
+  int32_t level;                     /* scans of one level run side by side: larger than the level of every earlier scan that touches
+                                        one of this scan's pairs */
+  int32_t reserved[5];
+} gan_jpegprog_scan;
+typedef struct gan_jpegprog_segment {
+  int32_t image, scan;               /* scan: index into the block's scan table */
+  int32_t index;                     /* its number inside the scan: RST((index - 1) & 7) stands in front of it when index > 0 */
+  int32_t unit_first, unit_count;    /* MCUs (interleaved scan) or real blocks of the component, raster order */
+  int32_t byte_begin, byte_end;      /* its entropy-coded bytes in the block, the marker after them excluded */
+  int32_t reserved;
+} gan_jpegprog_segment;
+#define GAN_JPEGPROG_ERR_REFINE 256  /* a refinement scan's symbol with a size other than 0 or 1 */
+#define GAN_JPEGPROG_ERR_EOBRUN 512  /* an end-of-band run that outlasts the blocks of its segment */
+#define GAN_JPEGPROG_ERR_COEF 1024   /* a coefficient outside int16 */
+/* Host only.  off[0] gan_jpegprog_image, off[1] scans, off[2] segments, off[3] dht, off[4] qt, off[5] scan bytes. */
+int gan_jpegprog_block_offsets(int n, int nscan, int nseg, int nver, int64_t* off);
+/* Host only.  Fills coef_off and plane_off of imgs[0 .. n-1] (host memory) and gives the workspace size. */
+int gan_jpegprog_bounds(gan_jpegdec_image* imgs, int n, int nver, int64_t* ws_bytes);
+/* One wave per table version: the decode tables of gan_jpegdec_tables.  Also zeroes the error words and the coefficient area with one
+ * memset.  blk_host: the host copy of the block's descriptors, which every entry validates. */
+int gan_jpegprog_tables(const void* blk_dev, const void* blk_host, int64_t blk_bytes, int n, int nscan, int nseg, int nver, void* ws, int64_t ws_bytes,
+                        void* stream);
+/* One 64-lane workgroup per image; a lane takes one (scan, restart segment).  The levels run one after the other with a workgroup
+ * barrier between them; the segments of one level, which touch disjoint int16 slots, run on different lanes at the same time.  The
+ * file's first 16 table versions are held in LDS, later ones are read from the workspace.  ITU-T T.81 Annex G as libjpeg reads it. */
+int gan_jpegprog_entropy(const void* blk_dev, const void* blk_host, int64_t blk_bytes, int n, int nscan, int nseg, int nver, void* ws, int64_t ws_bytes,
+                         void* stream);
+/* gan_jpegdec_idct and gan_jpegdec_pixels over this block. */
+int gan_jpegprog_idct(const void* blk_dev, const void* blk_host, int64_t blk_bytes, int n, int nscan, int nseg, int nver, void* ws, int64_t ws_bytes,
+                      void* stream);
+int gan_jpegprog_pixels(const void* blk_dev, const void* blk_host, int64_t blk_bytes, int n, int nscan, int nseg, int nver, void* ws, int64_t ws_bytes,
+                        uint8_t* out, int64_t out_bytes, int32_t* err, void* stream);
+
 /* ---- PNG decoder on the device: the pixels Image.open(p).convert("RGB") gives, for the files a host parser accepted: no interlace,
  *      compression and filter method 0, colour type 0, 2, 4 or 6 at 8 bits (grey is replicated, alpha dropped, no compositing) or colour
  *      type 3 at 1, 2, 4 or 8 bits with a PLTE that covers every index its depth can give (a plain lookup; tRNS changes nothing).  The

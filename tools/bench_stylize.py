@@ -10,10 +10,13 @@
 (e) PNG decode (--png): the mixed PNGs and 256 PNGs of 256 x 256 (the JPEG folder's images) at batch 16 with device_jpeg: PIL decoding
     serially and on a pool (io_threads 4, 16) against the device decoder (device_png, decode_chunk 16 / 64 / 256); same files every mode
 
+(f) progressive JPEG decode (--progressive): 256 progressive JPEGs of 256 x 256 (the JPEG folder's images) at batch 16 with device_jpeg: PIL
+    decoding serially and on a pool (io_threads 4, 16) against device_progressive (with device_decode) at decode_chunk 64 / 256; same files every mode
+
 Every shape is warmed up; the two paths are then timed in rotation for --rounds rounds (a host clock around work that ends in a device
 synchronise: each call ends in a download); the median round and the spread (min .. max) are reported.  The outputs of the two paths
 are compared before anything is timed.
-usage: bench_stylize.py [--size 256] [--batches 1,4,16] [--calls 40] [--rounds 5] [--photos 64] [--out FILE] [--jpeg] [--only-jpeg] [--decode] [--only-decode] [--png] [--only-png]
+usage: bench_stylize.py [--size 256] [--batches 1,4,16] [--calls 40] [--rounds 5] [--photos 64] [--out FILE] [--jpeg] [--only-jpeg] [--decode] [--only-decode] [--png] [--only-png] [--progressive] [--only-progressive]
 """
 import argparse
 import os
@@ -43,8 +46,9 @@ def make_folder(root: Path, n: int, seed: int = 0):
         Image.fromarray(img).save(root / ("sub" if i % 4 == 0 else ".") / f"p{i:03d}.png")
 
 
-def make_jpeg_folder(root: Path, n: int, size: int = 256, seed: int = 1, png: bool = False):
-    """n JPEGs of size x size under root: the realistic input (the reference's photo_jpg folder).  png: the same images as PNGs."""
+def make_jpeg_folder(root: Path, n: int, size: int = 256, seed: int = 1, png: bool = False, progressive: bool = False):
+    """n JPEGs of size x size under root: the realistic input (the reference's photo_jpg folder).  png: the same images as PNGs;
+    progressive: the same images saved with Pillow's progressive scan script."""
     from PIL import Image
     rng = np.random.default_rng(seed)
     root.mkdir(parents=True, exist_ok=True)
@@ -55,7 +59,7 @@ def make_jpeg_folder(root: Path, n: int, size: int = 256, seed: int = 1, png: bo
         if png:
             Image.fromarray(img).save(root / f"q{i:03d}.png")
         else:
-            Image.fromarray(img).save(root / f"q{i:03d}.jpg", quality=90)
+            Image.fromarray(img).save(root / f"q{i:03d}.jpg", quality=90, progressive=progressive)
 
 
 JPEG_MODES = (("a  device_io, serial PIL", dict()), ("b  PIL pool, io_threads 4", dict(io_threads=4)), ("b  PIL pool, io_threads 16", dict(io_threads=16)),
@@ -107,6 +111,46 @@ def decode_section(G, dev, S, rounds, photos, tmp: Path, png: bool = False):
                 lines.append(f"({d}) {name[3:]}: {verdict} the PIL pools beyond both spreads (its min {min(v):.1f} vs their max {best_pool:.1f})")
         for ln in lines[-(2 * len(MODES) - 2):]:
             print(ln, flush=True)
+    return lines
+
+
+PROGRESSIVE_MODES = (("a  PIL serial", dict()), ("b  PIL pool, io_threads 4", dict(io_threads=4)), ("b  PIL pool, io_threads 16", dict(io_threads=16)),
+                     ("f  device_progressive, chunk 64", dict(device_decode=True, device_progressive=True, decode_chunk=64)),
+                     ("f  device_progressive, chunk 256", dict(device_decode=True, device_progressive=True, decode_chunk=256)))
+
+
+def progressive_section(G, dev, S, rounds, tmp: Path):
+    """(f): every mode writes the same files (checked first), then the modes run in rotation; images/s, median [min .. max]."""
+    n, src = 256, tmp / "progressive"
+    make_jpeg_folder(src, n, S, progressive=True)
+    lines = [f"# (f) images/s over one pass of a folder of {n} progressive JPEGs of {S}x{S}, batch 16, device_jpeg, decode and encode included; "
+             f"median of {rounds} alternating rounds [min .. max]"]
+
+    def mode(i, kw):
+        def run():
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            assert I.stylize_folder(G, str(src), str(tmp / f"f_{i}"), device=str(dev), img_size=S, batch=16, device_io=True, device_jpeg=True, **kw) == n
+            torch.cuda.synchronize()
+            return n / (time.perf_counter() - t0)
+        return run
+    paths = {name: mode(i, kw) for i, (name, kw) in enumerate(PROGRESSIVE_MODES)}
+    for fn in paths.values():
+        fn()
+    outs = [{p.name: p.read_bytes() for p in (tmp / f"f_{i}").rglob("*.jpg")} for i in range(len(PROGRESSIVE_MODES))]
+    assert len(outs[0]) == n and all(o == outs[0] for o in outs), "the modes wrote different files"
+    times = rotate(paths, rounds)
+    lines.append(f"# the decoder's counts since the start of the section: {G._jpeg_dec.stats}, progressive among them: {G._jpeg_dec.progressive_stats}")
+    for name, v in times.items():
+        lines.append(f"(f) {name:44s} {statistics.median(v):8.1f} images/s [{min(v):8.1f} .. {max(v):8.1f}]")
+    for th in ("serial", "pool, io_threads 4", "pool, io_threads 16"):
+        ref = times[("a  PIL " if th == "serial" else "b  PIL ") + th]
+        for name, v in times.items():
+            if name.startswith("f"):
+                verdict = "faster than" if min(v) > max(ref) else "slower than" if max(v) < min(ref) else "not apart from"
+                lines.append(f"(f) {name[3:]}: {verdict} PIL {th} beyond both spreads ([{min(v):.1f} .. {max(v):.1f}] vs [{min(ref):.1f} .. {max(ref):.1f}])")
+    for ln in lines:
+        print(ln, flush=True)
     return lines
 
 
@@ -173,9 +217,12 @@ def main():
     ap.add_argument("--only-decode", action="store_true", help="run section (d) alone")
     ap.add_argument("--png", action="store_true", help="also run section (e)")
     ap.add_argument("--only-png", action="store_true", help="run section (e) alone")
+    ap.add_argument("--progressive", action="store_true", help="also run section (f)")
+    ap.add_argument("--only-progressive", action="store_true", help="run section (f) alone")
     a = ap.parse_args()
     a.decode = a.decode or a.only_decode
     a.png = a.png or a.only_png
+    a.progressive = a.progressive or a.only_progressive
     assert torch.cuda.is_available(), "bench_stylize.py measures on the GPU"
     dev, S = torch.device("cuda:0"), a.size
     C.set_seed(0)
@@ -185,9 +232,9 @@ def main():
     G.compute_dtype = BF16
     lines = [f"# tools/bench_stylize.py --size {S} --batches {a.batches} --calls {a.calls} --rounds {a.rounds} --photos {a.photos}"
              + (" --only-jpeg" if a.only_jpeg else " --jpeg" if a.jpeg else "") + (" --only-decode" if a.only_decode else " --decode" if a.decode else "")
-             + (" --only-png" if a.only_png else " --png" if a.png else ""),
+             + (" --only-png" if a.only_png else " --png" if a.png else "") + (" --only-progressive" if a.only_progressive else " --progressive" if a.progressive else ""),
              f"# generator ngf 64, 9 blocks, bf16 operands, eager launches; median of {a.rounds} alternating rounds [min .. max]"]
-    only = a.only_jpeg or a.only_decode or a.only_png
+    only = a.only_jpeg or a.only_decode or a.only_png or a.only_progressive
     if not only:
         lines.append(f"# (a) ms per call of {a.calls} consecutive calls, each ending in the download of the uint8 HWC batch to the host")
     old_out = lambda x: I.stylize(G, x).cpu().permute(0, 2, 3, 1).contiguous()
@@ -238,6 +285,8 @@ def main():
             lines += decode_section(G, dev, S, a.rounds, a.photos, tmp)
         if a.png:
             lines += decode_section(G, dev, S, a.rounds, a.photos, tmp, png=True)
+        if a.progressive:
+            lines += progressive_section(G, dev, S, a.rounds, tmp)
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
         with open(a.out, "w") as f:
