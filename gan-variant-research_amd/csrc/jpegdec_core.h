@@ -279,7 +279,7 @@ JD_FN void jd_pixel(const gan_jpegdec_image* im, const uint8_t* planes, int y, i
   rgb[2] = (uint8_t)jd_clamp8(Y + ((116130 * cb + 32768) >> 16));
 }
 
-// ---- the bodies of the kernels behind the coefficients, shared by jpegdec.hip and jpegprog.hip (both upload blocks begin with
+// ---- the bodies of the back-end kernels of jpegdec.hip, which both decoders launch (both upload blocks begin with
 // gan_jpegdec_image [n] and both workspaces lay out coefficients and planes alike).  Device only; the includer has common.h.
 #if defined(__HIPCC__)
 constexpr int JD_DHT_BYTES = 272;
@@ -343,5 +343,28 @@ __device__ __forceinline__ void jd_pixels_body(const uint8_t* __restrict__ blk, 
   jd_pixel(&im, reinterpret_cast<const uint8_t*>(ws + im.plane_off), y, x, rgb);
   uint8_t* o = out + im.out_off + (int64_t)g * 3;
   o[0] = rgb[0]; o[1] = rgb[1]; o[2] = rgb[2];
+}
+#else
+// ---- the host programs' walk behind the coefficients of one image: dequantise + jd_idct into the planes, then jd_pixel per pixel.
+// qt: the image's four quantisation tables; ws, out: the whole workspace and output.  Returns the GAN_JPEGDEC_ERR_* bits.
+static inline int jd_host_back(const gan_jpegdec_image* im, const uint16_t* qt, uint8_t* ws, uint8_t* out) {
+  const int16_t* coef = (const int16_t*)(ws + im->coef_off);
+  uint8_t* planes = ws + im->plane_off;
+  int err = 0;
+  for (int c = 0; c < im->ncomp; ++c) {
+    const JdComp cp = jd_comp(im, c);
+    const int nb = c == 0 ? im->mcux * im->mcuy * im->hmax * im->vmax : im->mcux * im->mcuy;
+    for (int r = 0; r < nb; ++r) {
+      int d[64];
+      for (int i = 0; i < 64; ++i) d[i] = coef[(int64_t)(cp.first + r) * 64 + i];
+      err |= jd_idct(d, qt + im->q_tab[c] * 64);
+      const int by = r / cp.bw, bx = r - by * cp.bw, stride = cp.bw * 8;
+      for (int y = 0; y < 8; ++y)
+        for (int x = 0; x < 8; ++x) planes[(int64_t)cp.first * 64 + (int64_t)(by * 8 + y) * stride + bx * 8 + x] = (uint8_t)d[8 * y + x];
+    }
+  }
+  for (int y = 0; y < im->H; ++y)
+    for (int x = 0; x < im->W; ++x) jd_pixel(im, planes, y, x, out + im->out_off + ((int64_t)y * im->W + x) * 3);
+  return err;
 }
 #endif

@@ -37,22 +37,7 @@ int main(int argc, char** argv) {
     const gan_jpegdec_image* im = imgs + b;
     int16_t* coef = (int16_t*)(ws + im->coef_off);
     for (int j = 0; j < im->seg_count; ++j) err[b] |= jd_decode_segment(im, segs + im->seg_first + j, j, blk, &tabs[4 * b], jd_zigzag, coef);
-    uint8_t* planes = ws + im->plane_off;
-    for (int c = 0; c < im->ncomp; ++c) {
-      const JdComp cp = jd_comp(im, c);
-      const int nb = c == 0 ? im->mcux * im->mcuy * im->hmax * im->vmax : im->mcux * im->mcuy;
-      const uint16_t* q = (const uint16_t*)(blk + o_qt) + (b * 4 + im->q_tab[c]) * 64;
-      for (int r = 0; r < nb; ++r) {
-        int d[64];
-        for (int i = 0; i < 64; ++i) d[i] = coef[(int64_t)(cp.first + r) * 64 + i];
-        err[b] |= jd_idct(d, q);
-        const int by = r / cp.bw, bx = r - by * cp.bw, stride = cp.bw * 8;
-        for (int y = 0; y < 8; ++y)
-          for (int x = 0; x < 8; ++x) planes[(int64_t)cp.first * 64 + (int64_t)(by * 8 + y) * stride + bx * 8 + x] = (uint8_t)d[8 * y + x];
-      }
-    }
-    for (int y = 0; y < im->H; ++y)
-      for (int x = 0; x < im->W; ++x) jd_pixel(im, planes, y, x, out + im->out_off + ((int64_t)y * im->W + x) * 3);
+    err[b] |= jd_host_back(im, (const uint16_t*)(blk + o_qt) + b * 4 * 64, ws, out);
   }
   f = fopen(argv[2], "wb");
   if (!f) { perror(argv[2]); return 2; }

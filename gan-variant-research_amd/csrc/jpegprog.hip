@@ -1,13 +1,16 @@
 // Progressive JPEG decoder on the device, pixel-identical to Image.open(p).convert("RGB") (libjpeg-turbo) for the files
-// dataio.parse_jpeg_progressive accepts.  The entropy stage is jpegprog_core.h; everything behind the coefficients is the baseline
-// decoder's code (the kernel bodies of jpegdec_core.h) over a block that begins with the same gan_jpegdec_image descriptors.
+// dataio.parse_jpeg_progressive accepts.  The entropy stage is jpegprog_core.h; everything behind the coefficients is the back end of
+// jpegdec.hip (jpegdec_back.h) over a block that begins with the same gan_jpegdec_image descriptors, so this file holds only what is
+// progressive: a progressive decode shows jpegdec_tables_kernel, jpegdec_idct_kernel and jpegdec_pixels_kernel in a trace, beside
+// jpegprog_entropy_kernel.
 //
 //   gan_jpegprog_tables  : one wave per DHT version -> decode tables; error words and coefficients zeroed by one memset
 //   gan_jpegprog_entropy : one 64-lane workgroup per image; a lane takes one (scan, restart segment); the scans' levels run one after
 //                          the other with a barrier between them, the independent scans of a level side by side
-//   gan_jpegprog_idct / gan_jpegprog_pixels : jd_idct_body / jd_pixels_body
+//   gan_jpegprog_idct / gan_jpegprog_pixels : the back end's launches
 #include "common.h"
 #include "jpegprog_core.h"
+#include "jpegdec_back.h"
 
 namespace {
 
@@ -16,12 +19,11 @@ constexpr int LDS_TABLES = 16;                     // table versions of a file h
 
 struct ProgLayout {
   int64_t off_pimg, off_scan, off_seg, off_dht, off_qt, off_data;      // upload block
-  int64_t off_err, off_coef, off_planes;                                // workspace; tables at 0
-  int max_blocks, max_pixels;
+  int64_t off_err, off_coef;                                            // workspace; tables at 0
+  JdBack back;
 };
 
 int64_t up16(int64_t v) { return (v + 15) / 16 * 16; }
-int64_t up256(int64_t v) { return (v + 255) / 256 * 256; }
 
 int block_offsets(int n, int nscan, int nseg, int nver, ProgLayout* L) {
   GAN_CHECK(n >= 1 && n <= 65535 && nscan >= 1 && nscan <= n * GAN_JPEGPROG_MAX_SCANS && nseg >= 1 && nseg <= (1 << 24) && nver >= 1 &&
@@ -34,18 +36,8 @@ int block_offsets(int n, int nscan, int nseg, int nver, ProgLayout* L) {
   L->off_dht = L->off_seg + (int64_t)nseg * sizeof(gan_jpegprog_segment);
   L->off_qt = up16(L->off_dht + (int64_t)nver * JD_DHT_BYTES);
   L->off_data = up16(L->off_qt + (int64_t)n * QT_BYTES);
-  L->off_err = up256((int64_t)nver * sizeof(JdTable));
-  L->off_coef = L->off_err + up256((int64_t)n * 4);
-  return 0;
-}
-
-int check_geometry(const gan_jpegdec_image& im, int i) {
-  GAN_CHECK(im.H >= 1 && im.H <= 65535 && im.W >= 1 && im.W <= 65535, "jpegprog: image %d: H=%d W=%d outside 1 .. 65535", i, im.H, im.W);
-  const bool gray = im.ncomp == 1 && im.hmax == 1 && im.vmax == 1;
-  const bool colour = im.ncomp == 3 && (im.hmax == 1 || im.hmax == 2) && (im.vmax == 1 || im.vmax == 2) && !(im.hmax == 1 && im.vmax == 2);
-  GAN_CHECK(gray || colour, "jpegprog: image %d: %d components with luma sampling %dx%d is outside the supported class", i, im.ncomp, im.hmax, im.vmax);
-  GAN_CHECK(im.mcux == (im.W + 8 * im.hmax - 1) / (8 * im.hmax) && im.mcuy == (im.H + 8 * im.vmax - 1) / (8 * im.vmax),
-            "jpegprog: image %d: %dx%d MCUs do not belong to H=%d W=%d", i, im.mcuy, im.mcux, im.H, im.W);
+  L->off_err = jd_up256((int64_t)nver * sizeof(JdTable));
+  L->off_coef = L->off_err + jd_up256((int64_t)n * 4);
   return 0;
 }
 
@@ -62,18 +54,8 @@ int check_block(const void* blk_dev, const void* blk_host, int64_t blk_bytes, in
   const gan_jpegprog_image* pi = (const gan_jpegprog_image*)(h + L->off_pimg);
   const gan_jpegprog_scan* sc = (const gan_jpegprog_scan*)(h + L->off_scan);
   const gan_jpegprog_segment* sg = (const gan_jpegprog_segment*)(h + L->off_seg);
-  int64_t coef_end = L->off_coef, max_blocks = 0, max_pixels = 0;
+  if (jd_check_images("jpegprog", im, n, ws_bytes, L->off_coef, &L->back)) return -1;
   for (int i = 0; i < n; ++i) {
-    if (check_geometry(im[i], i)) return -1;
-    for (int c = 0; c < 3; ++c)
-      GAN_CHECK(im[i].q_tab[c] >= 0 && im[i].q_tab[c] <= 3, "jpegprog: image %d: quantisation slot of component %d outside 0 .. 3", i, c);
-    const int64_t nb = jd_blocks(&im[i]);
-    GAN_CHECK(nb < (1 << 24), "jpegprog: image %d: %lld blocks: too large", i, (long long)nb);
-    GAN_CHECK(im[i].coef_off >= L->off_coef && im[i].coef_off % 16 == 0 && im[i].coef_off + nb * 128 <= ws_bytes,
-              "jpegprog: image %d: coefficient offset %lld leaves the workspace of %lld bytes", i, (long long)im[i].coef_off, (long long)ws_bytes);
-    coef_end = im[i].coef_off + nb * 128 > coef_end ? im[i].coef_off + nb * 128 : coef_end;
-    max_blocks = nb > max_blocks ? nb : max_blocks;
-    max_pixels = (int64_t)im[i].H * im[i].W > max_pixels ? (int64_t)im[i].H * im[i].W : max_pixels;
     const gan_jpegprog_image& p = pi[i];
     GAN_CHECK(p.scan_count >= 1 && p.scan_count <= GAN_JPEGPROG_MAX_SCANS && p.scan_first >= 0 && (int64_t)p.scan_first + p.scan_count <= nscan,
               "jpegprog: image %d: scans %d .. +%d outside the table of %d, or more than %d scans", i, p.scan_first, p.scan_count, nscan, GAN_JPEGPROG_MAX_SCANS);
@@ -128,21 +110,7 @@ int check_block(const void* blk_dev, const void* blk_host, int64_t blk_bytes, in
       GAN_CHECK(next_unit[s] == jp_units(&im[i], sc[p.scan_first + s].comp), "jpegprog: scan %d of image %d: its segments cover %d of its %d units", s, i, next_unit[s],
                 jp_units(&im[i], sc[p.scan_first + s].comp));
   }
-  L->off_planes = coef_end;
-  for (int i = 0; i < n; ++i) {                    // the planes lie behind every coefficient area (tables zeroes that span with one memset)
-    const int64_t nb = jd_blocks(&im[i]);
-    GAN_CHECK(im[i].plane_off >= coef_end && im[i].plane_off % 16 == 0 && im[i].plane_off + nb * 64 <= ws_bytes,
-              "jpegprog: image %d: plane offset %lld leaves the workspace of %lld bytes", i, (long long)im[i].plane_off, (long long)ws_bytes);
-  }
-  L->max_blocks = (int)max_blocks;
-  GAN_CHECK(max_pixels < (1ll << 32), "jpegprog: image too large");
-  L->max_pixels = (int)((max_pixels + 255) / 256);   // in workgroups of 256
   return 0;
-}
-
-__global__ __launch_bounds__(64) void jpegprog_tables_kernel(const uint8_t* __restrict__ dht, JdTable* __restrict__ tabs) {
-  __shared__ JdTable t;
-  jd_tables_body(dht, tabs, &t);
 }
 
 __global__ __launch_bounds__(64) void jpegprog_entropy_kernel(const uint8_t* __restrict__ blk, int64_t off_pimg, int64_t off_scan, int64_t off_seg,
@@ -189,15 +157,6 @@ __global__ __launch_bounds__(64) void jpegprog_entropy_kernel(const uint8_t* __r
   if (err) atomicOr(&errw[b], err);
 }
 
-__global__ __launch_bounds__(256) void jpegprog_idct_kernel(const uint8_t* __restrict__ blk, int64_t off_qt, char* __restrict__ ws, int32_t* __restrict__ errw) {
-  jd_idct_body(blk, off_qt, ws, errw);
-}
-
-__global__ __launch_bounds__(256) void jpegprog_pixels_kernel(const uint8_t* __restrict__ blk, const char* __restrict__ ws, uint8_t* __restrict__ out,
-                                                              const int32_t* __restrict__ errw, int32_t* __restrict__ err) {
-  jd_pixels_body(blk, ws, out, errw, err);
-}
-
 }  // namespace
 
 extern "C" int gan_jpegprog_block_offsets(int n, int nscan, int nseg, int nver, int64_t* off) {
@@ -211,19 +170,7 @@ extern "C" int gan_jpegprog_block_offsets(int n, int nscan, int nseg, int nver, 
 extern "C" int gan_jpegprog_bounds(gan_jpegdec_image* imgs, int n, int nver, int64_t* ws_bytes) {
   ProgLayout L;
   if (block_offsets(n, 1, 1, nver, &L)) return -1;
-  GAN_CHECK(imgs && ws_bytes, "jpegprog_bounds: null pointer");
-  int64_t o = L.off_coef;
-  for (int i = 0; i < n; ++i) {
-    if (check_geometry(imgs[i], i)) return -1;
-    imgs[i].coef_off = o;
-    o += up256((int64_t)jd_blocks(&imgs[i]) * 128);
-  }
-  for (int i = 0; i < n; ++i) {
-    imgs[i].plane_off = o;
-    o += up256(jd_plane_bytes(&imgs[i]));
-  }
-  *ws_bytes = o;
-  return 0;
+  return jd_place("jpegprog", imgs, n, L.off_coef, ws_bytes);
 }
 
 #define PROG_ARGS const void *blk_dev, const void *blk_host, int64_t blk_bytes, int n, int nscan, int nseg, int nver, void *ws, int64_t ws_bytes
@@ -233,11 +180,7 @@ extern "C" int gan_jpegprog_bounds(gan_jpegdec_image* imgs, int n, int nver, int
 
 extern "C" int gan_jpegprog_tables(PROG_ARGS, void* stream) {
   PROG_CHECK();
-  hipStream_t s = (hipStream_t)stream;
-  if (hipMemsetAsync((char*)ws + L.off_err, 0, (size_t)(L.off_planes - L.off_err), s) != hipSuccess) return gan_set_error(-2, "jpegprog_tables: hipMemsetAsync failed");
-  hipLaunchKernelGGL(jpegprog_tables_kernel, dim3(nver), dim3(64), 0, s, (const uint8_t*)blk_dev + L.off_dht, (JdTable*)ws);
-  GAN_LAUNCH_CHECK();
-  return 0;
+  return jd_launch_tables("jpegprog", (const uint8_t*)blk_dev + L.off_dht, nver, ws, L.off_err, L.back.off_planes, stream);
 }
 
 extern "C" int gan_jpegprog_entropy(PROG_ARGS, void* stream) {
@@ -250,21 +193,10 @@ extern "C" int gan_jpegprog_entropy(PROG_ARGS, void* stream) {
 
 extern "C" int gan_jpegprog_idct(PROG_ARGS, void* stream) {
   PROG_CHECK();
-  hipLaunchKernelGGL(jpegprog_idct_kernel, dim3((L.max_blocks + 255) / 256, n), dim3(256), 0, (hipStream_t)stream, (const uint8_t*)blk_dev, L.off_qt, (char*)ws,
-                     (int32_t*)((char*)ws + L.off_err));
-  GAN_LAUNCH_CHECK();
-  return 0;
+  return jd_launch_idct(blk_dev, n, L.off_qt, ws, L.off_err, L.back.max_blocks, stream);
 }
 
 extern "C" int gan_jpegprog_pixels(PROG_ARGS, uint8_t* out, int64_t out_bytes, int32_t* err, void* stream) {
   PROG_CHECK();
-  GAN_CHECK(out, "jpegprog_pixels: null pointer");
-  const gan_jpegdec_image* im = (const gan_jpegdec_image*)blk_host;
-  for (int i = 0; i < n; ++i)
-    GAN_CHECK(im[i].out_off >= 0 && im[i].out_off + (int64_t)im[i].H * im[i].W * 3 <= out_bytes, "jpegprog_pixels: image %d: output offset %lld leaves the output of %lld bytes",
-              i, (long long)im[i].out_off, (long long)out_bytes);
-  hipLaunchKernelGGL(jpegprog_pixels_kernel, dim3(L.max_pixels, n), dim3(256), 0, (hipStream_t)stream, (const uint8_t*)blk_dev, (const char*)ws, out,
-                     (const int32_t*)((const char*)ws + L.off_err), err);
-  GAN_LAUNCH_CHECK();
-  return 0;
+  return jd_launch_pixels("jpegprog", blk_dev, (const gan_jpegdec_image*)blk_host, n, ws, L.off_err, L.back.max_pixels, out, out_bytes, err, stream);
 }

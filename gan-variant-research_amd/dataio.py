@@ -285,105 +285,31 @@ _JPEG_ZIGZAG = (0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 
                 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63)
 
 
-def parse_jpeg(data: bytes) -> Optional[Dict]:
-    """The plan of a file the device decoder takes, or None ("not mine": Pillow decodes it).  Accepted: SOF0, 8-bit samples, 8-bit
-    quantisation tables, one interleaved scan of all components with Ss = 0, Se = 63, Ah = Al = 0; one component sampled 1x1, or
-    components 1, 2, 3 with chroma 1x1 and luma 1x1, 2x1 or 2x2; no Adobe APP14; DHT counts that sum to at most 256 and do not
-    over-subscribe the code space; an EOI after the scan, with nothing but RSTn markers and stuffed 0xFF bytes before it, and as many
-    RSTn as the restart interval asks.  Anything else -- progressive, arithmetic, 12-bit, CMYK, 4:1:1 / 4:4:0, several scans, DNL, fill
-    bytes, an unknown marker, a truncated file, another format -- is None."""
+# What the two JPEG parsers share.  Each helper returns None for what the device does not take, and the parser returns None with it.
+def _jpeg_segment(data: bytes, pos: int):
+    """(marker, L, body) of the marker segment at `pos`; EOI, which has no length, is (0xD9, 0, b"")."""
     n = len(data)
-    if n < 4 or data[0] != 0xFF or data[1] != 0xD8:
+    if pos + 2 > n or data[pos] != 0xFF:
         return None
-    pos, qt, dht, sof, ri = 2, {}, {}, None, 0
-    while True:
-        if pos + 4 > n or data[pos] != 0xFF:
-            return None
-        m = data[pos + 1]
-        L = (data[pos + 2] << 8) | data[pos + 3]
-        if L < 2 or pos + 2 + L > n:
-            return None
-        body = data[pos + 4:pos + 2 + L]
-        if m == 0xDB:
-            while body:
-                if body[0] >> 4 != 0 or (body[0] & 15) > 3 or len(body) < 65:
-                    return None
-                q = np.zeros(64, np.uint16)
-                q[list(_JPEG_ZIGZAG)] = np.frombuffer(body[1:65], np.uint8)
-                qt[body[0] & 15] = q
-                body = body[65:]
-        elif m == 0xC4:
-            while body:
-                if len(body) < 17 or body[0] >> 4 > 1 or (body[0] & 15) > 1:
-                    return None
-                counts = body[1:17]
-                total, code = sum(counts), 0
-                for l in range(16):
-                    code += counts[l]
-                    if code > (1 << (l + 1)):
-                        return None
-                    code <<= 1
-                if total > 256 or len(body) < 17 + total:
-                    return None
-                dht[(body[0] >> 4) * 2 + (body[0] & 15)] = body[1:17 + total]
-                body = body[17 + total:]
-        elif m == 0xC0:
-            if sof is not None or len(body) < 6 or body[0] != 8 or len(body) != 6 + 3 * body[5]:
-                return None
-            sof = ((body[1] << 8) | body[2], (body[3] << 8) | body[4], [(body[6 + 3 * c], body[7 + 3 * c] >> 4, body[7 + 3 * c] & 15, body[8 + 3 * c]) for c in range(body[5])])
-        elif m == 0xDD:
-            if L != 4:
-                return None
-            ri = (body[0] << 8) | body[1]
-        elif m == 0xEE:
-            if body[:5] == b"Adobe":
-                return None
-        elif m == 0xDA:
-            break
-        elif not (0xE0 <= m <= 0xEF or m == 0xFE):
-            return None
-        pos += 2 + L
-    if sof is None:
+    if data[pos + 1] == 0xD9:
+        return 0xD9, 0, b""
+    if pos + 4 > n:
         return None
-    H, W, comps = sof
-    if H < 1 or W < 1 or len(comps) not in (1, 3) or len(body) != 4 + 2 * len(comps) or body[0] != len(comps):
-        return None
-    if tuple(body[-3:]) != (0, 63, 0):
-        return None
-    if len(comps) == 1:
-        if comps[0][1:3] != (1, 1):
+    L = (data[pos + 2] << 8) | data[pos + 3]
+    return None if L < 2 or pos + 2 + L > n else (data[pos + 1], L, data[pos + 4:pos + 2 + L])
+
+
+def _dqt_tables(body) -> Optional[Dict]:
+    """{slot: uint16 [64] in natural order} of a DQT body: 8-bit tables in slots 0 .. 3."""
+    qt = {}
+    while body:
+        if body[0] >> 4 != 0 or (body[0] & 15) > 3 or len(body) < 65:
             return None
-        hmax = vmax = 1
-    else:
-        if tuple(c[0] for c in comps) != (1, 2, 3) or comps[1][1:3] != (1, 1) or comps[2][1:3] != (1, 1) or comps[0][1:3] not in ((1, 1), (2, 1), (2, 2)):
-            return None
-        hmax, vmax = comps[0][1:3]
-    dc_tab, ac_tab, q_tab = [0, 0, 0], [2, 2, 2], [0, 0, 0]
-    for c, (cid, _, _, tq) in enumerate(comps):
-        sel, tabs = body[1 + 2 * c], body[2 + 2 * c]
-        td, ta = tabs >> 4, tabs & 15
-        if sel != cid or td > 1 or ta > 1 or td not in dht or 2 + ta not in dht or tq not in qt:
-            return None
-        dc_tab[c], ac_tab[c], q_tab[c] = td, 2 + ta, tq
-    sb = pos + 2 + L
-    arr = np.frombuffer(data, np.uint8)
-    ff = np.flatnonzero(arr[sb:n - 1] == 0xFF) + sb          # one vectorised search: stuffed bytes, RSTn and the end of the scan
-    nxt = arr[ff + 1]
-    mpos, mk = ff[nxt != 0], nxt[nxt != 0]
-    other = np.flatnonzero((mk & 0xF8) != 0xD0)
-    if other.size == 0 or mk[other[0]] != 0xD9:
-        return None
-    e = int(other[0])
-    rst, end = mpos[:e], int(mpos[e])
-    mcux, mcuy = -(-W // (8 * hmax)), -(-H // (8 * vmax))
-    per = ri if ri else mcux * mcuy
-    nseg = -(-mcux * mcuy // per)
-    if rst.size != nseg - 1:
-        return None
-    begins = np.concatenate([[sb], rst + 2]).astype(np.int64)
-    ends = np.concatenate([rst, [end]]).astype(np.int64)
-    return {"H": H, "W": W, "ncomp": len(comps), "hmax": hmax, "vmax": vmax, "mcux": mcux, "mcuy": mcuy, "qt": qt, "dht": dht,
-            "dc_tab": dc_tab, "ac_tab": ac_tab, "q_tab": q_tab, "scan": (sb, end), "seg_begin": begins, "seg_end": ends, "per": per, "data": data}
+        q = np.zeros(64, np.uint16)
+        q[list(_JPEG_ZIGZAG)] = np.frombuffer(body[1:65], np.uint8)
+        qt[body[0] & 15] = q
+        body = body[65:]
+    return qt
 
 
 def _huffman_counts_legal(body) -> Optional[int]:
@@ -396,6 +322,137 @@ def _huffman_counts_legal(body) -> Optional[int]:
             return None
         code <<= 1
     return None if total > 256 or len(body) < 17 + total else total
+
+
+def _dht_tables(body, max_id: int) -> Optional[List]:
+    """[(class, id, counts and symbols)] of a DHT body, in its order; ids above `max_id` (baseline: 1, progressive: 3) are refused."""
+    tables = []
+    while body:
+        if len(body) < 17 or body[0] >> 4 > 1 or (body[0] & 15) > max_id:
+            return None
+        total = _huffman_counts_legal(body)
+        if total is None:
+            return None
+        tables.append((body[0] >> 4, body[0] & 15, body[1:17 + total]))
+        body = body[17 + total:]
+    return tables
+
+
+def _sof_frame(body):
+    """(H, W, [(id, h, v, quantisation slot)]) of a frame header with 8-bit samples."""
+    if len(body) < 6 or body[0] != 8 or len(body) != 6 + 3 * body[5]:
+        return None
+    return (body[1] << 8) | body[2], (body[3] << 8) | body[4], [(body[6 + 3 * c], body[7 + 3 * c] >> 4, body[7 + 3 * c] & 15, body[8 + 3 * c]) for c in range(body[5])]
+
+
+def _luma_sampling(comps) -> Optional[Tuple[int, int]]:
+    """(hmax, vmax) of the component classes the device takes: one component sampled 1x1, or components 1, 2, 3 with chroma 1x1 and luma
+    1x1, 2x1 or 2x2."""
+    if len(comps) == 1:
+        return (1, 1) if comps[0][1:3] == (1, 1) else None
+    if len(comps) != 3 or tuple(c[0] for c in comps) != (1, 2, 3) or comps[1][1:3] != (1, 1) or comps[2][1:3] != (1, 1) or comps[0][1:3] not in ((1, 1), (2, 1), (2, 2)):
+        return None
+    return comps[0][1:3]
+
+
+def _other_segment(m: int, body, ri: int) -> Optional[int]:
+    """The restart interval behind a segment that is neither tables, frame nor scan: DRI sets it, APPn and COM pass; None: a DRI of another
+    length, an Adobe APP14, any other marker."""
+    if m == 0xDD:
+        return (body[0] << 8) | body[1] if len(body) == 2 else None
+    if m == 0xEE and body[:5] == b"Adobe":
+        return None
+    return ri if 0xE0 <= m <= 0xEF or m == 0xFE else None
+
+
+def _markers(arr: np.ndarray, start: int):
+    """(positions, codes) of the markers in arr[start:], stuffed 0xFF 0x00 bytes left out, in one vectorised search."""
+    ff = np.flatnonzero(arr[start:len(arr) - 1] == 0xFF) + start
+    nxt = arr[ff + 1]
+    return ff[nxt != 0], nxt[nxt != 0]
+
+
+def _scan_end(mpos, mk, sb: int):
+    """(positions of the RSTn markers of the scan that begins at sb, position of the first other marker behind it)."""
+    i0 = int(np.searchsorted(mpos, sb))
+    other = np.flatnonzero((mk[i0:] & 0xF8) != 0xD0)
+    if other.size == 0:
+        return None
+    e = i0 + int(other[0])
+    return mpos[i0:e], int(mpos[e])
+
+
+def _segments(sb: int, rst, end: int):
+    """(seg_begin, seg_end) of a scan's restart segments: the entropy-coded bytes between its RSTn markers."""
+    return np.concatenate([[sb], rst + 2]).astype(np.int64), np.concatenate([rst, [end]]).astype(np.int64)
+
+
+def parse_jpeg(data: bytes) -> Optional[Dict]:
+    """The plan of a file the device decoder takes, or None ("not mine": Pillow decodes it).  Accepted: SOF0, 8-bit samples, 8-bit
+    quantisation tables, one interleaved scan of all components with Ss = 0, Se = 63, Ah = Al = 0; one component sampled 1x1, or
+    components 1, 2, 3 with chroma 1x1 and luma 1x1, 2x1 or 2x2; no Adobe APP14; DHT counts that sum to at most 256 and do not
+    over-subscribe the code space; an EOI after the scan, with nothing but RSTn markers and stuffed 0xFF bytes before it, and as many
+    RSTn as the restart interval asks.  Anything else -- progressive, arithmetic, 12-bit, CMYK, 4:1:1 / 4:4:0, several scans, DNL, fill
+    bytes, an unknown marker, a truncated file, another format -- is None."""
+    n = len(data)
+    if n < 4 or data[0] != 0xFF or data[1] != 0xD8:
+        return None
+    pos, qt, dht, sof, ri = 2, {}, {}, None, 0
+    while True:
+        seg = _jpeg_segment(data, pos)
+        if seg is None:
+            return None
+        m, L, body = seg
+        if m == 0xDB:
+            tables = _dqt_tables(body)
+            if tables is None:
+                return None
+            qt.update(tables)
+        elif m == 0xC4:
+            tables = _dht_tables(body, 1)
+            if tables is None:
+                return None
+            dht.update({2 * tc + th: raw for tc, th, raw in tables})
+        elif m == 0xC0:
+            sof = _sof_frame(body) if sof is None else None      # a second frame header is refused
+            if sof is None:
+                return None
+        elif m == 0xDA:
+            break
+        else:
+            ri = _other_segment(m, body, ri)
+            if ri is None:
+                return None
+        pos += 2 + L
+    if sof is None:
+        return None
+    H, W, comps = sof
+    sampling = _luma_sampling(comps)
+    if H < 1 or W < 1 or sampling is None or len(body) != 4 + 2 * len(comps) or body[0] != len(comps):
+        return None
+    if tuple(body[-3:]) != (0, 63, 0):
+        return None
+    hmax, vmax = sampling
+    dc_tab, ac_tab, q_tab = [0, 0, 0], [2, 2, 2], [0, 0, 0]
+    for c, (cid, _, _, tq) in enumerate(comps):
+        sel, tabs = body[1 + 2 * c], body[2 + 2 * c]
+        td, ta = tabs >> 4, tabs & 15
+        if sel != cid or td > 1 or ta > 1 or td not in dht or 2 + ta not in dht or tq not in qt:
+            return None
+        dc_tab[c], ac_tab[c], q_tab[c] = td, 2 + ta, tq
+    sb = pos + 2 + L
+    found = _scan_end(*_markers(np.frombuffer(data, np.uint8), sb), sb)      # stuffed bytes, RSTn and the end of the scan
+    if found is None or data[found[1] + 1] != 0xD9:
+        return None
+    rst, end = found
+    mcux, mcuy = -(-W // (8 * hmax)), -(-H // (8 * vmax))
+    per = ri if ri else mcux * mcuy
+    nseg = -(-mcux * mcuy // per)
+    if rst.size != nseg - 1:
+        return None
+    begins, ends = _segments(sb, rst, end)
+    return {"format": "jpeg", "H": H, "W": W, "ncomp": len(comps), "hmax": hmax, "vmax": vmax, "mcux": mcux, "mcuy": mcuy, "qt": qt, "dht": dht,
+            "dc_tab": dc_tab, "ac_tab": ac_tab, "q_tab": q_tab, "scan": (sb, end), "seg_begin": begins, "seg_end": ends, "per": per, "data": data}
 
 
 PROG_MAX_SCANS = PROG_MAX_TABLES = 64           # GAN_JPEGPROG_MAX_SCANS, GAN_JPEGPROG_MAX_TABLES
@@ -422,61 +479,35 @@ def parse_jpeg_progressive(data: bytes) -> Optional[Dict]:
     mpos = mk = None
     state = touch = None                       # per (component, coefficient): the Al reached (-1: untouched), the last scan that touched it
     while True:
-        if pos + 2 > n or data[pos] != 0xFF:
+        seg = _jpeg_segment(data, pos)
+        if seg is None:
             return None
-        m = data[pos + 1]
+        m, L, body = seg
         if m == 0xD9:
             break
-        if pos + 4 > n:
-            return None
-        L = (data[pos + 2] << 8) | data[pos + 3]
-        if L < 2 or pos + 2 + L > n:
-            return None
-        body = data[pos + 4:pos + 2 + L]
         if m == 0xDB:
-            if scans:
+            tables = None if scans else _dqt_tables(body)      # only before the first scan
+            if tables is None:
                 return None
-            while body:
-                if body[0] >> 4 != 0 or (body[0] & 15) > 3 or len(body) < 65:
-                    return None
-                q = np.zeros(64, np.uint16)
-                q[list(_JPEG_ZIGZAG)] = np.frombuffer(body[1:65], np.uint8)
-                qt[body[0] & 15] = q
-                body = body[65:]
+            qt.update(tables)
         elif m == 0xC4:
-            while body:
-                if len(body) < 17 or body[0] >> 4 > 1 or (body[0] & 15) > 3:
-                    return None
-                total = _huffman_counts_legal(body)
-                if total is None or len(versions) == PROG_MAX_TABLES:
-                    return None
-                slots[(body[0] >> 4, body[0] & 15)] = len(versions)
-                versions.append(body[1:17 + total])
-                body = body[17 + total:]
+            tables = _dht_tables(body, 3)
+            if tables is None or len(versions) + len(tables) > PROG_MAX_TABLES:
+                return None
+            for tc, th, raw in tables:                         # a slot defined again is a new version; a scan names versions
+                slots[(tc, th)] = len(versions)
+                versions.append(raw)
         elif m == 0xC2:
-            if sof is not None or len(body) < 6 or body[0] != 8 or len(body) != 6 + 3 * body[5]:
+            sof = _sof_frame(body) if sof is None else None      # a second frame header is refused
+            if sof is None:
                 return None
-            sof = ((body[1] << 8) | body[2], (body[3] << 8) | body[4], [(body[6 + 3 * c], body[7 + 3 * c] >> 4, body[7 + 3 * c] & 15, body[8 + 3 * c]) for c in range(body[5])])
             H, W, comps = sof
-            if H < 1 or W < 1 or len(comps) not in (1, 3):
+            sampling = _luma_sampling(comps)
+            if H < 1 or W < 1 or sampling is None:
                 return None
-            if len(comps) == 1:
-                if comps[0][1:3] != (1, 1):
-                    return None
-                hmax = vmax = 1
-            else:
-                if tuple(c[0] for c in comps) != (1, 2, 3) or comps[1][1:3] != (1, 1) or comps[2][1:3] != (1, 1) or comps[0][1:3] not in ((1, 1), (2, 1), (2, 2)):
-                    return None
-                hmax, vmax = comps[0][1:3]
+            hmax, vmax = sampling
             mcux, mcuy = -(-W // (8 * hmax)), -(-H // (8 * vmax))
             state, touch = np.full((len(comps), 64), -1, np.int64), np.full((len(comps), 64), -1, np.int64)
-        elif m == 0xDD:
-            if L != 4:
-                return None
-            ri = (body[0] << 8) | body[1]
-        elif m == 0xEE:
-            if body[:5] == b"Adobe":
-                return None
         elif m == 0xDA:
             if sof is None or len(scans) == PROG_MAX_SCANS or not body or len(body) != 4 + 2 * body[0]:
                 return None
@@ -515,15 +546,11 @@ def parse_jpeg_progressive(data: bytes) -> Optional[Dict]:
             state[members, Ss:Se + 1], touch[members, Ss:Se + 1] = Al, len(scans)
             sb = pos + 2 + L
             if mpos is None:                           # one vectorised search for every scan: stuffed bytes, RSTn and the markers behind the scans
-                ff = np.flatnonzero(arr[:n - 1] == 0xFF)
-                nxt = arr[ff + 1]
-                mpos, mk = ff[nxt != 0], nxt[nxt != 0]
-            i0 = int(np.searchsorted(mpos, sb))
-            other = np.flatnonzero((mk[i0:] & 0xF8) != 0xD0)
-            if other.size == 0:
+                mpos, mk = _markers(arr, sb)
+            found = _scan_end(mpos, mk, sb)
+            if found is None:
                 return None
-            e = i0 + int(other[0])
-            rst, end = mpos[i0:e], int(mpos[e])
+            rst, end = found
             if comp < 0:
                 units = mcux * mcuy
             else:
@@ -532,12 +559,15 @@ def parse_jpeg_progressive(data: bytes) -> Optional[Dict]:
             per = ri if ri else units
             if rst.size != -(-units // per) - 1:
                 return None
+            begins, ends = _segments(sb, rst, end)
             scans.append({"comp": comp, "Ss": Ss, "Se": Se, "Ah": Ah, "Al": Al, "tab": tab, "dep": dep, "level": level, "per": per, "units": units,
-                          "seg_begin": np.concatenate([[sb], rst + 2]).astype(np.int64), "seg_end": np.concatenate([rst, [end]]).astype(np.int64)})
+                          "seg_begin": begins, "seg_end": ends})
             pos = end
             continue
-        elif not (0xE0 <= m <= 0xEF or m == 0xFE):
-            return None
+        else:
+            ri = _other_segment(m, body, ri)
+            if ri is None:
+                return None
         pos += 2 + L
     if not scans or (state != 0).any():
         return None
@@ -593,16 +623,30 @@ class _DecoderBase:
         data = bytes(source) if isinstance(source, (bytes, bytearray, memoryview)) else open(os.fspath(source), "rb").read()
         return data, self.parse(data)
 
+    def _routes(self) -> Dict:
+        """{plan format: (the decoder that launches such plans, then every other decoder whose `stats` count them too)}, in launch order.
+        A decoder that launches its own plans takes every plan it is given."""
+        return {None: (self,)}
+
+    @staticmethod
+    def _is_mine(data: bytes) -> bool:
+        """Whether a source this decoder's parser refused is of its format (a member decoder counts those as `unsupported`)."""
+        raise NotImplementedError
+
     def _groups(self, plans):
         """[(decoder, indices of the sources it takes)]."""
-        return [(self, [i for i, p in enumerate(plans) if p is not None])]
+        return [(ds[0], [i for i, p in enumerate(plans) if p is not None and (fmt is None or p["format"] == fmt)]) for fmt, ds in self._routes().items()]
 
     def _count(self, groups, loaded, rest):
+        counted = {ds[0]: ds for ds in self._routes().values()}
         for d, idx in groups:
             bad = sum(1 for i in idx if i in d.last_errors)
-            d.stats["device"] += len(idx) - bad
-            d.stats["flagged"] += bad
-        self.stats["unsupported"] += len(rest)
+            for c in counted[d]:
+                c.stats["device"] += len(idx) - bad
+                c.stats["flagged"] += bad
+        self.stats["unsupported"] += len(rest)                   # every source that went to Pillow unparsed; a member counts its own format's
+        for d in {c for ds in counted.values() for c in ds} - {self}:
+            d.stats["unsupported"] += sum(1 for i in rest if d._is_mine(loaded[i][0]))
 
     def _upload(self, total: int):
         """The staging buffer's first `total` bytes on the device (the buffer itself on a CPU device)."""
@@ -670,6 +714,28 @@ class _DecoderBase:
         return [out[o:o + h * w * 3].view(h, w, 3) for o, (h, w) in zip(offsets, shapes)]
 
 
+def _pack_jpeg_images(dec: _DecoderBase, plans: Sequence[Dict], out_offsets: Sequence[int], spans: Sequence[Tuple[int, int]], o_qt: int, o_data: int):
+    """What the upload blocks of both JPEG decoders hold alike, into `dec`'s staging buffer: per image the geometry, quantisation slots and
+    out_off of its GanJpegdecImage, its quantisation tables from o_qt on, and bytes spans[i] = (first, end) of its file from o_data on, every
+    image's at a multiple of 16.  -> (block bytes, the staging buffer, the descriptors, per image: block offset - file offset of its bytes)."""
+    imgs = (_lib.GanJpegdecImage * len(plans))()
+    total = o_data + sum(-(-(se - sb) // 16) * 16 for sb, se in spans)
+    host = dec._grow("_host", total, host=True).numpy()
+    host[o_qt:o_data] = 0
+    at, shifts = o_data, []
+    for i, (p, im, (sb, se)) in enumerate(zip(plans, imgs, spans)):
+        im.ncomp, im.H, im.W, im.hmax, im.vmax, im.mcux, im.mcuy = p["ncomp"], p["H"], p["W"], p["hmax"], p["vmax"], p["mcux"], p["mcuy"]
+        for c in range(3):
+            im.q_tab[c] = p["q_tab"][c]
+        im.out_off = int(out_offsets[i])
+        for t, q in p["qt"].items():
+            host[o_qt + (4 * i + t) * 128:o_qt + (4 * i + t + 1) * 128].view(np.uint16)[:] = q
+        host[at:at + se - sb] = np.frombuffer(p["data"], np.uint8, se - sb, sb)
+        shifts.append(at - sb)
+        at += -(-(se - sb) // 16) * 16
+    return total, host, imgs, shifts
+
+
 class JpegDecoder(_DecoderBase):
     """Baseline JPEG files -> packed uint8 (H, W, 3) tensors on `device`, pixel-identical to `_decode` (Pillow) for every source.  The
     files `parse` accepts are decoded by csrc/jpegdec.hip: their descriptors, tables and scan bytes go up in one copy from one pinned
@@ -696,57 +762,35 @@ class JpegDecoder(_DecoderBase):
             plan = parse_jpeg_progressive(data)
         return data, plan
 
-    def _groups(self, plans):
-        if self._prog is None:
-            return super()._groups(plans)
-        is_prog = lambda p: p.get("format") == "jpegprog"
-        return [(self, [i for i, p in enumerate(plans) if p is not None and not is_prog(p)]),
-                (self._prog, [i for i, p in enumerate(plans) if p is not None and is_prog(p)])]
+    def _routes(self):
+        """The progressive group's counts go into this decoder's `stats` too; the refused SOF2 files into `progressive_stats`."""
+        return super()._routes() if self._prog is None else {"jpeg": (self,), "jpegprog": (self._prog, self)}
 
-    def _count(self, groups, loaded, rest):
-        super()._count(groups, loaded, rest)
-        self._count_progressive(groups, loaded, rest)
-
-    def _count_progressive(self, groups, loaded, rest):
-        """The progressive group's counts into this decoder's `stats`; the refused SOF2 files into `progressive_stats`."""
-        if self._prog is None:
-            return
-        for d, idx in groups:
-            if d is self._prog:
-                bad = sum(1 for i in idx if i in d.last_errors)
-                self.stats["device"] += len(idx) - bad
-                self.stats["flagged"] += bad
-        self._prog.stats["unsupported"] += sum(1 for i in rest if _is_progressive(loaded[i][0]))
+    @staticmethod
+    def _is_mine(data: bytes) -> bool:
+        return data[:2] == b"\xff\xd8"
 
     def _pack(self, plans: Sequence[Dict], out_offsets: Sequence[int]):
         """The upload block of `plans` in the staging buffer -> (block bytes, images, segments, workspace bytes)."""
         n = len(plans)
-        imgs = (_lib.GanJpegdecImage * n)()
         nseg = sum(len(p["seg_begin"]) for p in plans)
         o_seg, o_dht, o_qt, o_scan = self.ops.jpegdec_block_offsets(n, nseg)
-        total = o_scan + sum(-(-(p["scan"][1] - p["scan"][0]) // 16) * 16 for p in plans)
+        total, host, imgs, shifts = _pack_jpeg_images(self, plans, out_offsets, [p["scan"] for p in plans], o_qt, o_scan)
+        host[o_dht:o_qt] = 0
         segs = np.zeros((nseg, 5), np.int32)
-        host = self._grow("_host", total, host=True).numpy()
-        host[o_dht:o_scan] = 0
-        s0, at = 0, o_scan
-        for i, (p, im) in enumerate(zip(plans, imgs)):
+        s0 = 0
+        for i, (p, im, shift) in enumerate(zip(plans, imgs, shifts)):
             k = len(p["seg_begin"])
-            im.ncomp, im.H, im.W, im.hmax, im.vmax, im.mcux, im.mcuy, im.seg_first, im.seg_count = p["ncomp"], p["H"], p["W"], p["hmax"], p["vmax"], p["mcux"], p["mcuy"], s0, k
+            im.seg_first, im.seg_count = s0, k
             for c in range(3):
-                im.dc_tab[c], im.ac_tab[c], im.q_tab[c] = p["dc_tab"][c], p["ac_tab"][c], p["q_tab"][c]
-            im.out_off = int(out_offsets[i])
-            sb, se = p["scan"]
-            shift = at - sb
+                im.dc_tab[c], im.ac_tab[c] = p["dc_tab"][c], p["ac_tab"][c]
             segs[s0:s0 + k, 0] = i
             segs[s0:s0 + k, 1] = np.arange(k) * p["per"]
             segs[s0:s0 + k, 2] = np.minimum(p["per"], p["mcux"] * p["mcuy"] - segs[s0:s0 + k, 1])
             segs[s0:s0 + k, 3], segs[s0:s0 + k, 4] = p["seg_begin"] + shift, p["seg_end"] + shift
-            host[at:at + se - sb] = np.frombuffer(p["data"], np.uint8, se - sb, sb)
             for t, raw in p["dht"].items():
                 host[o_dht + (4 * i + t) * 272:o_dht + (4 * i + t) * 272 + len(raw)] = np.frombuffer(raw, np.uint8)
-            for t, q in p["qt"].items():
-                host[o_qt + (4 * i + t) * 128:o_qt + (4 * i + t + 1) * 128].view(np.uint16)[:] = q
-            s0, at = s0 + k, at + -(-(se - sb) // 16) * 16
+            s0 += k
         ws_bytes = self.ops.jpegdec_bounds(imgs)
         host[:o_seg] = np.frombuffer(imgs, np.uint8)
         host[o_seg:o_dht].view(np.int32)[:] = segs.reshape(-1)
@@ -772,29 +816,26 @@ class _ProgressiveJpeg(_DecoderBase):
     of `parse_jpeg_progressive`'s plans into the block of csrc/jpegprog.hip, and its four launches.  `stats` is the owner's
     `progressive_stats`."""
 
+    @staticmethod
+    def _is_mine(data: bytes) -> bool:
+        return _is_progressive(data)
+
     def _pack(self, plans: Sequence[Dict], out_offsets: Sequence[int]):
         """The upload block of `plans` in the staging buffer -> (block bytes, images, scans, segments, table versions, workspace bytes)."""
         n = len(plans)
-        imgs = (_lib.GanJpegdecImage * n)()
         nscan = sum(len(p["scans"]) for p in plans)
         nseg = sum(len(sc["seg_begin"]) for p in plans for sc in p["scans"])
         nver = sum(len(p["versions"]) for p in plans)
         o_pimg, o_scan, o_seg, o_dht, o_qt, o_data = self.ops.jpegprog_block_offsets(n, nscan, nseg, nver)
-        span = lambda p: (int(p["scans"][0]["seg_begin"][0]), int(p["scans"][-1]["seg_end"][-1]))      # first scan byte .. last scan's end
-        total = o_data + sum(-(-(span(p)[1] - span(p)[0]) // 16) * 16 for p in plans)
+        spans = [(int(p["scans"][0]["seg_begin"][0]), int(p["scans"][-1]["seg_end"][-1])) for p in plans]      # first scan byte .. last scan's end
+        total, host, imgs, shifts = _pack_jpeg_images(self, plans, out_offsets, spans, o_qt, o_data)
         pimg, scans, segs = np.zeros((n, 8), np.int32), np.zeros((nscan, 16), np.int32), np.zeros((nseg, 8), np.int32)
-        host = self._grow("_host", total, host=True).numpy()
         host[:o_pimg] = 0
-        host[o_dht:o_data] = 0
+        host[o_dht:o_qt] = 0
         c0 = s0 = v0 = 0
-        at = o_data
-        for i, (p, im) in enumerate(zip(plans, imgs)):
-            im.ncomp, im.H, im.W, im.hmax, im.vmax, im.mcux, im.mcuy = p["ncomp"], p["H"], p["W"], p["hmax"], p["vmax"], p["mcux"], p["mcuy"]
+        for i, (p, im, shift) in enumerate(zip(plans, imgs, shifts)):
             for c in range(3):
-                im.dc_tab[c], im.ac_tab[c], im.q_tab[c] = 0, 2, p["q_tab"][c]
-            im.out_off = int(out_offsets[i])
-            sb, se = span(p)
-            shift = at - sb
+                im.dc_tab[c], im.ac_tab[c] = 0, 2
             k = sum(len(sc["seg_begin"]) for sc in p["scans"])
             pimg[i] = (c0, len(p["scans"]), s0, k, v0, len(p["versions"]), p["nlevel"], 0)
             for j, sc in enumerate(p["scans"]):
@@ -808,12 +849,9 @@ class _ProgressiveJpeg(_DecoderBase):
                 rows[:, 4] = np.minimum(sc["per"], sc["units"] - rows[:, 3])
                 rows[:, 5], rows[:, 6] = sc["seg_begin"] + shift, sc["seg_end"] + shift
                 s0 += m
-            host[at:at + se - sb] = np.frombuffer(p["data"], np.uint8, se - sb, sb)
             for t, raw in enumerate(p["versions"]):
                 host[o_dht + (v0 + t) * 272:o_dht + (v0 + t) * 272 + len(raw)] = np.frombuffer(raw, np.uint8)
-            for t, q in p["qt"].items():
-                host[o_qt + (4 * i + t) * 128:o_qt + (4 * i + t + 1) * 128].view(np.uint16)[:] = q
-            c0, v0, at = c0 + len(p["scans"]), v0 + len(p["versions"]), at + -(-(se - sb) // 16) * 16
+            c0, v0 = c0 + len(p["scans"]), v0 + len(p["versions"])
         ws_bytes = self.ops.jpegprog_bounds(imgs, nver)
         host[:n * C.sizeof(_lib.GanJpegdecImage)] = np.frombuffer(imgs, np.uint8)
         host[o_pimg:o_scan].view(np.int32)[:] = pimg.reshape(-1)
@@ -936,6 +974,10 @@ class PngDecoder(_DecoderBase):
     def parse(data: bytes) -> Optional[Dict]:
         return parse_png(data)
 
+    @staticmethod
+    def _is_mine(data: bytes) -> bool:
+        return data[:8] == _PNG_SIGNATURE
+
     def _pack(self, plans: Sequence[Dict], out_offsets: Sequence[int]):
         """The upload block of `plans` in the staging buffer -> (block bytes, files, workspace bytes)."""
         n = len(plans)
@@ -996,26 +1038,9 @@ class DeviceDecoder(_DecoderBase):
             plan = parse_jpeg_progressive(data)
         return parse_png(data) if plan is None and self.png is not None else plan
 
-    def _groups(self, plans):
-        fmt = lambda p: p.get("format", "jpeg")
-        groups = [(self.jpeg, [i for i, p in enumerate(plans) if p is not None and fmt(p) == "jpeg"]),
-                  (self.png, [i for i, p in enumerate(plans) if p is not None and fmt(p) == "png"])]
-        if self.progressive:
-            groups.insert(1, (self.jpeg._prog, [i for i, p in enumerate(plans) if p is not None and fmt(p) == "jpegprog"]))
-        return groups
-
-    def _count(self, groups, loaded, rest):
-        super()._count(groups, loaded, rest)
-        if self.progressive:
-            self.jpeg._count_progressive(groups, loaded, rest)
-        self.stats["device"] += sum(len(idx) - len(d.last_errors) for d, idx in groups)
-        self.stats["flagged"] += len(self.last_errors)
-        for i in rest:
-            head = loaded[i][0][:8]
-            if self.png is not None and head == _PNG_SIGNATURE:
-                self.png.stats["unsupported"] += 1
-            elif self.jpeg is not None and head[:2] == b"\xff\xd8":
-                self.jpeg.stats["unsupported"] += 1
+    def _routes(self):
+        routes = {"jpeg": (self.jpeg, self), "jpegprog": (self.jpeg and self.jpeg._prog, self.jpeg, self), "png": (self.png, self)}
+        return {fmt: ds for fmt, ds in routes.items() if ds[0] is not None}
 
 
 class ImageStore:
