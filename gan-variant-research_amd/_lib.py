@@ -152,6 +152,9 @@ PROTOTYPES = {
     "gan_jpeg_blocks": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, i64, vp, vp]),
     "gan_jpeg_tables": (C.c_int, [vp, C.c_int, vp, vp, vp]),
     "gan_jpeg_scan": (C.c_int, [vp, i64, C.c_int, C.c_int, C.c_int, vp, vp, i64, vp, vp]),
+    "gan_crc32_ranges": (C.c_int, [vp, i64, vp, C.c_int, vp, vp, vp]),
+    "gan_jpeg_files_bounds": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(i64)]),
+    "gan_jpeg_files": (C.c_int, [vp, C.c_int, vp, C.c_int, vp, vp, i64, vp, C.c_int, vp, i64, vp, vp, vp, vp]),
     "gan_jpegdec_block_offsets": (C.c_int, [C.c_int, C.c_int, C.POINTER(i64)]),
     "gan_jpegdec_bounds": (C.c_int, [vp, C.c_int, C.POINTER(i64)]),
     "gan_jpegdec_tables": (C.c_int, [vp, vp, i64, C.c_int, C.c_int, vp, i64, vp]),

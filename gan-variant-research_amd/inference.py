@@ -8,6 +8,8 @@ Pillow's BILINEAR taps (:175-180) in front of it.  JPEG / PNG decoding is PIL's 
 `dataio.JpegDecoder`'s on the device with `device_decode=True` (the same pixels); JPEG encoding (:252) is PIL's by
 default and `JpegEncoder`'s on the device with `device_jpeg=True`, byte for byte the same files.  `stylize_folder` walks a
 PIL-readable folder, with the resize and both conversions on the host (the default) or on the device (`device_io=True`).
+`zip_path` makes the files the stored entries of one archive (`ZipWriter`, byte-identical to Python's zipfile); with the device
+encoder, `JpegEncoder.encode_block` hands over whole files and their CRC-32 from the device (csrc/zip.hip).
 The command line is generate_folder.py next to this file.
 """
 from __future__ import annotations
@@ -150,7 +152,7 @@ class JpegEncoder:
         self.ws, self.out = new(ws_bytes, torch.uint8), new(out_bytes, torch.uint8)
         self.hist, self.codes = new((self.max_batch, 4, 256), torch.int32), new((self.max_batch, 4, 256), torch.int32)
         self.dht, self.offsets = new((self.max_batch, 4, 272), torch.uint8), new(self.max_batch + 1, torch.int64)
-        self._programs = {}
+        self._programs, self._file_programs, self._files = {}, {}, None
         s = 5000 // self.quality if self.quality < 50 else 200 - 2 * self.quality
         head = b"\xff\xd8" + _segment(0xE0, b"JFIF\x00" + bytes((1, 1, 0, 0, 1, 0, 1, 0, 0)))
         for i, base in enumerate((_JPEG_LUMA, _JPEG_CHROMA)):
@@ -189,6 +191,161 @@ class JpegEncoder:
             files.append(self._head + tables + self._sos + scan[off[b]:off[b + 1]] + b"\xff\xd9")
         return files
 
+    def _file_program(self, B: int):
+        """The buffers of `encode_block`, made at its first call (an encoder that only serves `encode` never holds them), and the launch
+        sequence for a batch of B."""
+        if self._files is None:
+            o, mb = self.ops, self.max_batch
+            as_dev = lambda data: torch.frombuffer(bytearray(data), dtype=torch.uint8).to(self.device)
+            self._head_dev, self._sos_dev = as_dev(self._head), as_dev(self._sos)
+            self._files = torch.zeros(o.jpeg_files_bounds(mb, self.H, self.W, len(self._head), len(self._sos)), dtype=torch.uint8, device=self.device)
+            # one block for everything that comes back beside the files: int64 offsets [mb + 1] | int32 crc [mb] | int32 flag
+            self._meta = torch.zeros(8 * (mb + 1) + 4 * mb + 4, dtype=torch.uint8, device=self.device)
+            self.file_offsets = self._meta[:8 * (mb + 1)].view(torch.int64)
+            self.crc, self.flag = self._meta[8 * (mb + 1):8 * (mb + 1) + 4 * mb].view(torch.int32), self._meta[8 * (mb + 1) + 4 * mb:].view(torch.int32)
+        prog = self._file_programs.get(B)
+        if prog is None:
+            prog = self._file_programs[B] = self._program(B) + [self.ops.jpeg_files(self._head_dev, self._sos_dev, self.dht, self.out, self.offsets, B, self._files,
+                                                                                    self.file_offsets, self.crc, self.flag)]
+        return prog
+
+    @torch.inference_mode()
+    def encode_block(self, batch: torch.Tensor):
+        """`encode` for a consumer that wants the files as they lie in memory: (block, offsets, crcs) with block a bytes-like object
+        (a memoryview), `block[offsets[b]:offsets[b + 1]]` the file `encode(batch)[b]`, and crcs[b] its CRC-32 (zlib.crc32).  The files are
+        put together and checksummed on the device (csrc/zip.hip); two downloads: offsets, CRCs and the flag word in one small copy, the
+        files in one contiguous copy."""
+        from ._lib import GanError
+        B = int(batch.shape[0])
+        if batch.dtype != torch.uint8 or tuple(batch.shape[1:]) != (self.H, self.W, 3) or not 1 <= B <= self.max_batch or batch.device != self.rgb.device:
+            raise ValueError(f"JpegEncoder.encode_block: expected uint8 (1 .. {self.max_batch}, {self.H}, {self.W}, 3) on {self.rgb.device}, "
+                             f"got {batch.dtype} {tuple(batch.shape)} on {batch.device}")
+        prog = self._file_program(B)
+        self.rgb[:B].copy_(batch)
+        for op in prog:
+            op()
+        mb = self.max_batch
+        meta = self._meta.cpu().numpy()
+        off = meta[:8 * (B + 1)].view("<i8").tolist()
+        crcs = meta[8 * (mb + 1):8 * (mb + 1) + 4 * B].view("<u4").tolist()
+        flag = int(meta[8 * (mb + 1) + 4 * mb:].view("<u4")[0])
+        if flag:
+            raise GanError(f"JpegEncoder.encode_block: the device flagged the batch (flag = {flag}: 1 = inconsistent scan offsets, 2 = the files buffer is too small)")
+        return memoryview(self._files[:off[B]].cpu().numpy()), off, crcs
+
+
+class ZipWriter:
+    """A ZIP archive of stored (uncompressed) entries, byte-identical to Python's zipfile for
+    `ZipFile(path, "w", ZIP_STORED)` with `writestr(ZipInfo(name, date_time=date_time), data)` per entry in the same order: version 20,
+    no data descriptor, external attributes 0o600 << 16, flag 0x800 for a name that is not ASCII.  An entry needs its name, its bytes and
+    their CRC-32; `add_block` takes the CRCs from whoever has them already (JpegEncoder.encode_block: the device).  The archive is
+    written to path + ".part" and renamed by a clean close; an exception inside `with` removes the part file.  No ZIP64: more than
+    MAX_ENTRIES entries, or a size or an offset of MAX_BYTES or more, is a ValueError, and so is a repeated name."""
+    MAX_ENTRIES = 65535
+    MAX_BYTES = 1 << 32
+
+    def __init__(self, path, date_time=(1980, 1, 1, 0, 0, 0)):
+        import struct
+        import sys
+        self._struct = struct
+        self.path, self._part = str(path), str(path) + ".part"
+        y, mo, d, h, mi, sec = date_time
+        if not (1980 <= y <= 2107 and 1 <= mo <= 12 and 1 <= d <= 31 and 0 <= h <= 23 and 0 <= mi <= 59 and 0 <= sec <= 59):
+            raise ValueError(f"ZipWriter: date_time = {date_time}: a ZIP holds 1980-01-01 .. 2107-12-31")
+        self._date, self._time = (y - 1980) << 9 | mo << 5 | d, h << 11 | mi << 5 | sec // 2
+        self._system = 0 if sys.platform == "win32" else 3              # zipfile.ZipInfo.create_system
+        self._entries, self._names, self._pos = [], set(), 0
+        self._f = open(self._part, "wb")
+
+    def __len__(self):
+        return len(self._entries)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, exc_type, exc, tb):
+        if exc_type is None:
+            self.close()
+        else:
+            self.abort()
+        return False
+
+    def abort(self):
+        """Drop the archive: the part file goes, nothing appears at `path`."""
+        import os
+        if self._f is not None:
+            self._f.close()
+            self._f = None
+            if os.path.exists(self._part):
+                os.remove(self._part)
+
+    def _local(self, name: str, size: int, crc: int) -> bytes:
+        """The local header of the next entry, recorded for the central directory."""
+        if self._f is None:
+            raise ValueError("ZipWriter: the archive is closed")
+        if name in self._names:
+            raise ValueError(f"ZipWriter: the name {name!r} is in the archive already")
+        if len(self._entries) >= self.MAX_ENTRIES:
+            raise ValueError(f"ZipWriter: more than {self.MAX_ENTRIES} entries need ZIP64, which is not written")
+        try:
+            raw, flags = name.encode("ascii"), 0
+        except UnicodeEncodeError:
+            raw, flags = name.encode("utf-8"), 0x800
+        if len(raw) > 65535:
+            raise ValueError("ZipWriter: a name of more than 65535 bytes")
+        if size >= self.MAX_BYTES or self._pos >= self.MAX_BYTES or self._pos + 30 + len(raw) + size >= self.MAX_BYTES:
+            raise ValueError(f"ZipWriter: a size or an offset of {self.MAX_BYTES} or more needs ZIP64, which is not written")
+        self._names.add(name)
+        self._entries.append((raw, flags, crc, size, self._pos))
+        self._pos += 30 + len(raw) + size
+        return self._struct.pack("<4s2B4HL2L2H", b"PK\x03\x04", 20, 0, flags, 0, self._time, self._date, crc, size, size, len(raw), 0) + raw
+
+    def add(self, name: str, data, crc=None):
+        """One entry; crc: the CRC-32 of data when the caller has it, else zlib.crc32 computes it here."""
+        import zlib
+        data = memoryview(data).cast("B")
+        head = self._local(name, len(data), (zlib.crc32(data) if crc is None else int(crc)) & 0xFFFFFFFF)
+        self._f.write(head)
+        self._f.write(data)
+
+    def add_block(self, names, block, offsets, crcs=None):
+        """len(names) entries from one block: entry b is block[offsets[b]:offsets[b + 1]] with CRC-32 crcs[b] (crcs None: computed
+        here).  Headers and data go out in one write."""
+        import zlib
+        block = memoryview(block).cast("B")
+        if len(offsets) != len(names) + 1 or (crcs is not None and len(crcs) != len(names)):
+            raise ValueError(f"ZipWriter.add_block: {len(names)} names, {len(offsets)} offsets, {None if crcs is None else len(crcs)} CRCs")
+        if any(not 0 <= offsets[b] <= offsets[b + 1] <= len(block) for b in range(len(names))):
+            raise ValueError("ZipWriter.add_block: offsets that do not lie in the block in order")
+        parts = []
+        for b, name in enumerate(names):
+            data = block[offsets[b]:offsets[b + 1]]
+            parts.append(self._local(name, len(data), (zlib.crc32(data) if crcs is None else int(crcs[b])) & 0xFFFFFFFF))
+            parts.append(data)
+        self._f.write(b"".join(parts))
+
+    def close(self):
+        """Central directory and end record, then the rename to `path`.  A second close does nothing."""
+        import os
+        if self._f is None:
+            return
+        try:
+            start, pack = self._pos, self._struct.pack
+            out = []
+            for raw, flags, crc, size, offset in self._entries:
+                out.append(pack("<4s4B4HL2L5H2L", b"PK\x01\x02", 20, self._system, 20, 0, flags, 0, self._time, self._date, crc, size, size, len(raw), 0, 0,
+                                0, 0, 0o600 << 16, offset) + raw)
+            cd = b"".join(out)
+            if start + len(cd) >= self.MAX_BYTES:
+                raise ValueError(f"ZipWriter: a central directory that ends at {self.MAX_BYTES} or beyond needs ZIP64, which is not written")
+            self._f.write(cd + pack("<4s4H2LH", b"PK\x05\x06", 0, 0, len(self._entries), len(self._entries), len(cd), start, 0))
+        except BaseException:
+            self.abort()
+            raise
+        self._f.close()
+        self._f = None
+        os.replace(self._part, self.path)
+
 
 def _jpeg_encoder(G, device, batch: int, H: int, W: int) -> JpegEncoder:
     """The encoder cached on the generator, like `_infer_pipe`."""
@@ -226,9 +383,9 @@ def _folder_decoder(G, device, jpeg: bool, png: bool, progressive: bool = False)
 
 
 @torch.inference_mode()
-def stylize_folder(G, src_dir: str, out_dir: str, device: str = "cuda", img_size: int = 256, batch: int = 16, limit: Optional[int] = None,
+def stylize_folder(G, src_dir: str, out_dir: Optional[str] = None, device: str = "cuda", img_size: int = 256, batch: int = 16, limit: Optional[int] = None,
                    device_io: bool = False, device_jpeg: bool = False, io_threads: int = 1, device_decode: bool = False, decode_chunk: int = 256,
-                   device_png: bool = False, device_progressive: bool = False) -> int:
+                   device_png: bool = False, device_progressive: bool = False, zip_path: Optional[str] = None) -> int:
     """generate_folder.py:207-252 with PIL doing what torchvision's Resize(BILINEAR) / ToTensor / Normalize / ToPILImage do there.
     device_io: PIL only decodes and encodes; each photo is uploaded as uint8 HWC, `stylize_images` resizes, normalises, runs the
     generator and converts on the device, and one contiguous HWC download feeds PIL.  The files written are byte-identical.
@@ -240,9 +397,18 @@ def stylize_folder(G, src_dir: str, out_dir: str, device: str = "cuda", img_size
     the decoder flags, still go through PIL.  device_png (needs device_io; independent of device_decode): the same for the PNGs, with
     `dataio.PngDecoder` (one workgroup per file: again the files in flight are its throughput); with both switches one
     `dataio.DeviceDecoder` reads every file once and sends it by its content.  device_progressive (needs device_decode): the
-    progressive JPEGs `dataio.parse_jpeg_progressive` accepts are decoded on the device too, in the same calls.  Same files either way."""
+    progressive JPEGs `dataio.parse_jpeg_progressive` accepts are decoded on the device too, in the same calls.  Same files either way.
+    zip_path: the files also (or, without out_dir, only) become the stored entries of one archive, written by `ZipWriter` in the order
+    of the sorted paths; an entry is named like the file, relative to the output root with `/` separators.  With device_jpeg the
+    entries come from `JpegEncoder.encode_block`: whole files and their CRC-32 from the device, no per-file assembly and no checksum
+    on the host; otherwise PIL saves into memory and the writer checksums.  Two sources that map to one output name (a.png beside
+    a.jpg) are a ValueError there, where the folder keeps the later file.  At least one of out_dir and zip_path is required."""
+    import contextlib
+    import io
     import numpy as np
     from PIL import Image
+    if out_dir is None and zip_path is None:
+        raise ValueError("stylize_folder: give out_dir, zip_path or both: there is nowhere to write")
     if device_jpeg and not device_io:
         raise ValueError("device_jpeg=True needs device_io=True: the encoder reads the uint8 batch the device epilogue leaves")
     if device_decode and not device_io:
@@ -256,13 +422,14 @@ def stylize_folder(G, src_dir: str, out_dir: str, device: str = "cuda", img_size
     if io_threads < 1:
         raise ValueError(f"io_threads = {io_threads}: at least 1")
     exts = {".jpg", ".jpeg", ".png", ".bmp", ".webp", ".tif", ".tiff"}
-    src_root, out_root = Path(src_dir), Path(out_dir)
+    src_root, out_root = Path(src_dir), None if out_dir is None else Path(out_dir)
     paths = sorted(p for p in src_root.rglob("*") if p.suffix.lower() in exts)
     if limit is not None:
         paths = paths[:limit]
     if not paths:
         raise FileNotFoundError(f"No images found under: {src_dir}")
-    out_root.mkdir(parents=True, exist_ok=True)
+    if out_root is not None:
+        out_root.mkdir(parents=True, exist_ok=True)
     pool = None
     if io_threads > 1:
         from concurrent.futures import ThreadPoolExecutor
@@ -285,6 +452,14 @@ def stylize_folder(G, src_dir: str, out_dir: str, device: str = "cuda", img_size
 
     def save_bytes(p, data):
         target(p).write_bytes(data)
+
+    def pil_bytes(img):
+        buf = io.BytesIO()
+        Image.fromarray(img).save(buf, format="JPEG", quality=95, subsampling=0, optimize=True)
+        return buf.getvalue()
+
+    def entry(p):
+        return p.relative_to(src_root).with_suffix(".jpg").as_posix()
 
     def decoded_ahead():
         """The images of `paths` in chunks of decode_chunk files, the next chunk being decoded while the caller works on this one."""
@@ -309,31 +484,48 @@ def stylize_folder(G, src_dir: str, out_dir: str, device: str = "cuda", img_size
                     imgs[0].record_stream(main)      # one buffer behind all views; allocated on the side stream, read on this one
                 yield imgs
 
-    try:
-        on_device = device_decode or device_png
-        ready, chunks = [], decoded_ahead() if on_device else None
-        for i in range(0, len(paths), batch):
-            chunk = paths[i:i + batch]
-            if device_io:
-                if on_device:
-                    while len(ready) < min(i + batch, len(paths)):
-                        ready.extend(next(chunks))
-                    imgs, ready[i:i + batch] = ready[i:i + batch], [None] * len(chunk)
+    with contextlib.ExitStack() as stack:
+        # one writer, on this thread, in the order of `paths`: the pool only ever encodes and writes files of the folder
+        zw = stack.enter_context(ZipWriter(zip_path)) if zip_path is not None else None
+        try:
+            on_device = device_decode or device_png
+            ready, chunks = [], decoded_ahead() if on_device else None
+            for i in range(0, len(paths), batch):
+                chunk = paths[i:i + batch]
+                if device_io:
+                    if on_device:
+                        while len(ready) < min(i + batch, len(paths)):
+                            ready.extend(next(chunks))
+                        imgs, ready[i:i + batch] = ready[i:i + batch], [None] * len(chunk)
+                    else:
+                        imgs = [torch.from_numpy(a).to(device) for a in each(decode, chunk)]
+                    y = stylize_images(G, imgs, img_size)
+                    if device_jpeg:
+                        enc = _jpeg_encoder(G, y.device, len(chunk), img_size, img_size)
+                        if zw is None:
+                            each(save_bytes, chunk, enc.encode(y))
+                            continue
+                        block, off, crcs = enc.encode_block(y)
+                        zw.add_block([entry(p) for p in chunk], block, off, crcs)
+                        if out_root is not None:
+                            each(save_bytes, chunk, [block[off[b]:off[b + 1]] for b in range(len(chunk))])
+                        continue
+                    y = y.cpu().numpy()
                 else:
-                    imgs = [torch.from_numpy(a).to(device) for a in each(decode, chunk)]
-                y = stylize_images(G, imgs, img_size)
-                if device_jpeg:
-                    each(save_bytes, chunk, _jpeg_encoder(G, y.device, len(chunk), img_size, img_size).encode(y))
+                    arr = np.stack(each(decode_resized, chunk))
+                    x = torch.from_numpy(arr).permute(0, 3, 1, 2).div(255.0).sub(0.5).div(0.5).contiguous().to(device)
+                    y = stylize(G, x).cpu().permute(0, 2, 3, 1).numpy()
+                if zw is None:
+                    each(save_pil, chunk, y)
                     continue
-                y = y.cpu().numpy()
-            else:
-                arr = np.stack(each(decode_resized, chunk))
-                x = torch.from_numpy(arr).permute(0, 3, 1, 2).div(255.0).sub(0.5).div(0.5).contiguous().to(device)
-                y = stylize(G, x).cpu().permute(0, 2, 3, 1).numpy()
-            each(save_pil, chunk, y)
-    finally:
-        if chunks is not None:
-            chunks.close()
-        if pool is not None:
-            pool.shutdown()
+                files = each(pil_bytes, y)
+                if out_root is not None:
+                    each(save_bytes, chunk, files)
+                for p, data in zip(chunk, files):
+                    zw.add(entry(p), data)
+        finally:
+            if chunks is not None:
+                chunks.close()
+            if pool is not None:
+                pool.shutdown()
     return len(paths)

@@ -571,6 +571,32 @@ class HipOps:
         assert codes.numel() >= B * 1024 and offsets.numel() >= B + 1 and out.is_contiguous() and offsets.is_contiguous()
         return self._call("gan_jpeg_scan", self._p(ws), ws.numel(), B, H, W, self._p(codes), self._p(out), out.numel(), self._p(offsets), self._s())
 
+    # ---- whole files and their CRC-32 for stored ZIP entries (csrc/zip.hip; inference.JpegEncoder owns the buffers)
+    def crc32_ranges(self, buf: torch.Tensor, offsets: torch.Tensor, crc: torch.Tensor, flag: torch.Tensor) -> Op:
+        """zlib's CRC-32 of buf[offsets[i]:offsets[i + 1]] for the n = len(offsets) - 1 ranges, into crc (n) int32; an inconsistent pair
+        gives 0 and ORs 1 into flag (1) int32, which the caller zeroes."""
+        n = offsets.numel() - 1
+        assert buf.dtype == torch.uint8 and offsets.dtype == torch.int64 and crc.dtype == torch.int32 and flag.dtype == torch.int32
+        assert buf.is_contiguous() and offsets.is_contiguous() and crc.is_contiguous() and n >= 0 and crc.numel() >= n and flag.numel() >= 1
+        return self._call("gan_crc32_ranges", self._p(buf), buf.numel(), self._p(offsets), n, self._p(crc), self._p(flag), self._s())
+
+    def jpeg_files_bounds(self, B, H, W, head_bytes, sos_bytes=14):
+        """Bytes that B complete files of H x W can need: jpeg_bounds' scan bytes plus head, four full DHT segments, SOS and EOI each."""
+        out = C.c_int64(0)
+        _lib.check(self.lib.gan_jpeg_files_bounds(B, H, W, int(head_bytes), int(sos_bytes), C.byref(out)), "gan_jpeg_files_bounds")
+        return int(out.value)
+
+    def jpeg_files(self, head: torch.Tensor, sos: torch.Tensor, dht: torch.Tensor, scan: torch.Tensor, scan_offsets: torch.Tensor, B,
+                   files: torch.Tensor, file_offsets: torch.Tensor, crc: torch.Tensor, flag: torch.Tensor) -> Op:
+        """Complete JPEG files back to back in files: head, the four DHT segments of dht (B, 4, 272), sos, the image's bytes of scan, EOI.
+        file_offsets (B + 1) int64, crc (B) int32 = CRC-32 of every file, flag (1) int32: bit 0 inconsistent scan_offsets, bit 1 files too small."""
+        assert all(t.dtype == torch.uint8 and t.is_contiguous() for t in (head, sos, dht, scan, files))
+        assert scan_offsets.dtype == torch.int64 and file_offsets.dtype == torch.int64 and crc.dtype == torch.int32 and flag.dtype == torch.int32
+        assert dht.numel() >= B * 4 * 272 and scan_offsets.numel() >= B + 1 and file_offsets.numel() >= B + 1 and crc.numel() >= B and flag.numel() >= 1
+        assert scan_offsets.is_contiguous() and file_offsets.is_contiguous() and crc.is_contiguous()
+        return self._call("gan_jpeg_files", self._p(head), head.numel(), self._p(sos), sos.numel(), self._p(dht), self._p(scan), scan.numel(),
+                          self._p(scan_offsets), int(B), self._p(files), files.numel(), self._p(file_offsets), self._p(crc), self._p(flag), self._s())
+
     # ---- JPEG decoder (csrc/jpegdec.hip; dataio.JpegDecoder owns the buffers).  A decode's descriptors are new with every call, so these
     #      entries launch at once instead of returning a prebuilt Op.
     def _now(self, name: str, *args):

@@ -240,6 +240,7 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--device-png", action="store_true", help="Decode PNGs on the device")
     p.add_argument("--device", type=str, default=None, help="Device: cuda or cuda:N")
     p.add_argument("--no-copy", action="store_true", help="Write the meta file and the table, copy no image")
+    p.add_argument("--zip", default=None, metavar="PATH", help="Write the selected images as stored entries of this archive (what images/ holds), also with --no-copy")
     return p
 
 
@@ -289,19 +290,28 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
         outimgs.mkdir(parents=True, exist_ok=True)
         for p in sel_paths:
             shutil.copy2(p, outimgs / Path(p).name)               # as in the reference, a later file of the same name overwrites
+    zipped = None
+    if a.zip:
+        from .inference import ZipWriter
+        last = {Path(p).name: p for p in sel_paths}              # what images/ holds after the copy: the last file of a name
+        with ZipWriter(a.zip) as zw:
+            for name in sorted(last):
+                zw.add(name, Path(last[name]).read_bytes())      # bytes from disk: the checksum is the host's
+            zipped = len(zw)
     if collisions:
         print(f"{collisions} selected images share a file name with an earlier one; images/ holds {len(set(names))} files")
     with open(Path(a.outdir) / "selection_meta.json", "w") as f:
         json.dump({"real": a.real, "cand_roots": a.cand_roots, "tau": a.tau, "k": a.k, "selected": len(sel_paths),
                    "candidates": len(cand_paths), "kept": int(res["kept"].sum()), "collisions": collisions,
-                   "kmeans_inertia": res["kmeans"]["inertia"], "kmeans_n_iter": res["kmeans"]["n_iter"]}, f, indent=2)
+                   "kmeans_inertia": res["kmeans"]["inertia"], "kmeans_n_iter": res["kmeans"]["n_iter"],
+                   **({"zip": a.zip, "zip_entries": zipped} if a.zip else {})}, f, indent=2)
     with open(Path(a.outdir) / "selection.csv", "w", newline="") as f:
         w = csv.writer(f)
         w.writerow(["path", "score", "dist", "min_cos", "nearest_real_path", "rank"])
         for rank, i in enumerate(res["chosen"], 1):
             w.writerow([str(cand_paths[i]), repr(float(res["score"][i])), repr(float(res["dist"][i])), repr(float(res["min_cos"][i])),
                         str(real_paths[int(res["nearest_real"][i])]), rank])
-    print(f"Selected {len(sel_paths)} images into {outimgs}")
+    print(f"Selected {len(sel_paths)} images into {outimgs if not a.no_copy or not a.zip else a.zip}")
     return 0
 
 

@@ -484,6 +484,36 @@ int gan_jpeg_tables(const uint32_t* hist, int n, uint8_t* dht, uint32_t* codes, 
 int gan_jpeg_scan(void* ws, int64_t ws_bytes, int B, int H, int W, const uint32_t* codes, uint8_t* out, int64_t out_bytes, int64_t* offsets,
                   void* stream);
 
+/* ---- What a stored ZIP entry needs beside its name, made on the device: the bytes of the file and their CRC-32 (csrc/zip.hip).
+ *      The CRC-32 is zlib's: reflected polynomial 0xEDB88320, register all ones at the start, complemented at the end; an empty range
+ *      gives 0.  Integer arithmetic only and no atomic whose order matters (the only one ORs a constant into `flag`), so repeated
+ *      calls give identical words.  Refused with a message, before any launch: a NULL pointer, a negative count or byte size, B outside
+ *      1 .. 65535, a head outside 2 .. 65535 or an SOS outside 4 .. 65535 bytes, an image size gan_jpeg_bounds refuses. */
+/* CRC-32 of n byte ranges of one device buffer; range i is buf[offsets[i] .. offsets[i + 1]).  offsets: int64 [n + 1] on the device (what
+ * gan_jpeg_scan and gan_jpeg_files leave there); crc: uint32 [n] on the device; flag: one uint32 on the device, zeroed by the caller.
+ * One launch, one workgroup of 256 lanes per range: the range is cut into 256 pieces at addresses that are multiples of 16, a lane
+ * runs its piece through four slice tables in LDS (16-byte loads), multiplies its register by x^(8 bytes after its piece) modulo the
+ * polynomial (32-step carry-less multiply, x^(2^k) from a table) and the workgroup XORs the products.  Every load is clamped to
+ * [0, buf_bytes).  An inconsistent pair (negative, decreasing, or past buf_bytes) reads nothing, writes 0 for that range and ORs 1 into
+ * *flag; the other ranges are not affected.  n == 0 succeeds and launches nothing. */
+int gan_crc32_ranges(const uint8_t* buf, int64_t buf_bytes, const int64_t* offsets, int n, uint32_t* crc, uint32_t* flag, void* stream);
+/* Host only: bytes of `files` that B images of H x W can need: out_bytes of gan_jpeg_bounds + B (head_bytes + 4 (5 + 16 + 256) +
+ * sos_bytes + 2). */
+int gan_jpeg_files_bounds(int B, int H, int W, int head_bytes, int sos_bytes, int64_t* files_bytes);
+/* Complete JPEG files back to back on the device.  head: the constant bytes SOI .. SOF0; sos: the constant SOS segment; dht: uint8
+ * [B][4][272] from gan_jpeg_tables (tables DC-Y, AC-Y, DC-C, AC-C); scan / scan_offsets (int64 [B + 1]): what gan_jpeg_scan left.
+ * File b = head | four DHT segments in the order DC0 AC0 DC1 AC1 (class / id bytes 0x00 0x10 0x01 0x11), each FF C4, the big-endian
+ * length 2 + 1 + 16 + n_t, the class byte, the 16 counts and n_t = min(sum of the counts, 256) symbols | sos | scan bytes of image b |
+ * FF D9.  Three launches with no host round trip between them: sizes and their exclusive scan (one workgroup), the copy (one workgroup
+ * per file; correct for every byte alignment of source and destination), the CRC-32 of every file (the kernel of gan_crc32_ranges).
+ * files: file b is files[file_offsets[b] .. file_offsets[b + 1]); file_offsets: int64 [B + 1] on the device; crc: uint32 [B]; flag: one
+ * uint32, overwritten: bit 0 = a pair of scan_offsets is inconsistent (negative, decreasing or past scan_bytes; that file gets an empty
+ * scan), bit 1 = files_bytes is too small (the offsets are clamped to it and the files that do not fit are cut short).  Nothing past
+ * files[files_bytes) is written. */
+int gan_jpeg_files(const uint8_t* head, int head_bytes, const uint8_t* sos, int sos_bytes, const uint8_t* dht, const uint8_t* scan,
+                   int64_t scan_bytes, const int64_t* scan_offsets, int B, uint8_t* files, int64_t files_bytes, int64_t* file_offsets,
+                   uint32_t* crc, uint32_t* flag, void* stream);
+
 /* ---- Baseline JPEG decoder on the device: the pixels Image.open(p).convert("RGB") gives (libjpeg-turbo's 8-bit path: Huffman decode,
  *      jidctint.c's jpeg_idct_islow, jdsample.c's fancy h2v1 / h2v2 upsampling, jdcolor.c's YCbCr -> RGB), for the files a host parser
  *      accepted: SOF0, 8 bit, one interleaved scan, 1 component (1x1) or 3 components with chroma 1x1 and luma 1x1 / 2x1 / 2x2, no Adobe

@@ -13,10 +13,14 @@
 (f) progressive JPEG decode (--progressive): 256 progressive JPEGs of 256 x 256 (the JPEG folder's images) at batch 16 with device_jpeg: PIL
     decoding serially and on a pool (io_threads 4, 16) against device_progressive (with device_decode) at decode_chunk 64 / 256; same files every mode
 
+(g, h, i) the archive (--zip): 256 JPEGs of 256 x 256 at batch 16 with device_jpeg and device_decode (decode_chunk 256), from the first read
+    to the closed images.zip: (g) stylize_folder into a folder, then zipfile (stored) over that folder; (h) zip_path with the files from
+    encode() and zlib's CRC on the host; (i) zip_path with encode_block (files and CRC-32 from the device); same archive bytes every mode
+
 Every shape is warmed up; the two paths are then timed in rotation for --rounds rounds (a host clock around work that ends in a device
 synchronise: each call ends in a download); the median round and the spread (min .. max) are reported.  The outputs of the two paths
 are compared before anything is timed.
-usage: bench_stylize.py [--size 256] [--batches 1,4,16] [--calls 40] [--rounds 5] [--photos 64] [--out FILE] [--jpeg] [--only-jpeg] [--decode] [--only-decode] [--png] [--only-png] [--progressive] [--only-progressive]
+usage: bench_stylize.py [--size 256] [--batches 1,4,16] [--calls 40] [--rounds 5] [--photos 64] [--out FILE] [--jpeg] [--only-jpeg] [--decode] [--only-decode] [--png] [--only-png] [--progressive] [--only-progressive] [--zip] [--only-zip]
 """
 import argparse
 import os
@@ -154,6 +158,69 @@ def progressive_section(G, dev, S, rounds, tmp: Path):
     return lines
 
 
+def zip_section(G, dev, S, rounds, tmp: Path):
+    """(g), (h), (i): every mode leaves the same archive bytes (checked first), then the modes run in rotation; images/s, median [min .. max]."""
+    import zipfile
+    n, src = 256, tmp / "jpegs"
+    if not src.exists():
+        make_jpeg_folder(src, n, S)
+    kw = dict(device=str(dev), img_size=S, batch=16, device_io=True, device_jpeg=True, device_decode=True, decode_chunk=256)
+    device_block = I.JpegEncoder.encode_block
+
+    def host_block(self, batch):
+        """What a writer without the device's files has: encode()'s per-file assembly, joined, and no CRC (the writer runs zlib's)."""
+        files = self.encode(batch)
+        off = [0]
+        for f in files:
+            off.append(off[-1] + len(f))
+        return b"".join(files), off, None
+
+    def today(out):
+        assert I.stylize_folder(G, str(src), str(tmp / "g_dir"), **kw) == n
+        with zipfile.ZipFile(out, "w", zipfile.ZIP_STORED) as z:
+            for p in sorted((tmp / "g_dir").rglob("*.jpg")):
+                z.writestr(zipfile.ZipInfo(p.relative_to(tmp / "g_dir").as_posix(), date_time=(1980, 1, 1, 0, 0, 0)), p.read_bytes())
+
+    def direct(block_fn):
+        def go(out):
+            I.JpegEncoder.encode_block = block_fn
+            try:
+                assert I.stylize_folder(G, str(src), zip_path=str(out), **kw) == n
+            finally:
+                I.JpegEncoder.encode_block = device_block
+        return go
+    MODES = (("g  folder, then zipfile over it", today), ("h  zip_path, encode() + host CRC", direct(host_block)), ("i  zip_path, encode_block", direct(device_block)))
+
+    def mode(i, go):
+        def run():
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            go(tmp / f"zip_{i}.zip")
+            torch.cuda.synchronize()
+            return n / (time.perf_counter() - t0)
+        return run
+    paths = {name: mode(i, go) for i, (name, go) in enumerate(MODES)}
+    for fn in paths.values():
+        fn()
+    outs = [(tmp / f"zip_{i}.zip").read_bytes() for i in range(len(MODES))]
+    assert all(o == outs[0] for o in outs), "the modes wrote different archives"
+    with zipfile.ZipFile(tmp / "zip_2.zip") as z:
+        assert z.testzip() is None and len(z.infolist()) == n
+    times = rotate(paths, rounds)
+    lines = [f"# (g, h, i) images/s from the first read to the closed archive: {n} JPEGs of {S}x{S}, batch 16, device_jpeg, device_decode (chunk 256); "
+             f"median of {rounds} alternating rounds [min .. max]; archive of {len(outs[0])} bytes, identical in every mode"]
+    for name, v in times.items():
+        lines.append(f"({name[0]}) {name[3:]:36s} {statistics.median(v):8.1f} images/s [{min(v):8.1f} .. {max(v):8.1f}]")
+    keys = list(times)
+    for a, b in ((2, 1), (2, 0), (1, 0)):
+        va, vb = times[keys[a]], times[keys[b]]
+        verdict = "faster than" if min(va) > max(vb) else "slower than" if max(va) < min(vb) else "not apart from"
+        lines.append(f"({keys[a][0]}) {verdict} ({keys[b][0]}) beyond both spreads ([{min(va):.1f} .. {max(va):.1f}] vs [{min(vb):.1f} .. {max(vb):.1f}])")
+    for ln in lines:
+        print(ln, flush=True)
+    return lines
+
+
 def jpeg_section(G, dev, S, rounds, photos, tmp: Path):
     """(c): every mode writes the same files (checked first), then the modes run in rotation; images/s, median [min .. max]."""
     lines = [f"# (c) images/s over one pass of a folder, batch 16, {S}x{S}, decode and JPEG encode included; median of {rounds} alternating rounds [min .. max]"]
@@ -219,7 +286,10 @@ def main():
     ap.add_argument("--only-png", action="store_true", help="run section (e) alone")
     ap.add_argument("--progressive", action="store_true", help="also run section (f)")
     ap.add_argument("--only-progressive", action="store_true", help="run section (f) alone")
+    ap.add_argument("--zip", action="store_true", help="also run sections (g, h, i)")
+    ap.add_argument("--only-zip", action="store_true", help="run sections (g, h, i) alone")
     a = ap.parse_args()
+    a.zip = a.zip or a.only_zip
     a.decode = a.decode or a.only_decode
     a.png = a.png or a.only_png
     a.progressive = a.progressive or a.only_progressive
@@ -232,9 +302,10 @@ def main():
     G.compute_dtype = BF16
     lines = [f"# tools/bench_stylize.py --size {S} --batches {a.batches} --calls {a.calls} --rounds {a.rounds} --photos {a.photos}"
              + (" --only-jpeg" if a.only_jpeg else " --jpeg" if a.jpeg else "") + (" --only-decode" if a.only_decode else " --decode" if a.decode else "")
-             + (" --only-png" if a.only_png else " --png" if a.png else "") + (" --only-progressive" if a.only_progressive else " --progressive" if a.progressive else ""),
+             + (" --only-png" if a.only_png else " --png" if a.png else "") + (" --only-progressive" if a.only_progressive else " --progressive" if a.progressive else "")
+             + (" --only-zip" if a.only_zip else " --zip" if a.zip else ""),
              f"# generator ngf 64, 9 blocks, bf16 operands, eager launches; median of {a.rounds} alternating rounds [min .. max]"]
-    only = a.only_jpeg or a.only_decode or a.only_png or a.only_progressive
+    only = a.only_jpeg or a.only_decode or a.only_png or a.only_progressive or a.only_zip
     if not only:
         lines.append(f"# (a) ms per call of {a.calls} consecutive calls, each ending in the download of the uint8 HWC batch to the host")
     old_out = lambda x: I.stylize(G, x).cpu().permute(0, 2, 3, 1).contiguous()
@@ -287,6 +358,8 @@ def main():
             lines += decode_section(G, dev, S, a.rounds, a.photos, tmp, png=True)
         if a.progressive:
             lines += progressive_section(G, dev, S, a.rounds, tmp)
+        if a.zip:
+            lines += zip_section(G, dev, S, a.rounds, tmp)
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
         with open(a.out, "w") as f:
