@@ -22,11 +22,33 @@ constexpr int PRECISION_BITS = 32 - 8 - 2;
 
 __device__ __forceinline__ int clip8(int v) { return v < 0 ? 0 : (v > 255 ? 255 : v); }
 
-// ---- horizontal pass: source rows of the crop box -> tmp [B][tmp_rows][S][4] (uint8 RGBX), only the window's columns
+// Pillow 12.2 Image.resize makes the vertical pass first when the source is more than 100 times taller than wide and the target is
+// lower than the source (`size[1] > size[0] * 100 and new_height < size[1]`, either filter).  The bytes between the passes are rounded,
+// so the order shows in the result.
+__device__ __forceinline__ bool vertical_first(const gan_input_job& j) { return j.crop_h > (int64_t)100 * j.crop_w && j.res_h < j.crop_h; }
+
+// ---- first pass, horizontal: source rows of the crop box -> tmp [B][tmp_rows][S][4] (uint8 RGBX), only the window's columns
 __global__ __launch_bounds__(256) void input_resize_h_kernel(const gan_input_job* __restrict__ jobs, const int32_t* __restrict__ tables,
                                                              uint8_t* __restrict__ tmp, int tmp_rows, int S) {
   const gan_input_job j = jobs[blockIdx.y];
   const int idx = blockIdx.x * 256 + threadIdx.x;
+  if (vertical_first(j)) {              // the vertical pass comes first: the window's rows of every crop column -> tmp [S][crop_w]
+    if (idx >= S * j.crop_w) return;    // crop_w < crop_h / 100 <= tmp_rows: fits the image's tmp_rows * S pixels
+    const int y = idx / j.crop_w, x = idx - y * j.crop_w;
+    const int32_t* b = tables + j.vb_off + 2 * (j.win_y + y);
+    const int32_t* k = tables + j.vk_off + (int64_t)(j.win_y + y) * j.vksize;
+    const int ymin = b[0], n = b[1];
+    const uint8_t* col = j.src + (int64_t)(j.crop_y + ymin) * j.src_stride + (int64_t)(j.crop_x + x) * 3;
+    int s0 = 1 << (PRECISION_BITS - 1), s1 = s0, s2 = s0;
+    for (int t = 0; t < n; ++t) {
+      const int w = k[t];
+      const uint8_t* p = col + (int64_t)t * j.src_stride;
+      s0 += p[0] * w; s1 += p[1] * w; s2 += p[2] * w;
+    }
+    uchar4 o = make_uchar4((unsigned char)clip8(s0 >> PRECISION_BITS), (unsigned char)clip8(s1 >> PRECISION_BITS), (unsigned char)clip8(s2 >> PRECISION_BITS), 255);
+    reinterpret_cast<uchar4*>(tmp)[(int64_t)blockIdx.y * tmp_rows * S + idx] = o;
+    return;
+  }
   if (idx >= j.crop_h * S) return;
   const int y = idx / S, x = idx - y * S;
   const int32_t* b = tables + j.hb_off + 2 * (j.win_x + x);
@@ -42,13 +64,28 @@ __global__ __launch_bounds__(256) void input_resize_h_kernel(const gan_input_job
   reinterpret_cast<uchar4*>(tmp)[((int64_t)blockIdx.y * tmp_rows + y) * S + x] = o;
 }
 
-// ---- vertical pass: tmp -> img [B][S][S][4], only the window's rows
+// ---- second pass, vertical: tmp -> img [B][S][S][4], only the window's rows
 __global__ __launch_bounds__(256) void input_resize_v_kernel(const gan_input_job* __restrict__ jobs, const int32_t* __restrict__ tables,
                                                              const uint8_t* __restrict__ tmp, int tmp_rows, int S, uint8_t* __restrict__ img) {
   const gan_input_job j = jobs[blockIdx.y];
   const int idx = blockIdx.x * 256 + threadIdx.x;
   if (idx >= S * S) return;
   const int y = idx / S, x = idx - y * S;
+  if (vertical_first(j)) {              // tmp holds the vertical pass [S][crop_w]: this is the horizontal one
+    const int32_t* b = tables + j.hb_off + 2 * (j.win_x + x);
+    const int32_t* k = tables + j.hk_off + (int64_t)(j.win_x + x) * j.hksize;
+    const int xmin = b[0], n = b[1];
+    const uchar4* row = reinterpret_cast<const uchar4*>(tmp) + (int64_t)blockIdx.y * tmp_rows * S + (int64_t)y * j.crop_w + xmin;
+    int s0 = 1 << (PRECISION_BITS - 1), s1 = s0, s2 = s0;
+    for (int t = 0; t < n; ++t) {
+      const int w = k[t];
+      const uchar4 p = row[t];
+      s0 += p.x * w; s1 += p.y * w; s2 += p.z * w;
+    }
+    uchar4 o = make_uchar4((unsigned char)clip8(s0 >> PRECISION_BITS), (unsigned char)clip8(s1 >> PRECISION_BITS), (unsigned char)clip8(s2 >> PRECISION_BITS), 255);
+    reinterpret_cast<uchar4*>(img)[((int64_t)blockIdx.y * S + y) * S + x] = o;
+    return;
+  }
   const int32_t* b = tables + j.vb_off + 2 * (j.win_y + y);
   const int32_t* k = tables + j.vk_off + (int64_t)(j.win_y + y) * j.vksize;
   const int ymin = b[0], n = b[1];
@@ -85,7 +122,11 @@ __global__ __launch_bounds__(1024) void input_gray_mean_kernel(const uint8_t* __
 
 // Blend.c ImagingBlend: float32 in1 + alpha * (in2 - in1); alpha in [0,1] truncates, otherwise clip first
 __device__ __forceinline__ int blend1(int in1, int in2, float alpha, bool inside) {
-  const float t = __fadd_rn((float)in1, __fmul_rn(alpha, (float)(in2 - in1)));
+  // Two roundings, as the C code's: plain operators, so that this file's `fp contract(off)` governs them.  __fmul_rn and __fadd_rn
+  // are header inlines compiled under the default contraction: a pair of them fuses into one v_fma_f32 (one rounding), which changes
+  // bytes for factors next to a fraction k / (in2 - in1), 1 + 2^-23 among them.
+  const float prod = alpha * (float)(in2 - in1);
+  const float t = (float)in1 + prod;
   if (inside) return (int)t & 255;
   return t <= 0.f ? 0 : (t >= 255.f ? 255 : (int)t);
 }
@@ -184,7 +225,8 @@ __global__ __launch_bounds__(256) void input_finish_u8_kernel(const gan_input_jo
 __device__ __forceinline__ uint32_t unit_to_u8(float v) {
   if (!(v >= -1.f)) v = -1.f;            // clamp(-1, 1); a NaN takes this branch and becomes byte 0
   if (v > 1.f) v = 1.f;
-  return (uint32_t)rintf(__fmul_rn(__fadd_rn(__fmul_rn(v, 0.5f), 0.5f), 255.f));      // rintf: half to even, as torch.round
+  const float unit = v * 0.5f + 0.5f;     // plain operators under this file's contract(off) (v * 0.5 is exact: one rounding either way)
+  return (uint32_t)rintf(unit * 255.f);   // rintf: half to even, as torch.round
 }
 
 template <typename T, bool PACKED>

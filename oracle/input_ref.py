@@ -75,14 +75,20 @@ def _resample_axis(img: np.ndarray, bounds: np.ndarray, kk: np.ndarray, axis: in
 
 def resize_bicubic(img: np.ndarray, out_h: int, out_w: int) -> np.ndarray:
     """Image.resize((out_w, out_h), BICUBIC) on an HWC uint8 image: horizontal pass, then vertical, uint8 in between; a pass
-    whose size does not change is skipped (Resample.c ImagingResample)."""
+    whose size does not change is skipped (Resample.c ImagingResample).  A source more than 100 times taller than wide that is being
+    lowered goes through the vertical pass first (Image.resize: `size[1] > size[0] * 100 and new_height < size[1]`;
+    tests/test_input_pipeline_edges_cpu.py pins both halves of the condition on Pillow itself)."""
     H, W = img.shape[:2]
     x = img
-    if out_w != W:
-        x = _resample_axis(x, *resize_coeffs(W, 0, W, out_w), axis=1)
-    if out_h != H:
-        x = _resample_axis(x, *resize_coeffs(H, 0, H, out_h), axis=0)
+    for axis in ((0, 1) if vertical_first(H, W, out_h) else (1, 0)):
+        i, o = ((H, out_h), (W, out_w))[axis]
+        if o != i:
+            x = _resample_axis(x, *resize_coeffs(i, 0, i, o), axis=axis)
     return x
+
+
+def vertical_first(H: int, W: int, out_h: int) -> bool:
+    return H > 100 * W and out_h < H
 
 
 # ------------------------------------------------------------------------------------------------ ImageEnhance / blend
