@@ -191,6 +191,11 @@ PROTOTYPES = {
     "gan_patch_loss": (C.c_int, [PV, C.c_int, f32, f32, vp, PV, vp]),
     "gan_l1_loss": (C.c_int, [PV, C.c_int, vp, f32, vp, vp, PV, vp, vp]),
     "gan_r1_reduce": (C.c_int, [PV, C.c_int, f32, vp, PV, vp, vp]),
+    "gan_palette_stats": (C.c_int, [PV, C.c_int, vp, vp, vp]),
+    "gan_palette_batch_mean": (C.c_int, [vp, C.c_int, vp, vp]),
+    "gan_palette_prior_update": (C.c_int, [vp, f32, vp, vp, C.c_int, f32, vp]),
+    "gan_palette_loss": (C.c_int, [vp, vp, C.c_int, f32, vp, vp, vp]),
+    "gan_palette_bwd": (C.c_int, [PV, C.c_int, vp, vp, vp, f32, PV, C.c_int, vp]),
     "gan_patchnce_ws_floats": (C.c_int64, [C.c_int, C.c_int, C.c_int]),
     "gan_patchnce_fwd": (C.c_int, [PV, PV, vp, C.c_int, C.c_int, f32, f32, vp, vp, vp]),
     "gan_patchnce_bwd": (C.c_int, [PV, vp, C.c_int, C.c_int, f32, f32, PV, vp, vp]),

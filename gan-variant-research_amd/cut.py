@@ -21,7 +21,7 @@ import torch.nn as nn
 
 from ._lib import ACT_NONE, BF16, F32, HALO_NONE, HALO_ZERO
 from .nets import DiscriminatorFamilyNet, GeneratorNet, SpectralNorm, fp8_switches
-from .runtime import ADAM_CHUNK, Ctx, HipOps, Program, View, cpad
+from .runtime import ADAM_CHUNK, Ctx, HipOps, Program, View, check_palette_size, cpad
 
 NCE_LAYERS_DEFAULT = (0, 4, 8, 12, 16)
 
@@ -466,6 +466,14 @@ class CutTrainer:
         self.world_size, self.pg = world_size, process_group
         self.average_losses = bool(average_losses) and process_group is not None
         lw = config["loss_weights"]
+        # Palette prior (csrc/palette.hip): active iff loss_weights.palette > 0 -- the reference's own `--set loss_weights.palette=0.5` example
+        # against its shipped YAML; the top-level `palette: {enabled: ...}` key is not read.  palette_prior.* defaults are that YAML's.
+        self.palette_w = float(lw.get("palette", 0) or 0)
+        self.palette = self.palette_w > 0
+        pp = config.get("palette_prior") or {}
+        self.pal_T, self.pal_ema, self.pal_decay = int(pp.get("low_freq_size", 32)), bool(pp.get("use_ema", True)), float(pp.get("ema_decay", 0.99))
+        if self.palette:
+            check_palette_size(self.pal_T)
         self.policy = config["diffaugment"].get("policy", ["color", "translation", "cutout"]) if config["diffaugment"].get("enable", False) else None
         self.aug = DiffAugment(self.policy) if self.policy is not None else None
         self.generator, self.discriminator = generator, discriminator
@@ -524,7 +532,14 @@ class CutTrainer:
         self.both = torch.zeros(2 * B, 3, S, S, dtype=torch.float32, device=self.device)   # photos | monets, one staging tensor
         self.photos, self.monets = self.both[:B], self.both[B:]
         self.fake_out = torch.zeros_like(self.photos)
-        self.losses = f32(max(16, len(LOSS_SLOTS) + len(SCALE_SLOTS) * (K - 1)))
+        self.losses = f32(max(16, len(LOSS_SLOTS) + len(SCALE_SLOTS) * (K - 1) + (1 if self.palette else 0)))
+        if self.palette:
+            # statistics of the fake and the Monet batch (cells kept for the backward), the batch means, the prior and its update count
+            n = B * self.pal_T * self.pal_T * 3
+            self.pal_cells_f, self.pal_cells_m, self.pal_stats_f, self.pal_stats_m = f32(n), f32(n), f32(B * 6), f32(B * 6)
+            self.pal_gstats, self.pal_batch, self.pal_prior = f32(B * 6), f32(8), f32(8)
+            self.pal_steps = torch.zeros(1, dtype=torch.int32, device=self.device)
+            self.pal_monets = self.ctx.view(B, S, S, 8, 0, dtype=F32)      # the fp32 batch as received, never a bf16 copy
         self.nce_hw = [(S >> (0 if i == 0 else 1 if i == 1 else 2 if i < 3 + nb else 1 if i == 3 + nb else 0)) ** 2 for i in self.nce_layers]
         # every per-step random draw (3 DiffAugment tables, PatchNCE ids) lives in ONE device block filled by ONE non-blocking copy
         # from pinned memory: seven small pageable copies would each stall the host until the stream drains (measured: 7 idle gaps
@@ -550,6 +565,18 @@ class CutTrainer:
         """Loss slot; d_real / d_fake / g_adv have one per discriminator scale (gan_patch_loss overwrites its slot)."""
         i = LOSS_SLOTS[name] if scale == 0 else len(LOSS_SLOTS) + len(SCALE_SLOTS) * (scale - 1) + SCALE_SLOTS.index(name)
         return self.losses[i:i + 1]
+
+    def _palette_slot_index(self) -> int:
+        """The palette loss lives behind the per-scale slots: no other slot moves."""
+        return len(LOSS_SLOTS) + len(SCALE_SLOTS) * (self.num_scales - 1)
+
+    def _palette_allreduce(self):
+        """Data parallel: the six batch means of the Monet statistics become their sum over the ranks (the prior update divides by the
+        rank count), so every rank holds the prior of the global batch.  Queued on the main stream, between the two small launches."""
+        if not (self.world_size > 1 or getattr(self, "force_allreduce", False)):
+            return
+        import torch.distributed as dist
+        dist.all_reduce(self.pal_batch, group=self.pg)
 
     def _scale_sum(self, v, name) -> float:
         return sum(v[LOSS_SLOTS[name] if s == 0 else len(LOSS_SLOTS) + len(SCALE_SLOTS) * (s - 1) + SCALE_SLOTS.index(name)]
@@ -676,6 +703,22 @@ class CutTrainer:
         pg0 = Program("G-step (features backward)")
         pg = Program("G-step")
         g_img, g_fold, g_img2 = g_adv_img, False, None
+        # ---- palette prior: statistics, prior update and loss on the main stream (they need nothing from the discriminator and run beside
+        # its step); the gradient is added to the adversarial image gradient at the head of the G-step, whatever consumes that next
+        ppal = None
+        if self.palette:
+            T, w = self.pal_T, self.palette_w
+            ppal = Program("palette")
+            ppal.add(ops.nchw_to_view(self.monets, 3, self.pal_monets, HALO_NONE))
+            ppal.add(ops.palette_stats(self.pal_monets, T, self.pal_cells_m, self.pal_stats_m))
+            ppal.add(ops.palette_batch_mean(self.pal_stats_m, B, self.pal_batch))
+            ppal.add(self._palette_allreduce)
+            ppal.add(ops.palette_prior_update(self.pal_batch, 1.0 / self.world_size, self.pal_prior, self.pal_steps, self.pal_ema, self.pal_decay))
+            ppal.add(ops.palette_stats(fake, T, self.pal_cells_f, self.pal_stats_f))
+            i = self._palette_slot_index()
+            ppal.add(ops.palette_loss(self.pal_stats_f, self.pal_prior, B, w, self.losses[i:i + 1], self.pal_gstats))
+            assert (g_adv_img.B, g_adv_img.H, g_adv_img.W, g_adv_img.C, g_adv_img.dtype) == (fake.B, fake.H, fake.W, fake.C, fake.dtype)
+            pg.add(ops.palette_bwd(fake, T, self.pal_cells_f, self.pal_stats_f, self.pal_gstats, w, g_adv_img, True))
         if self.nce_layers:
             pg0.add(self.p2.bwd_program(hooks=hooks, accumulate=True, need_input_grad=True))
             g_img, g_fold, g_img2 = self.p2.g_input, True, g_adv_img
@@ -703,7 +746,7 @@ class CutTrainer:
         pfo.add(ops.view_to_nchw(fake, 3, self.fake_out))
         return {"p1": p1, "p3": p3, "photos_v": photos_v, "prog_gfwd": prog_gfwd, "prog_d_compute": pd, "prog_g_features": pf,
                 "prog_g_adversarial": pa, "prog_g_features_bwd": pg0, "prog_g_compute": pg,
-                "prog_g_identity": pi, "prog_fake_out": pfo}
+                "prog_g_identity": pi, "prog_fake_out": pfo, "prog_palette": ppal}
 
     def _build_updates(self):
         """R1 and the optimiser updates with their operand-copy refresh: built after every mode planned so far, because a
@@ -928,6 +971,10 @@ class CutTrainer:
         self.losses[LOSS_SLOTS["idw"]] = idw
         self.prog_gfwd.run()
         self._ev_fake_ready()                       # main: G(photos) done   -> the discriminator's stream may start
+        if self.prog_palette is not None:
+            # main stream, beside the discriminator's step.  Queued first: data parallel, its six-float all-reduce then stands in front of the
+            # discriminator's gradient all-reduce instead of behind it.  (Queued in front of _ev_adv_wait instead it measured no faster.)
+            self.prog_palette.run()
         # ---- discriminator's stream: D step, its all-reduce and update, lazy R1, then the adversarial gradient of the fake image
         self.prog_d_compute.run()
         self._allreduce(self.opt_D)
@@ -977,6 +1024,9 @@ class CutTrainer:
         out = {"d_loss": d_loss, "g_adv": g_adv / lw["adv"] if lw["adv"] != 0 else 0.0, "nce": v[4] / lw["patchnce"] if lw["patchnce"] > 0 else 0.0,
                "identity": v[5] if idw > 0 else 0.0, "r1": v[2] if do_r1 else 0.0, "identity_weight": idw}
         out["g_loss"] = lw["adv"] * out["g_adv"] + lw["patchnce"] * out["nce"] + idw * out["identity"]
+        if self.palette:                 # the key exists only when the term is active: every other configuration's dict is what it was
+            out["palette"] = v[self._palette_slot_index()] / self.palette_w
+            out["g_loss"] += self.palette_w * out["palette"]
         if any(not math.isfinite(x) for k, x in out.items() if k != "identity_weight"):
             raise ValueError(f"NaN loss detected at step {step}. Training stopped to prevent corruption.")   # train_cutpp.py:326-329
         return out
@@ -1005,10 +1055,14 @@ class CutTrainer:
         """The reference's checkpoint dict: generator / discriminator state_dicts (reference keys), torch.optim.Adam-layout optimiser
         states, {'decay','shadow'} EMA -- loadable by the reference's load_checkpoint and vice versa."""
         self._device_sync()              # the discriminator's state is written on its own stream
-        return {"step": step, "generator": {k: v.clone() for k, v in self.generator.state_dict().items()},
-                "discriminator": {k: v.clone() for k, v in self.discriminator.state_dict().items()},
-                "opt_G": _adam_state_dict(self.opt_G), "opt_D": _adam_state_dict(self.opt_D), "metrics": metrics or {}, "config": self.config,
-                "ema_G": {"decay": self.opt_G.ema_decay, "shadow": {k: v.clone() for k, v in self.opt_G.shadow.items()}}, "scaler": {}}
+        ck = {"step": step, "generator": {k: v.clone() for k, v in self.generator.state_dict().items()},
+              "discriminator": {k: v.clone() for k, v in self.discriminator.state_dict().items()},
+              "opt_G": _adam_state_dict(self.opt_G), "opt_D": _adam_state_dict(self.opt_D), "metrics": metrics or {}, "config": self.config,
+              "ema_G": {"decay": self.opt_G.ema_decay, "shadow": {k: v.clone() for k, v in self.opt_G.shadow.items()}}, "scaler": {}}
+        if self.palette:                 # a key of its own: the reference's load_checkpoint reads named keys only
+            pr = self.pal_prior[:6].view(3, 2)
+            ck["palette_prior"] = {"mean": pr[:, 0].clone(), "std": pr[:, 1].clone(), "steps": int(self.pal_steps)}
+        return ck
 
     def save_checkpoint(self, path: str, step: int, metrics: Optional[dict] = None):
         import pathlib
@@ -1032,6 +1086,12 @@ class CutTrainer:
         if "ema_G" in ck and self.opt_G.flat_ema is not None:
             for k, v in ck["ema_G"]["shadow"].items():
                 self.opt_G.shadow[k].copy_(v)
+        if self.palette:                 # without the key the prior starts afresh (its first update sets it)
+            pp = ck.get("palette_prior")
+            self.pal_prior.zero_()
+            self.pal_steps.fill_(0 if pp is None else int(pp["steps"]))
+            if pp is not None:
+                self.pal_prior[:6].view(3, 2).copy_(torch.stack([pp["mean"].reshape(3), pp["std"].reshape(3)], 1))
         self._device_sync()
         self.G.repack_program().run()
         self.D.repack_program().run()

@@ -207,6 +207,90 @@ def compute_patchnce_loss(generator, src_images, tgt_images, nce_layers, tempera
     return fn(src_feats, tgt_feats)
 
 
+# ------------------------------------------------------------------------------------------------ palette prior
+class _PalettePlan(_Plan):
+    """Statistics, batch mean / prior update and loss + image gradient of csrc/palette.hip for one (shape, T, EMA setting)."""
+
+    def __init__(self, shape, device, T, use_ema, decay):
+        super().__init__(device)
+        B, C, H, W = shape
+        assert C == 3, "the palette prior reads RGB images (B,3,H,W)"
+        ops, ctx = self.ops, self.ctx
+        self.x = torch.zeros(shape, dtype=torch.float32, device=device)
+        self.g = torch.zeros(shape, dtype=torch.float32, device=device)
+        v, gv = ctx.view(B, H, W, 8, 0), ctx.view(B, H, W, 8, 0)
+        cells = ctx.f32(B * T * T * 3)
+        self.stats, gstats, batch = ctx.f32(B * 6), ctx.f32(B * 6), ctx.f32(8)
+        self.prior, self.loss = ctx.f32(8), ctx.f32(1)
+        self.steps = torch.zeros(1, dtype=torch.int32, device=device)
+        self.fwd = Program("palette.stats")
+        self.fwd.add(ops.nchw_to_view(self.x, 3, v, HALO_NONE))
+        self.fwd.add(ops.palette_stats(v, T, cells, self.stats))
+        self.update = Program("palette.prior")                       # after fwd on the Monet batch
+        self.update.add(ops.palette_batch_mean(self.stats, B, batch))
+        self.update.add(ops.palette_prior_update(batch, 1.0, self.prior, self.steps, use_ema, decay))
+        self.lossbwd = Program("palette.loss")                       # after fwd on the fake batch
+        self.lossbwd.add(ops.palette_loss(self.stats, self.prior, B, 1.0, self.loss, gstats))
+        self.lossbwd.add(ops.palette_bwd(v, T, cells, self.stats, gstats, 1.0, gv, False))
+        self.lossbwd.add(ops.view_to_nchw(gv, 3, self.g))
+
+
+def _palette_plan(shape, device, T, use_ema=True, decay=0.99) -> _PalettePlan:
+    from .runtime import check_palette_size
+    check_palette_size(T)
+    key = ("palette", tuple(shape), device, int(T), bool(use_ema), float(decay))
+    return _plan(key, lambda: _PalettePlan(tuple(shape), device, int(T), bool(use_ema), float(decay)))
+
+
+def low_freq_lab_stats(images: torch.Tensor, target_size: int = 32):
+    """get_low_freq_stats(rgb_to_lab(denormalize(images)), target_size) of GAN_Variant1/dataio/transforms.py:52-119 in one pass:
+    (mean, std), each (B, 3), of the Lab image pooled to target_size x target_size.  Forward only."""
+    from . import ops_library  # noqa: F401
+    return torch.ops.mi355x_gan.palette_stats(images, int(target_size))
+
+
+class PalettePriorLoss(nn.Module):
+    """mean over images and channels of (|mean_fake - mean_prior| + |std_fake - std_prior|) / 100 on the low-frequency Lab statistics,
+    against a prior that follows the Monet batches (`use_ema`: prior = decay * prior + (1 - decay) * batch, the first call sets it;
+    otherwise prior = batch).  The statistic is the reference's (transforms.py:52-119); the reference's own loss file was deleted, so
+    this formula is the project's.  forward(fake, monets) updates the prior, then returns the scalar with gradient to `fake`; the prior
+    is a constant for the gradient.  `prior` is a (3, 2) buffer of (mean, std) per Lab channel, `steps` the number of updates."""
+
+    def __init__(self, low_freq_size: int = 32, use_ema: bool = True, ema_decay: float = 0.99):
+        super().__init__()
+        from .runtime import check_palette_size
+        check_palette_size(low_freq_size)
+        self.low_freq_size, self.use_ema, self.ema_decay = int(low_freq_size), bool(use_ema), float(ema_decay)
+        self.register_buffer("prior", torch.zeros(3, 2))
+        self.register_buffer("steps", torch.zeros(1, dtype=torch.int32))
+
+    @property
+    def prior_mean(self):
+        return self.prior[:, 0]
+
+    @property
+    def prior_std(self):
+        return self.prior[:, 1]
+
+    @torch.no_grad()
+    def update_prior(self, monets: torch.Tensor):
+        x = monets.detach().float().contiguous()
+        if self.prior.device != x.device:
+            self.to(x.device)
+        p = _palette_plan(x.shape, x.device, self.low_freq_size, self.use_ema, self.ema_decay)
+        p.x.copy_(x)
+        p.prior[:6].copy_(self.prior.reshape(-1)); p.steps.copy_(self.steps)
+        p.fwd.run()
+        p.update.run()
+        self.prior.copy_(p.prior[:6].view(3, 2)); self.steps.copy_(p.steps)
+
+    def forward(self, fake: torch.Tensor, monets: torch.Tensor) -> torch.Tensor:
+        self.update_prior(monets)
+        from . import ops_library  # noqa: F401
+        loss, _ = torch.ops.mi355x_gan.palette_prior_fwd(fake, self.prior.detach().clone(), self.low_freq_size)
+        return loss
+
+
 # ------------------------------------------------------------------------------------------------ DiffAugment (a11)
 class _AugPlan(_Plan):
     def __init__(self, shape, device):

@@ -16,11 +16,26 @@ import torch
 
 from .cut import identity_weight_at
 from .autograd import r1_regularization
-from .losses import PatchNCELoss, discriminator_hinge_loss, generator_hinge_loss, identity_loss
+from .losses import PalettePriorLoss, PatchNCELoss, discriminator_hinge_loss, generator_hinge_loss, identity_loss
+
+_PALETTE = {}      # id(generator) -> (generator, PalettePriorLoss): the prior of a run whose caller passes no module of its own
 
 
-def train_step(step, photos, monets, generator, discriminator, opt_G, opt_D, ema_G, amp_ctx, diffaugment, config, device, rnd: Optional[dict] = None):
+def palette_prior_for(generator, config) -> PalettePriorLoss:
+    """The run's PalettePriorLoss, built from `palette_prior.*` (the shipped YAML's defaults when the block is absent)."""
+    ent = _PALETTE.get(id(generator))
+    if ent is None or ent[0] is not generator:
+        pp = config.get("palette_prior") or {}
+        ent = _PALETTE[id(generator)] = (generator, PalettePriorLoss(pp.get("low_freq_size", 32), pp.get("use_ema", True), pp.get("ema_decay", 0.99)))
+    return ent[1]
+
+
+def train_step(step, photos, monets, generator, discriminator, opt_G, opt_D, ema_G, amp_ctx, diffaugment, config, device, rnd: Optional[dict] = None,
+               palette_prior: Optional[PalettePriorLoss] = None):
+    """palette_prior (optional, not in the reference's signature): the module that holds the palette prior when `loss_weights.palette` > 0
+    (default: one per generator, kept here).  The loss dict gains `palette` only then, as in cut.CutTrainer."""
     lw = config["loss_weights"]
+    palette_w = float(lw.get("palette", 0) or 0)
     identity_weight = identity_weight_at(step, config)                                    # :224-228
     rnd = rnd or {}
 
@@ -60,12 +75,18 @@ def train_step(step, photos, monets, generator, discriminator, opt_G, opt_D, ema
         if identity_weight > 0:
             idt_loss = identity_loss(generator, monets)
         g_loss = lw["adv"] * g_adv_loss + lw["patchnce"] * nce_loss + identity_weight * idt_loss
+        if palette_w > 0:
+            fn = palette_prior if palette_prior is not None else palette_prior_for(generator, config)
+            palette_loss = fn(fake, monets)
+            g_loss = g_loss + palette_w * palette_loss
     amp_ctx.scale_backward(g_loss)
     amp_ctx.step_optimizer(opt_G, max_grad_norm=config.get("grad_clip_g", 10.0))
     if ema_G is not None:
         ema_G.update()
     losses = {"d_loss": d_loss.item(), "g_loss": g_loss.item(), "g_adv": g_adv_loss.item(), "nce": nce_loss.item(), "identity": idt_loss.item(),
               "r1": r1_loss.item(), "identity_weight": identity_weight}
+    if palette_w > 0:
+        losses["palette"] = palette_loss.item()
     if any(not math.isfinite(v) for k, v in losses.items() if k != "identity_weight"):
         raise ValueError(f"NaN loss detected at step {step}. Training stopped to prevent corruption.")   # :325-329
     return losses

@@ -154,6 +154,9 @@ _LIB.define("patchnce_bwd(Tensor saved, Tensor grad_loss) -> Tensor")
 _LIB.define("diffaugment_fwd(Tensor x, Tensor params) -> Tensor")
 _LIB.define("diffaugment_bwd(Tensor gy, Tensor params) -> Tensor")
 _LIB.define("allreduce_bucket_(Tensor(a!) flat, str group) -> Tensor(a!)")
+_LIB.define("palette_stats(Tensor images, int target_size) -> (Tensor, Tensor)")
+_LIB.define("palette_prior_fwd(Tensor fake, Tensor prior, int target_size) -> (Tensor, Tensor)")
+_LIB.define("palette_prior_bwd(Tensor saved, Tensor grad_loss) -> Tensor")
 
 
 def _conv_fwd(x, w, b, stride, pad, pad_mode, act, transposed=False):
@@ -368,6 +371,32 @@ _LIB.impl("diffaugment_bwd", lambda gy, prm: _aug_run(_f(gy), prm, True), _IMPL)
 _LIB.impl("allreduce_bucket_", _allreduce_bucket, _IMPL)
 
 
+# ---- palette prior (dataio/transforms.py:52-119 under a loss of this project's, csrc/palette.hip): like PatchNCE, the forward op hands the
+#      image gradient for a unit upstream gradient to its backward op as `saved`
+def _palette_stats(x, T):
+    from . import losses as LS
+    p = LS._palette_plan(x.shape, x.device, T)
+    p.x.copy_(x)
+    p.fwd.run()
+    st = p.stats[:x.shape[0] * 6].view(x.shape[0], 3, 2)
+    return st[..., 0].clone(), st[..., 1].clone()
+
+
+def _palette_prior_fwd(x, prior, T):
+    from . import losses as LS
+    p = LS._palette_plan(x.shape, x.device, T)
+    p.x.copy_(x)
+    p.prior[:6].copy_(prior.reshape(-1))
+    p.fwd.run()
+    p.lossbwd.run()
+    return p.loss.clone().reshape(()), p.g.clone()
+
+
+_LIB.impl("palette_stats", lambda images, target_size: _palette_stats(_f(images), target_size), _IMPL)
+_LIB.impl("palette_prior_fwd", lambda fake, prior, target_size: _palette_prior_fwd(_f(fake), _f(prior), target_size), _IMPL)
+_LIB.impl("palette_prior_bwd", lambda saved, g: saved * g, _IMPL)
+
+
 # ------------------------------------------------------------------------------------------------ autograd formulas
 def _act_chain(ctx_act, y, g):
     """dL/d(pre-activation) from dL/dy: the fused epilogue activation's derivative, through its output."""
@@ -437,6 +466,9 @@ def _aug_setup(ctx, inputs, output):
 
 
 torch.library.register_autograd("mi355x_gan::patchnce_fwd", _nce_backward, setup_context=_nce_setup)
+# the prior is a constant for the gradient
+torch.library.register_autograd("mi355x_gan::palette_prior_fwd", lambda ctx, g_loss, g_saved: (torch.ops.mi355x_gan.palette_prior_bwd(ctx.saved_tensors[0], g_loss), None, None),
+                                setup_context=_nce_setup)
 torch.library.register_autograd("mi355x_gan::diffaugment_fwd", lambda ctx, g: (torch.ops.mi355x_gan.diffaugment_bwd(g.contiguous(), ctx.saved_tensors[0]), None),
                                 setup_context=_aug_setup)
 torch.library.register_autograd("mi355x_gan::replication_pad2d", lambda ctx, g: (torch.ops.mi355x_gan.replication_pad2d_bwd(g.contiguous(), ctx.pad), None),

@@ -22,6 +22,12 @@ IN_WS_CHUNKS = 96
 ADAM_CHUNK = 16384
 
 
+def check_palette_size(T):
+    """palette_prior.low_freq_size: the unbiased standard deviation over T*T cells needs T >= 2 (torch gives NaN for one cell)."""
+    if int(T) != T or not 2 <= int(T) <= 1024:
+        raise ValueError(f"palette prior: low_freq_size must be an integer in [2, 1024], got {T!r}")
+
+
 def torch_dtype(code: int):
     return torch.float32 if code == F32 else torch.uint8 if code == FP8 else torch.bfloat16      # FP8: raw e4m3 bytes
 
@@ -896,6 +902,30 @@ class HipOps:
 
     def r1_reduce(self, g: View, Cr, scale, loss, u: Optional[View], ws) -> Op:
         return self._call("gan_r1_reduce", self._v(g), Cr, C.c_float(scale), self._p(loss), self._v(u), self._p(ws), self._s())
+
+    # ---- palette prior (csrc/palette.hip): cells [B][T*T][3], stats / gstats [B][3][2], batch / prior [3][2] fp32, steps int32 [1]
+    def palette_stats(self, x: View, T, cells, stats) -> Op:
+        check_palette_size(T)
+        assert cells.numel() >= x.B * T * T * 3 and stats.numel() >= x.B * 6
+        return self._call("gan_palette_stats", self._v(x), int(T), self._p(cells), self._p(stats), self._s())
+
+    def palette_batch_mean(self, stats, B, batch) -> Op:
+        assert stats.numel() >= B * 6 and batch.numel() >= 6
+        return self._call("gan_palette_batch_mean", self._p(stats), int(B), self._p(batch), self._s())
+
+    def palette_prior_update(self, batch, batch_scale, prior, steps, use_ema, decay) -> Op:
+        assert steps.dtype == torch.int32 and prior.numel() >= 6 and batch.numel() >= 6
+        return self._call("gan_palette_prior_update", self._p(batch), C.c_float(batch_scale), self._p(prior), self._p(steps), int(bool(use_ema)),
+                          C.c_float(decay), self._s())
+
+    def palette_loss(self, stats, prior, B, scale, loss, gstats) -> Op:
+        assert stats.numel() >= B * 6 and (gstats is None or gstats.numel() >= B * 6)
+        return self._call("gan_palette_loss", self._p(stats), self._p(prior), int(B), C.c_float(scale), self._p(loss), self._p(gstats), self._s())
+
+    def palette_bwd(self, x: View, T, cells, stats, gstats, scale, gx: View, accumulate) -> Op:
+        check_palette_size(T)
+        return self._call("gan_palette_bwd", self._v(x), int(T), self._p(cells), self._p(stats), self._p(gstats), C.c_float(scale), self._v(gx),
+                          int(bool(accumulate)), self._s())
 
     def patchnce_ws_floats(self, B, P, Cc) -> int:
         return int(self.lib.gan_patchnce_ws_floats(B, P, Cc))

@@ -785,6 +785,34 @@ int gan_l1_loss(const gan_view* x, int C, const float* target_nchw, float scale,
 /* r1 = (1/B) sum_b sum_chw g^2 (train_cutpp.py:201) and u = scale * 2 g / B into `u` (interior) */
 int gan_r1_reduce(const gan_view* g, int C, float scale, float* loss, const gan_view* u, float* ws, void* stream);
 
+/* ---- palette prior: low-frequency CIE-Lab statistics (GAN_Variant1/dataio/transforms.py:52-54 denormalize, :57-96 rgb_to_lab,
+ *      :99-119 get_low_freq_stats), a loss against a running prior and its gradient wrt the image.  The reference's file that combined
+ *      them (losses/palette_prior_lab.py) is gone; the loss below is this project's statement (DESIGN.md "Palette prior").
+ *      x: fp32 or bf16 view, C = 8, channels 0..2 real, values in [-1, 1] (clamped like the reference); any halo.  T = low_freq_size
+ *      in [2, 1024] (T = 1: error; the unbiased std of one cell is NaN).
+ *      gan_palette_stats: cells[B][T*T][3] fp32 = adaptive_avg_pool2d of Lab to T x T (cell i covers rows floor(i H / T) ..
+ *      ceil((i + 1) H / T) - 1, columns likewise), then stats[B][3][2] fp32 = (mean of the T*T cells, their unbiased std) per image and
+ *      channel (L, a, b), taken in two fp64 passes over the stored cells.  Two launches.
+ *      gan_palette_batch_mean: batch[3][2] = mean over the B images of stats.
+ *      gan_palette_prior_update: v = batch * batch_scale (batch_scale = 1 / ranks after a summing all-reduce of `batch`);
+ *      prior[3][2] = v if !use_ema or *steps == 0, else decay * prior + (1 - decay) * v; then ++*steps (device int32).
+ *      gan_palette_loss: *loss = scale / (3B) * sum_{b,c} (|m - m_prior| + |s - s_prior|) / 100 (overwritten);
+ *      gstats[B][3][2] (may be NULL) = the derivative of the UNSCALED loss wrt stats, sign(0) = 0.
+ *      gan_palette_bwd: channels 0..2 of gx's interior pixels = (accumulate: +=) scale * dLoss/dx, with cells / stats / gstats of the
+ *      calls above for the same x: per cell gm / N + gs (cell - m) / ((N - 1) s) (the gs term is 0 where s == 0), spread over the
+ *      cell's pixels, then the transposed Jacobian of the Lab chain recomputed from x -- at every `where` the derivative of the branch the
+ *      forward took, clamp passing the gradient on [0, 1] inclusive.  Every value is finite for every finite x.  accumulate = 0 writes
+ *      channels 3..7 of interior pixels as 0; accumulate = 1 leaves their bits.  Halos of gx are never written.
+ *      Halos and pad channels of x are never read: a NaN there changes nothing.  A NaN in a real channel makes that image's cells and
+ *      stats, and through them *loss, NaN; the statistics and gradients of the other images are unaffected.
+ *      Fixed-order reductions (fp32 per lane, fp64 across lanes), no atomics: repeated calls repeat their bits. */
+int gan_palette_stats(const gan_view* x, int T, float* cells, float* stats, void* stream);
+int gan_palette_batch_mean(const float* stats, int B, float* batch, void* stream);
+int gan_palette_prior_update(const float* batch, float batch_scale, float* prior, int32_t* steps, int use_ema, float decay, void* stream);
+int gan_palette_loss(const float* stats, const float* prior, int B, float scale, float* loss, float* gstats, void* stream);
+int gan_palette_bwd(const gan_view* x, int T, const float* cells, const float* stats, const float* gstats, float scale,
+                    const gan_view* gx, int accumulate, void* stream);
+
 /* ---- PatchNCE (GAN_Variant1/losses/patchnce_cut.py:42-110) for one feature layer.
  *      ids: device int32 [P] positions in [0,H*W).  ws: fp32 workspace >= gan_patchnce_ws_floats(B,P,C).
  *      fwd: *loss += weight * mean_b CE.  bwd: grad rows of tgt (scaled by weight) are ADDED into `gtgt`
