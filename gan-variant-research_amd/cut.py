@@ -21,7 +21,7 @@ import torch.nn as nn
 
 from ._lib import ACT_NONE, BF16, F32, HALO_NONE, HALO_ZERO
 from .nets import DiscriminatorFamilyNet, GeneratorNet, SpectralNorm, fp8_switches
-from .runtime import ADAM_CHUNK, Ctx, HipOps, Program, View, check_palette_size, cpad
+from .runtime import AdamPlan, Ctx, HipOps, Program, View, check_palette_size, check_weight_decay, cpad
 
 NCE_LAYERS_DEFAULT = (0, 4, 8, 12, 16)
 
@@ -293,13 +293,13 @@ class AMPContext:
 class FusedAdam:
     """get_optimizer's torch.optim.Adam (sched_optim.py:5-27) over a flat parameter block, fused with clip_grad_norm_
     and EMA.update (amp_utils.py:29-41, io_ckpt.py:23-29) in one multi-tensor launch.  weight_decay is torch.optim.Adam's (L2, added to
-    the clipped gradient); decoupled makes it AdamW's.  With weight_decay 0 the launch is gan_adam_step, as it always was."""
+    the clipped gradient); decoupled makes it AdamW's.  With weight_decay 0 the launch is gan_adam_step, as it always was.  Chunks, workspace,
+    tables, learning rate and launches are a runtime.AdamPlan's (`plan`); its tensors are aliased here under the names they always had."""
 
     def __init__(self, ctx: Ctx, names: List[str], shapes: List[torch.Size], init: Dict[str, torch.Tensor], lr=2e-4, betas=(0.5, 0.999),
                  eps=1e-8, weight_decay=0.0, ema_decay: Optional[float] = None, decoupled: bool = False):
-        if not weight_decay >= 0.0:
-            raise ValueError(f"Invalid weight_decay value: {weight_decay}")
-        self.ctx, self.names, self.lr, self.betas, self.eps, self.ema_decay = ctx, names, lr, betas, eps, ema_decay
+        check_weight_decay(weight_decay)
+        self.ctx, self.names, self.betas, self.eps, self.ema_decay = ctx, names, betas, eps, ema_decay
         self.weight_decay, self.decoupled = float(weight_decay), bool(decoupled)
         sizes = [int(np.prod(s)) for s in shapes]
         self.offsets = np.concatenate([[0], np.cumsum([(n + 3) // 4 * 4 for n in sizes])]).astype(np.int64)  # 16-byte aligned slices
@@ -321,45 +321,35 @@ class FusedAdam:
                 self.shadow[n] = self.flat_ema[o:o + sz].view(shp)
                 self.shadow[n].copy_(init[n])
         self.sizes = sizes
-        ct, co = [], []
-        for i, sz in enumerate(sizes):
-            for off in range(0, sz, ADAM_CHUNK):
-                ct.append(i)
-                co.append(off)
-        self.nchunks = len(ct)
-        self.chunk_tensor = torch.tensor(ct, dtype=torch.int32, device=dev)
-        self.chunk_off = torch.tensor(co, dtype=torch.int64, device=dev)
-        self.norm_out = torch.zeros(4, dtype=torch.float32, device=dev)
-        self.ws = torch.zeros(self.nchunks + 16, dtype=torch.float32, device=dev)
         self._tables = {}
-        # the learning rate lives in one device float that the prebuilt launches read (gan_adam_step lr_dev): a scheduler
-        # (Basic_GAN/src/train.py:54-58,125: LambdaLR) rewrites it between epochs without rebuilding any program
         self.base_lr = float(lr)
-        self.lr_dev = torch.full((1,), float(lr), dtype=torch.float32, device=dev)
+        self.plan = AdamPlan(ctx, self._entries(()), lr)
+        self.nchunks, self.chunk_tensor, self.chunk_off = self.plan.nchunks, self.plan.chunk_tensor, self.plan.chunk_off
+        self.norm_out, self.ws, self.lr_dev = self.plan.norm_out, self.plan.ws, self.plan.lr_dev
+
+    @property
+    def lr(self) -> float:
+        return self.plan.lr
 
     def set_lr(self, lr: float):
         """What LambdaLR.step() does to param_groups[0]['lr'] (train.py:125): takes effect with the next step."""
-        self.lr = float(lr)
-        self.lr_dev.fill_(float(lr))
+        self.plan.set_lr(lr)
+
+    def _entries(self, skip):
+        cut = lambda flat, i: None if flat is None else flat[int(self.offsets[i]):int(self.offsets[i]) + self.sizes[i]]
+        return [{"p": cut(self.flat_p, i), "g": None if n in skip else cut(self.flat_g, i), "m": cut(self.flat_m, i), "v": cut(self.flat_v, i),
+                 "ema": cut(self.flat_ema, i), "step": self.steps[i:i + 1]} for i, n in enumerate(self.names)]
 
     def table(self, skip: Sequence[str] = ()) -> torch.Tensor:
         key = tuple(sorted(skip))
         if key not in self._tables:
-            ents = []
-            for i, n in enumerate(self.names):
-                o, sz = int(self.offsets[i]), self.sizes[i]
-                ents.append({"p": self.flat_p[o:o + sz], "g": None if n in skip else self.flat_g[o:o + sz], "m": self.flat_m[o:o + sz],
-                             "v": self.flat_v[o:o + sz], "ema": self.flat_ema[o:o + sz] if self.flat_ema is not None else None,
-                             "step": self.steps[i:i + 1]})
-            self._tables[key] = self.ctx.ops.make_adam_table(ents)
+            self._tables[key] = self.plan.table(self._entries(key) if key else None)
         return self._tables[key]
 
     def step_op(self, max_norm: Optional[float], grad_scale: float = 1.0, skip: Sequence[str] = ()):
-        args = (self.table(skip), len(self.names), self.chunk_tensor, self.chunk_off, self.nchunks, self.lr, self.betas[0], self.betas[1], self.eps,
-                max_norm if max_norm is not None else 0.0, grad_scale, self.ema_decay if self.ema_decay is not None else 0.0, self.norm_out, self.ws)
-        if self.weight_decay == 0.0:
-            return self.ctx.ops.adam_step(*args, lr_dev=self.lr_dev)
-        return self.ctx.ops.adam_step_wd(*args, self.weight_decay, self.decoupled, lr_dev=self.lr_dev)
+        return self.plan.step_op(self.betas[0], self.betas[1], self.eps, max_norm if max_norm is not None else 0.0, grad_scale,
+                                 self.ema_decay if self.ema_decay is not None else 0.0, self.weight_decay, self.decoupled, table=self.table(skip),
+                                 cached=False)      # the trainers build their update programs again for every mode they plan
 
 
 def _adam_state_dict(opt: "FusedAdam", with_initial_lr: bool = False) -> dict:

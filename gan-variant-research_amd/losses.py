@@ -16,17 +16,9 @@ import torch.nn as nn
 from . import autograd as AG
 from ._lib import F32, HALO_NONE, HALO_ZERO
 from .cut import DiffAugment as _DiffAugmentSampler
-from .runtime import Program, cpad
+from .runtime import Program, cached_plan, cpad
 
 _PLANS: Dict[tuple, object] = {}
-
-
-def _plan(key, make):
-    key = key + (torch.cuda.current_stream().cuda_stream if torch.cuda.is_available() else 0,)      # see ops_library._stream_key
-    p = _PLANS.get(key)
-    if p is None:
-        p = _PLANS[key] = make()
-    return p
 
 
 class _Plan:
@@ -57,7 +49,7 @@ class _PatchLossPlan(_Plan):
 class _PatchLossFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, mode, target):
-        p = _plan(("patch_loss", tuple(x.shape), x.device, mode, float(target)), lambda: _PatchLossPlan(tuple(x.shape), x.device, mode, target))
+        p = cached_plan(_PLANS, ("patch_loss", tuple(x.shape), x.device, mode, float(target)), x.device, lambda: _PatchLossPlan(tuple(x.shape), x.device, mode, target))
         p.x.copy_(x)
         p.prog.run()
         ctx.save_for_backward(p.g.clone())
@@ -124,7 +116,7 @@ class _L1Plan(_Plan):
 class _L1Fn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, target):
-        p = _plan(("l1", tuple(x.shape), x.device), lambda: _L1Plan(tuple(x.shape), x.device))
+        p = cached_plan(_PLANS, ("l1", tuple(x.shape), x.device), x.device, lambda: _L1Plan(tuple(x.shape), x.device))
         p.x.copy_(x); p.t.copy_(target)
         p.prog.run()
         ctx.save_for_backward(p.g.clone())
@@ -239,7 +231,7 @@ def _palette_plan(shape, device, T, use_ema=True, decay=0.99) -> _PalettePlan:
     from .runtime import check_palette_size
     check_palette_size(T)
     key = ("palette", tuple(shape), device, int(T), bool(use_ema), float(decay))
-    return _plan(key, lambda: _PalettePlan(tuple(shape), device, int(T), bool(use_ema), float(decay)))
+    return cached_plan(_PLANS, key, device, lambda: _PalettePlan(tuple(shape), device, int(T), bool(use_ema), float(decay)))
 
 
 def low_freq_lab_stats(images: torch.Tensor, target_size: int = 32):

@@ -28,7 +28,7 @@ import torch.nn as nn
 from . import autograd as AG
 from ._lib import ACT_NONE, ACT_RELU, ACT_LRELU, ACT_TANH, BF16, F32, HALO_NONE, HALO_REFLECT, HALO_REPLICATE, HALO_ZERO
 from .convplan import ConvLayer
-from .runtime import IN_WS_CHUNKS, Program, View, cpad
+from .runtime import IN_WS_CHUNKS, Program, View, cached_plan, cpad
 
 PAD_ZERO, PAD_REFLECT = 0, 1
 _COMPUTE_DTYPE = [F32]
@@ -40,21 +40,6 @@ def set_compute_dtype(dtype: int):
     """F32 (exact fp32 MFMA, the parity mode; default) or BF16 (bf16 operands, fp32 accumulation) for the ops of this library."""
     assert dtype in (F32, BF16)
     _COMPUTE_DTYPE[0] = dtype
-
-
-def _stream_key() -> int:
-    """A plan's launches are bound to the HIP stream that was current when it was built (raw handle in the prebuilt calls) while its
-    staging copies run on whatever stream is current at the call: the current stream is therefore part of every plan key, so a caller
-    working on another stream (a prefetch stream, `with torch.cuda.stream(s)`) gets a plan of its own instead of an unordered pair."""
-    return torch.cuda.current_stream().cuda_stream if torch.cuda.is_available() else 0
-
-
-def _plan(key, make):
-    key = key + (_stream_key(),)
-    p = _PLANS.get(key)
-    if p is None:
-        p = _PLANS[key] = make()
-    return p
 
 
 def _dev_key(t: torch.Tensor):
@@ -124,7 +109,7 @@ class _ConvPlan:
 
 def _conv_plan(x_shape, w, b, stride, pad, pad_mode, act, transposed) -> _ConvPlan:
     key = ("conv", _dev_key(w), _COMPUTE_DTYPE[0], tuple(x_shape), tuple(w.shape), b is not None, stride, pad, pad_mode, act, transposed)
-    return _plan(key, lambda: _ConvPlan(w.device, _COMPUTE_DTYPE[0], tuple(x_shape), tuple(w.shape), b is not None, stride, pad, pad_mode, act, transposed))
+    return cached_plan(_PLANS, key, w.device, lambda: _ConvPlan(w.device, _COMPUTE_DTYPE[0], tuple(x_shape), tuple(w.shape), b is not None, stride, pad, pad_mode, act, transposed))
 
 
 def _f(t: torch.Tensor) -> torch.Tensor:
@@ -177,7 +162,7 @@ def _conv_dgrad(dy, w, x_shape, stride, pad, pad_mode, transposed=False):
 
 def _conv_wgrad(x, dy, w_shape, has_bias, stride, pad, pad_mode, transposed=False):
     key = ("convw", _dev_key(x), _COMPUTE_DTYPE[0], tuple(x.shape), tuple(w_shape), has_bias, stride, pad, pad_mode, ACT_NONE, transposed)
-    p = _plan(key, lambda: _ConvPlan(x.device, _COMPUTE_DTYPE[0], tuple(x.shape), tuple(w_shape), has_bias, stride, pad, pad_mode, ACT_NONE, transposed))
+    p = cached_plan(_PLANS, key, x.device, lambda: _ConvPlan(x.device, _COMPUTE_DTYPE[0], tuple(x.shape), tuple(w_shape), has_bias, stride, pad, pad_mode, ACT_NONE, transposed))
     p.x_in.copy_(x)
     p.dy_in.copy_(dy)
     p.wgrad.run()
@@ -221,7 +206,7 @@ class _NormPlan:
 
 def _norm_plan(x, act, has_res) -> _NormPlan:
     key = ("norm", _dev_key(x), _COMPUTE_DTYPE[0], tuple(x.shape), act, has_res)
-    return _plan(key, lambda: _NormPlan(x.device, _COMPUTE_DTYPE[0], tuple(x.shape), act, has_res))
+    return cached_plan(_PLANS, key, x.device, lambda: _NormPlan(x.device, _COMPUTE_DTYPE[0], tuple(x.shape), act, has_res))
 
 
 def _in_fwd(x, eps, act, residual):
@@ -271,7 +256,7 @@ class _PadPlan:
 
 
 def _pad_plan(shape, device, pad, mode=HALO_REFLECT) -> _PadPlan:
-    return _plan(("pad", (device.type, device.index), tuple(shape), pad, mode), lambda: _PadPlan(device, tuple(shape), pad, mode))
+    return cached_plan(_PLANS, ("pad", (device.type, device.index), tuple(shape), pad, mode), device, lambda: _PadPlan(device, tuple(shape), pad, mode))
 
 
 def _pad_fwd(x, pad, mode=HALO_REFLECT):
@@ -305,7 +290,7 @@ class _ActPlan:
 
 
 def _act_bwd(y, gy, act):
-    p = _plan(("act", _dev_key(y), tuple(y.shape), act), lambda: _ActPlan(y.device, tuple(y.shape), act))
+    p = cached_plan(_PLANS, ("act", _dev_key(y), tuple(y.shape), act), y.device, lambda: _ActPlan(y.device, tuple(y.shape), act))
     p.y_in.copy_(y)
     p.g_in.copy_(gy)
     p.prog.run()
@@ -335,7 +320,7 @@ _LIB.impl("fused_clip_adam_ema_", _fused_adam, _IMPL)
 def _nce_fwd(src, tgt, ids, temperature):
     from . import losses as LS
     P = int(ids.numel())
-    p = LS._plan(("nce", tuple(tgt.shape), tgt.device, P, float(temperature)), lambda: LS._NcePlan(tuple(tgt.shape), tgt.device, P, temperature))
+    p = cached_plan(LS._PLANS, ("nce", tuple(tgt.shape), tgt.device, P, float(temperature)), tgt.device, lambda: LS._NcePlan(tuple(tgt.shape), tgt.device, P, temperature))
     p.src.copy_(src); p.tgt.copy_(tgt); p.ids.copy_(ids)
     p.fwd.run()
     return p.loss.clone().reshape(()), p.g.clone()
@@ -343,7 +328,7 @@ def _nce_fwd(src, tgt, ids, temperature):
 
 def _aug_run(x, prm, backward):
     from . import losses as LS
-    p = LS._plan(("aug", tuple(x.shape), x.device), lambda: LS._AugPlan(tuple(x.shape), x.device))
+    p = cached_plan(LS._PLANS, ("aug", tuple(x.shape), x.device), x.device, lambda: LS._AugPlan(tuple(x.shape), x.device))
     p.prm.copy_(prm)
     if backward:
         p.gy.copy_(x)

@@ -1021,6 +1021,82 @@ class Ctx:
         return cur
 
 
+def check_weight_decay(weight_decay):
+    """torch.optim.Adam's refusal, at construction as torch has it and where the launch is chosen (a NaN fails the comparison too)."""
+    if not weight_decay >= 0.0:
+        raise ValueError(f"Invalid weight_decay value: {weight_decay}")
+
+
+class AdamPlan:
+    """What a fused clip + Adam (+ EMA) launch over a fixed set of tensors needs besides them: the ADAM_CHUNK slices, norm_out, the
+    workspace, the table, the learning rate (host value beside the device float the kernels read: a scheduler rewrites that and rebuilds
+    nothing) and the prebuilt launches.  cut.FusedAdam, training.HipAdam and training.fused_adam_launch are its front ends.
+    `entries` as make_adam_table takes them; the table is made with the first launch."""
+
+    def __init__(self, ctx: Ctx, entries: Sequence[dict], lr: float):
+        self.ctx, self.entries, self.n, self.lr = ctx, entries, len(entries), float(lr)
+        ct, co = [], []
+        for i, e in enumerate(entries):
+            for off in range(0, e["p"].numel(), ADAM_CHUNK):
+                ct.append(i); co.append(off)
+        self.nchunks = len(ct)
+        self.chunk_tensor, self.chunk_off = ctx.i32(ct), torch.tensor(co, dtype=torch.int64, device=ctx.device)
+        self.norm_out, self.ws, self.lr_dev = ctx.f32(4), ctx.f32(self.nchunks + 16), ctx.f32(1, self.lr)
+        self._table, self._ops = None, {}
+
+    def table(self, entries: Optional[Sequence[dict]] = None) -> torch.Tensor:
+        """The plan's table (made once), or a new one for other entries over the same tensors (FusedAdam's skip sets share the chunks,
+        norm_out and the workspace); the caller keeps such a table alive and passes it to step_op."""
+        if entries is not None:
+            return self.ctx.ops.make_adam_table(entries)
+        if self._table is None:
+            self._table = self.ctx.ops.make_adam_table(self.entries)
+        return self._table
+
+    def set_lr(self, lr: float):
+        if float(lr) != self.lr:      # a scheduler moved the rate: one device float follows, the prebuilt launches stay
+            self.lr = float(lr)
+            self.lr_dev.fill_(self.lr)
+
+    def step_op(self, b1, b2, eps, max_norm, grad_scale, ema_decay, weight_decay=0.0, decoupled=False, inv_scale=None, skip_nonfinite=False,
+                table=None, cached=True) -> Op:
+        """The launch for these arguments, gan_adam_step without decay and gan_adam_step_wd with it, built once per argument tuple
+        (cached=False: a new one, for a trainer that builds its update programs again).  The positional lr is the plan's when the launch
+        is built; the kernels read lr_dev."""
+        table = self.table() if table is None else table
+        key = (id(table), b1, b2, eps, max_norm, grad_scale, ema_decay, float(weight_decay), bool(decoupled) and weight_decay != 0.0,
+               inv_scale.data_ptr() if inv_scale is not None else 0, bool(skip_nonfinite))
+        op = self._ops.get(key) if cached else None
+        if op is None:
+            check_weight_decay(weight_decay)
+            args = (table, self.n, self.chunk_tensor, self.chunk_off, self.nchunks, self.lr, b1, b2, eps, max_norm, grad_scale, ema_decay,
+                    self.norm_out, self.ws)
+            kw = dict(lr_dev=self.lr_dev)
+            if inv_scale is not None or skip_nonfinite:      # GradScaler's arguments only where a caller gives them
+                kw.update(inv_scale=inv_scale, skip_nonfinite=skip_nonfinite)
+            if weight_decay == 0.0:
+                op = self.ctx.ops.adam_step(*args, **kw)
+            else:
+                op = self.ctx.ops.adam_step_wd(*args, float(weight_decay), bool(decoupled), **kw)
+            self._ops[key] = op
+        return op
+
+
+def stream_key(device) -> int:
+    """Last part of every plan key.  The op layer bakes the stream that is current on the TENSORS' device into a plan's launches
+    (HipOps._s) while the staging copies run on whatever stream is current there at each call: keyed on that stream's handle, a caller on
+    another stream (`with torch.cuda.stream(s)`) gets a plan of its own, not an unordered pair -- also on a GPU that is not current."""
+    device = torch.device(device)
+    return torch.cuda.current_stream(device).cuda_stream if device.type == "cuda" else 0
+
+
+def cached_plan(cache: dict, key: tuple, device, make):
+    key = key + (stream_key(device),)
+    if key not in cache:
+        cache[key] = make()
+    return cache[key]
+
+
 def cpad(c: int) -> int:
     """Channel padding rule of halo-NHWC: next power of two >= 8."""
     p = 8

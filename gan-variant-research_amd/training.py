@@ -20,7 +20,7 @@ import torch
 from . import autograd as AG
 from ._lib import F32
 from .cut import AMPContext as _AMPBase
-from .runtime import ADAM_CHUNK
+from .runtime import AdamPlan, check_weight_decay, stream_key
 
 
 class HipAdam(torch.optim.Optimizer):
@@ -36,8 +36,7 @@ class HipAdam(torch.optim.Optimizer):
     def __init__(self, params, lr=2e-4, betas=(0.5, 0.999), eps=1e-8, weight_decay=0.0, amsgrad=False, *, decoupled_weight_decay=False):
         if amsgrad:
             raise NotImplementedError("amsgrad needs a fourth state tensor (max_exp_avg_sq) that gan_adam_tensor does not carry")
-        if not weight_decay >= 0.0:
-            raise ValueError(f"Invalid weight_decay value: {weight_decay}")
+        check_weight_decay(weight_decay)
         super().__init__(params, dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay, amsgrad=False,
                                       decoupled_weight_decay=bool(decoupled_weight_decay)))
         self._ema: Dict[int, torch.Tensor] = {}      # id(param) -> shadow tensor (attached by EMA)
@@ -63,26 +62,17 @@ class HipAdam(torch.optim.Optimizer):
 
     def _plan(self, gi, group, live):
         """Prebuilt launch for one param group and one pattern of present gradients (ops hold raw pointers)."""
-        key = (gi, live, group["betas"], group["eps"], torch.cuda.current_stream().cuda_stream if torch.cuda.is_available() else 0)
+        ps = group["params"]
+        dev = ps[0].device
+        key = (gi, live, group["betas"], group["eps"], stream_key(dev))
         pl = self._plans.get(key)
         if pl is None:
-            ps = group["params"]
-            dev = ps[0].device
-            ctx = AG._new_ctx(dev, F32)
-            ents, ct, co = [], [], []
+            ctx, ents = AG._new_ctx(dev, F32), []
             for i, p in enumerate(ps):
                 st = self._state(p)
                 ents.append({"p": p.data.view(-1), "g": st["grad_buf"].view(-1) if live[i] else None, "m": st["exp_avg"].view(-1),
                              "v": st["exp_avg_sq"].view(-1), "ema": self._ema[id(p)].view(-1) if id(p) in self._ema else None, "step": st["step"]})
-                for off in range(0, p.numel(), ADAM_CHUNK):
-                    ct.append(i); co.append(off)
-            pl = {"ctx": ctx, "norm": torch.zeros(4, dtype=torch.float32, device=dev),
-                  "ct": torch.tensor(ct, dtype=torch.int32, device=dev), "co": torch.tensor(co, dtype=torch.int64, device=dev),
-                  "ws": torch.zeros(len(ct) + 16, dtype=torch.float32, device=dev), "ops": {},
-                  "lr": float(group["lr"]), "lr_dev": torch.full((1,), float(group["lr"]), dtype=torch.float32, device=dev)}
-            pl["table"] = ctx.ops.make_adam_table(ents)
-            pl["n"], pl["nchunks"] = len(ps), len(ct)
-            self._plans[key] = pl
+            pl = self._plans[key] = AdamPlan(ctx, ents, group["lr"])
         return pl
 
     @torch.no_grad()
@@ -100,25 +90,11 @@ class HipAdam(torch.optim.Optimizer):
                 if on:
                     self.state[p]["grad_buf"].copy_(p.grad)
             mn = float(max_grad_norm) if max_grad_norm is not None else 0.0
-            if float(group["lr"]) != pl["lr"]:      # a scheduler moved the rate: one device float follows, the prebuilt launch stays
-                pl["lr"] = float(group["lr"])
-                pl["lr_dev"].fill_(pl["lr"])
-            wd, dec = float(group.get("weight_decay", 0.0)), bool(group.get("decoupled_weight_decay", False))
-            if not wd >= 0.0:
-                raise ValueError(f"Invalid weight_decay value: {wd}")
-            hk = (mn, wd, dec and wd != 0.0)
-            op = pl["ops"].get(hk)
-            if op is None:
-                b1, b2 = group["betas"]
-                args = (pl["table"], pl["n"], pl["ct"], pl["co"], pl["nchunks"], pl["lr"], b1, b2, group["eps"], mn, 1.0, self._ema_decay,
-                        pl["norm"], pl["ws"])
-                if wd == 0.0:
-                    op = pl["ctx"].ops.adam_step(*args, lr_dev=pl["lr_dev"])
-                else:
-                    op = pl["ctx"].ops.adam_step_wd(*args, wd, dec, lr_dev=pl["lr_dev"])
-                pl["ops"][hk] = op
-            op()
-            self.last_grad_norm = pl["norm"]
+            pl.set_lr(group["lr"])
+            b1, b2 = group["betas"]
+            pl.step_op(b1, b2, group["eps"], mn, 1.0, self._ema_decay, float(group.get("weight_decay", 0.0)),
+                       bool(group.get("decoupled_weight_decay", False)))()
+            self.last_grad_norm = pl.norm_out
             for p, on in zip(ps, live):            # EMA.update covers every parameter, also one the kernel skipped for want of a gradient
                 if not on and id(p) in self._ema:
                     self._ema[id(p)].mul_(self._ema_decay).add_(p.data, alpha=1.0 - self._ema_decay)
@@ -167,48 +143,28 @@ def fused_adam_launch(params, grads, m, v, ema, steps, lr, b1, b2, eps, max_norm
     address would grow without bound and pin every old gradient."""
     n = len(params)
     assert n and len(grads) == n and len(m) == n and len(v) == n and len(ema) in (0, n) and steps.dtype == torch.int32 and steps.numel() == n
+    dev = params[0].device
     key = tuple((t.data_ptr(), t.numel()) for grp in (params, m, v, ema) for t in grp) + (steps.data_ptr(), inv_scale.data_ptr() if inv_scale is not None else 0,
-                                                                                         torch.cuda.current_stream().cuda_stream if torch.cuda.is_available() else 0)
+                                                                                         stream_key(dev))
     pl = _FUSED_PLANS.get(key)
     if pl is None:
-        dev = params[0].device
-        ctx = AG._new_ctx(dev, F32)
-        ents, ct, co, gbuf = [], [], [], []
+        ctx, ents = AG._new_ctx(dev, F32), []
         for i in range(n):
             for t in (params[i], m[i], v[i]) + ((ema[i],) if ema else ()):
                 assert t.dtype == torch.float32 and t.is_contiguous() and t.numel() == params[i].numel()
-            gbuf.append(torch.zeros(params[i].numel(), dtype=torch.float32, device=dev))
-            ents.append({"p": params[i].view(-1), "g": gbuf[i], "m": m[i].view(-1), "v": v[i].view(-1),
-                         "ema": ema[i].view(-1) if ema else None, "step": steps[i:i + 1]})
-            for off in range(0, params[i].numel(), ADAM_CHUNK):
-                ct.append(i); co.append(off)
+            ents.append({"p": params[i].view(-1), "g": torch.zeros(params[i].numel(), dtype=torch.float32, device=dev), "m": m[i].view(-1),
+                         "v": v[i].view(-1), "ema": ema[i].view(-1) if ema else None, "step": steps[i:i + 1]})
         if len(_FUSED_PLANS) >= 8:      # a handful of optimisers per process; anything beyond that is a caller churning its state tensors
             _FUSED_PLANS.pop(next(iter(_FUSED_PLANS)))
-        pl = _FUSED_PLANS[key] = {"ctx": ctx, "norm": torch.zeros(4, dtype=torch.float32, device=dev), "table": ctx.ops.make_adam_table(ents),
-                                  "ct": torch.tensor(ct, dtype=torch.int32, device=dev), "co": torch.tensor(co, dtype=torch.int64, device=dev),
-                                  "ws": torch.zeros(len(ct) + 16, dtype=torch.float32, device=dev), "gbuf": gbuf,
-                                  "keep": (params, m, v, ema, steps, inv_scale), "ops": {},
-                                  "lr": float(lr), "lr_dev": torch.full((1,), float(lr), dtype=torch.float32, device=dev)}
+        plan = AdamPlan(ctx, ents, lr)
+        # beside the plan: the staging buffers, the state the launch points into, and the plan's tensors under the keys this entry always had
+        pl = _FUSED_PLANS[key] = {"plan": plan, "gbuf": [e["g"] for e in ents], "keep": (params, m, v, ema, steps, inv_scale),
+                                  "ct": plan.chunk_tensor, "co": plan.chunk_off, "norm": plan.norm_out}
     for g, p in zip(grads, params):
         assert g.dtype == torch.float32 and g.numel() == p.numel()
     torch._foreach_copy_(pl["gbuf"], [g.reshape(-1) for g in grads])
-    if float(lr) != pl["lr"]:
-        pl["lr"] = float(lr)
-        pl["lr_dev"].fill_(pl["lr"])
-    if not weight_decay >= 0.0:
-        raise ValueError(f"Invalid weight_decay value: {weight_decay}")
-    hk = (b1, b2, eps, max_norm, grad_scale, ema_decay if ema else 0.0, bool(skip_nonfinite), float(weight_decay), bool(decoupled) and weight_decay != 0.0)
-    op = pl["ops"].get(hk)
-    if op is None:
-        args = (pl["table"], n, pl["ct"], pl["co"], len(pl["ct"]), pl["lr"], b1, b2, eps, max_norm, grad_scale, ema_decay if ema else 0.0,
-                pl["norm"], pl["ws"])
-        kw = dict(lr_dev=pl["lr_dev"], inv_scale=inv_scale, skip_nonfinite=skip_nonfinite)
-        if weight_decay == 0.0:
-            op = pl["ctx"].ops.adam_step(*args, **kw)
-        else:
-            op = pl["ctx"].ops.adam_step_wd(*args, float(weight_decay), bool(decoupled), **kw)
-        pl["ops"][hk] = op
-    op()
+    pl["plan"].set_lr(lr)
+    pl["plan"].step_op(b1, b2, eps, max_norm, grad_scale, ema_decay if ema else 0.0, weight_decay, decoupled, inv_scale, skip_nonfinite)()
     AG.notify_weights_changed()
     return pl["norm"][:1].clone(), pl["norm"][2:3].clone()
 

@@ -163,7 +163,7 @@ def test_a_scheduler_that_moves_the_rate_every_step_keeps_one_plan_and_one_table
     assert seen == pytest.approx([LR * rule(e) for e in range(5)]) and len(set(seen)) == 5
     assert len(mine._plans) == 1 and counts["make_adam_table"] == 1 and counts["adam_step_wd"] == 1, (len(mine._plans), counts)
     (pl,) = mine._plans.values()
-    assert float(pl["lr_dev"]) == t32(seen[-1])
+    assert float(pl.lr_dev) == t32(seen[-1])
 
 
 @pytest.mark.parametrize("kind", list(KINDS))

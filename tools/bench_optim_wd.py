@@ -6,11 +6,16 @@ four paths: gan_adam_step, gan_adam_step_wd with weight_decay 0 (the same kernel
 The paths run in rotation after a warm-up, `rounds` times, `iters` calls each between two HIP events; per path the median and [min .. max]
 of the rounds are printed, with bytes/s at 36 B per parameter (p, m, v, ema read and written, g read by the update kernel; the
 sum-of-squares kernel reads g once more, which is not counted).  The yardstick for "unchanged" is the first path in the same run; the
-margin is the rounds' own spread.  All four paths step the same state block.  Needs a GPU."""
+margin is the rounds' own spread.  All four paths step the same state block.  Needs a GPU.
+
+    python tools/bench_optim_wd.py --host [--calls 200] [--reps 3] [--out FILE]
+
+times the HOST side instead (see host()): what training.HipAdam.step and the fused_clip_adam_ema_ op cost per call on four small tensors."""
 import argparse
 import os
 import statistics
 import sys
+import time
 
 import torch
 
@@ -23,14 +28,57 @@ MODEL = {"generator": {"ngf": 64, "n_blocks": 9, "n_downsampling": 2, "padding_t
          "discriminator": {"ndf": 64, "n_layers": 3, "num_scales": 1, "use_spectral_norm": False}}
 
 
+SMALL = [1, 5, 16384, 16387]      # four tensors, five chunks: the kernels take their least time, what is left is the host's
+
+
+def host(args, dev):
+    """--host: host clock per call of training.HipAdam.step and of torch.ops.mi355x_gan.fused_clip_adam_ema_ (L2 decay, EMA, clipping)
+    on the SMALL tensors, `--calls` calls between two device synchronises, `--reps` repetitions in rotation after a warm-up."""
+    from gan_variant_research_amd import ops_library  # noqa: F401  (registers the ops)
+    from gan_variant_research_amd import training as T
+    new = lambda: [torch.randn(n, device=dev) for n in SMALL]
+    ps = [torch.nn.Parameter(t) for t in new()]
+    opt = T.HipAdam(ps, weight_decay=1e-4)
+    opt.attach_ema({id(p): p.detach().clone() for p in ps}, 0.999)
+    for p, g in zip(ps, new()):
+        p.grad = g
+    q, g, m, v, ema = new(), new(), [torch.zeros(n, device=dev) for n in SMALL], [torch.zeros(n, device=dev) for n in SMALL], new()
+    steps = torch.zeros(len(SMALL), dtype=torch.int32, device=dev)
+    paths = [("HipAdam.step", lambda: opt.step(max_grad_norm=10.0)),
+             ("fused_clip_adam_ema_", lambda: torch.ops.mi355x_gan.fused_clip_adam_ema_(q, g, m, v, ema, steps, 2e-4, 0.5, 0.999, 1e-8, 10.0, 1.0, 0.999,
+                                                                                         None, False, 1e-4, False))]
+    times = {name: [] for name, _ in paths}
+    for rep in range(-1, args.reps):          # -1: the warm-up (plans, tables and launches are built)
+        for name, call in paths:
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(args.calls):
+                call()
+            torch.cuda.synchronize()
+            if rep >= 0:
+                times[name].append((time.perf_counter() - t0) / args.calls * 1e6)
+    lines = [f"{name:22s} host us per call over {args.calls} calls, {args.reps} repetitions: " + "  ".join(f"{t:.2f}" for t in ts) +
+             f"   median {statistics.median(ts):.2f}  spread {max(ts) - min(ts):.2f}" for name, ts in times.items()]
+    print("\n".join(lines), flush=True)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--iters", type=int, default=1000)
+    ap.add_argument("--host", action="store_true")
+    ap.add_argument("--calls", type=int, default=200)
+    ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--out", default=None)
     args = ap.parse_args(argv)
     assert torch.cuda.is_available(), "bench_optim_wd.py measures on the GPU"
     dev = torch.device("cuda:0")
+    if args.host:
+        return host(args, dev)
     ctx = Ctx(HipOps(dev), dev, F32)
     gen, _ = C.build_models({"model": MODEL}, "cpu")
     sd = {k: v.detach().float() for k, v in gen.state_dict().items()}
