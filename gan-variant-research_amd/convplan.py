@@ -217,6 +217,8 @@ class ConvLayer:
             ty = _phase_taps(self.k, self.p, ry)
             for rx in range(2):
                 tx = _phase_taps(self.k, self.p, rx)
+                if not ty or not tx:
+                    raise GanError(f"k{self.k} s2 p{self.p}: sub-pixel phase ({ry}, {rx}) has no tap (a 1x1 stride-2 layer is not planned, on any B or map)")
                 dmy, dmx = min(d for _, d in ty), min(d for _, d in tx)
                 taps = [(dy - dmy, dx - dmx, kh * self.k + kw) for kh, dy in ty for kw, dx in tx]
                 pk = _Pack(self.ctx, taps, n_real, c_real, True, i2, self.kk)
@@ -297,7 +299,10 @@ class ConvLayer:
         """dst[2a+r] = sum_taps src[a + d] * w: used by ConvTranspose2d forward and by the strided conv's input gradient."""
         ops, out = self.ctx.ops, []
         gh, gw = dst.H // 2, dst.W // 2
-        pairs = self._pair_packs(packs) if (dst.halo == 0 and mask is None and dst.C == 64) else None
+        # a paired launch views the destination as 128-channel super-pixels: both phases of a row then have the same extent, which
+        # holds on an even destination only (an odd one takes the four single phases below, each with its own extent)
+        even = dst.H % 2 == 0 and dst.W % 2 == 0
+        pairs = self._pair_packs(packs) if (even and dst.halo == 0 and mask is None and dst.C == 64) else None
         if pairs is not None:
             # the destination as rows of 128-channel super-pixels (same storage)
             sup = View(dst.t, dst.B, dst.H, gw, 128, 0, dst.dtype)
@@ -315,6 +320,11 @@ class ConvLayer:
                 return [ops.conv_igemm(c) for c in calls]
         for pk in packs:
             (ry, rx), (dmy, dmx), (dxy, dxx) = pk.phase, pk.dmin, pk.dmax
+            # phase (ry, rx) covers rows ry, ry + 2, ... and columns rx, rx + 2, ... of the destination: one more of the even ones when
+            # the extent is odd, none of the odd ones on a 1-wide map (that phase has no launch)
+            gh, gw = (dst.H - ry + 1) // 2, (dst.W - rx + 1) // 2
+            if gh == 0 or gw == 0:
+                continue
             assert src.halo + dmy >= 0 and src.halo + dmx >= 0, "source halo too small (top/left)"
             assert gh - 1 + dxy <= src.H - 1 + src.halo and gw - 1 + dxx <= src.W - 1 + src.halo, "source halo too small (bottom/right)"
             out.append(ops.conv_igemm(pk.finalize(ConvCall(src.B, gh, gw, pk.cred, pk.ntaps, pk.nw, min(pk.nw, dst.C), src, src.halo + dmy, src.halo + dmx,
@@ -373,7 +383,18 @@ class ConvLayer:
                     raise GanError(f"input gradient B{dy.B} {call.Ho}x{call.Wo} C{dx.C}: the launch cannot carry the backward chain (ask can_chain first)")
                 self.chain_parts = n
             return [ops.conv_igemm(call)]
-        assert not padded_domain and (dx.H, dx.W) == (2 * dy.H, 2 * dy.W)
+        # every input size whose forward output is dy: odd maps, and even ones whose last row / column no tap reaches (their gradient
+        # is 0, read from the zero halo of dy)
+        k = self.k
+        if padded_domain or (dy.H, dy.W) != ((dx.H + 2 * p - k) // 2 + 1, (dx.W + 2 * p - k) // 2 + 1):
+            raise GanError(f"input gradient B{dy.B} {dx.H}x{dx.W} k{k} s{self.s} p{p}: " + ("a strided convolution has no padded-domain gradient"
+                           if padded_domain else f"a {dy.H}x{dy.W} output gradient is not the size of this map's forward output"))
+        for pk in self.dgrad_packs:
+            (ry, rx), (dmy, dmx), (dxy, dxx) = pk.phase, pk.dmin, pk.dmax
+            gh, gw = (dx.H - ry + 1) // 2, (dx.W - rx + 1) // 2
+            if gh and gw and not (dy.halo + dmy >= 0 and dy.halo + dmx >= 0 and gh - 1 + dxy <= dy.H - 1 + dy.halo and gw - 1 + dxx <= dy.W - 1 + dy.halo):
+                raise GanError(f"input gradient B{dy.B} {dx.H}x{dx.W} k{k} s{self.s} p{p}: phase ({ry}, {rx}) reads outside the halo {dy.halo} "
+                               f"of the {dy.H}x{dy.W} output gradient")
         return self._phased(self.dgrad_packs, dy, dx, ACT_NONE, None, mask)
 
     def can_chain(self, dy: View, dx: View) -> bool:

@@ -48,7 +48,10 @@ typedef struct gan_view {
  * for output channel n is act(sum + bias[n]) [* lrelu'(mask)] stored at
  * out[((b*out_Hp + ho*out_sy + out_y0)*out_Wp + wo*out_sx + out_x0)*out_C + n].
  * One descriptor covers nn.Conv2d forward, its input-gradient (flipped taps over a zero-haloed dY), the
- * four sub-pixel phases of nn.ConvTranspose2d and their gradients. */
+ * four sub-pixel phases of nn.ConvTranspose2d and their gradients, and the four phases of a stride-2
+ * nn.Conv2d's input gradient (out_sy = out_sx = 2, out_y0 / out_x0 = the phase).  Phase (ry, rx) of an H x W
+ * destination has Ho = (H - ry + 1) / 2 and Wo = (W - rx + 1) / 2: on an odd destination the phases differ in
+ * extent, and a phase without pixels (the odd ones of a 1-pixel axis) has no launch. */
 typedef struct gan_conv_desc {
   int32_t dtype;                 /* operand/out dtype */
   int32_t B, Ho, Wo;             /* GEMM rows */

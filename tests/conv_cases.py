@@ -59,14 +59,19 @@ def out_hw(g):
 
 
 # ------------------------------------------------------------------------------------------------ the cases
-# The 15 shapes of the geometry group: (cin, cout, k, s, p, transposed, H, W, reflect), then per direction the kernel the bf16 planner
+# The 20 shapes of the geometry group: (cin, cout, k, s, p, transposed, H, W, reflect), then per direction the kernel the bf16 planner
 # takes and its launch count, and the launch count in fp32 (always the generic kernel; no paired phases there).  None: no such direction.
 TABLE = [
     ((3, 16, 7, 1, 3, False, 5, 23, True), ("generic", 1, 1), ("generic", 1, 1)),
     ((64, 3, 7, 1, 3, False, 17, 33, True), ("win7", 1, 1), ("win7", 1, 1)),
     ((3, 64, 7, 1, 3, False, 33, 4, True), ("win7", 1, 1), ("win7", 1, 1)),
     ((16, 32, 3, 2, 1, False, 6, 14, False), ("generic", 1, 1), ("generic", 4, 4)),
-    ((16, 32, 3, 2, 1, False, 7, 13, False), ("generic", 1, 1), None),     # stride 2 on an odd map: the planner has no input gradient for it
+    ((16, 32, 3, 2, 1, False, 7, 13, False), ("generic", 1, 1), ("generic", 4, 4)),     # stride 2 on an odd map: phases of 4x7, 4x6, 3x7, 3x6
+    ((3, 16, 4, 2, 1, False, 9, 5, False), ("generic", 1, 1), ("generic", 4, 4)),         # k4 on an odd map: 5x3, 5x2, 4x3, 4x2
+    ((128, 256, 4, 2, 1, False, 9, 11, False), ("patch", 1, 1), ("patch", 4, 4)),         # the four 4-tap phases, each with its own extent
+    ((64, 128, 3, 2, 1, False, 7, 13, False), ("patch", 1, 1), ("generic", 4, 4)),        # 64 output channels on an odd map: never paired
+    ((64, 128, 3, 2, 1, False, 6, 13, False), ("patch", 1, 1), ("generic", 4, 4)),        # even H, odd W: not paired either
+    ((16, 32, 3, 2, 1, False, 1, 1, False), ("generic", 1, 1), ("generic", 1, 1)),        # one pixel: phase (0, 0) alone has an extent
     ((128, 128, 3, 1, 1, False, 2, 40, True), ("patch", 1, 1), ("patch", 1, 1)),
     ((128, 128, 3, 1, 1, False, 19, 15, True), ("patch", 1, 1), ("patch", 1, 1)),
     ((128, 64, 3, 2, 1, True, 3, 9, False), ("patch", 2, 4), ("patch", 1, 1)),          # forward: the paired phases
@@ -112,6 +117,9 @@ def _geometry_specs():
         P((256, 256, 3, 1, 1, False, 12, 20, True), env=[("GAN_PATCH_BN", "256"), ("GAN_PATCH_BM", "288")], rows=288, cols=256),
         P((256, 256, 3, 1, 1, False, 12, 20, True), op="dgrad", env=[("GAN_PATCH_BN", "256")], rows=256, cols=256),
         P((128, 256, 4, 2, 1, False, 6, 10, False), op="dgrad", static_taps=4, n=4),                       # the four 4-tap phases of a k4 s2 input gradient
+        P((128, 256, 4, 2, 1, False, 9, 11, False), op="dgrad", static_taps=4, n=4, rows=256, cols=128,    # ... on an odd map: 5x6, 5x5, 4x6 and 4x5 pixels,
+          some=[(("layout", 1), ("static_taps", 4), ("tiles", 3))]),                                          # none too small for the kernel: one tile per image
+        Spec((64, 128, 3, 2, 1, False, 7, 13, False), 3, BF16, "dgrad", "generic", layout=0, n=4, cols=64),  # an odd destination is not viewed as super-pixels
         Spec((128, 256, 3, 2, 1, False, 6, 10, False), 3, BF16, "dgrad", "patch", some=[(("layout", 1), ("static_taps", 2)), (("layout", 1), ("static_taps", 4)), (("layout", 0),)], n=4),
         P((128, 128, 4, 1, 1, False, 6, 10, False), static_taps=16),
         P((64, 128, 7, 1, 3, False, 9, 12, True), static_taps=0, slices=7),                                 # the generic tap loop: 49 taps
@@ -151,6 +159,8 @@ def _epilogue_specs():
         out += [Spec((16, 32, 3, 2, 1, False, 6, 10, False), 3, dt, "dgrad", "generic", mask=mh, layout=0, n=4) for dt in (BF16, F32)]
         out.append(Spec((128, 64, 4, 1, 1, False, 6, 9, False), 3, BF16, "dgrad", "patch", mask=mh, layout=1))
         out.append(Spec((128, 128, 4, 2, 1, False, 6, 10, False), 3, BF16, "dgrad", "patch", mask=mh, layout=1, n=4))
+        out += [Spec((16, 32, 4, 2, 1, False, 9, 7, False), 3, dt, "dgrad", "generic", mask=mh, layout=0, n=4) for dt in (BF16, F32)]       # odd maps: the mask
+        out.append(Spec((128, 256, 4, 2, 1, False, 9, 11, False), 3, BF16, "dgrad", "patch", mask=mh, layout=1, n=4, static_taps=4))     # offsets follow the phase
         out.append(Spec((32, 16, 3, 2, 1, True, 3, 5, False), 3, BF16, "dgrad", "generic", mask=mh, layout=0))          # a transposed layer's input gradient
     out += [Spec(E_PATCH, 3, BF16, "fwd", "patch", stats=True, layout=1), Spec(E_PATCH2, 3, BF16, "fwd", "patch", stats=True, layout=1, tiles=6),
             Spec(E_PATCH, 1, BF16, "fwd", "patch", stats=True, layout=1), Spec(E_FROM3, 3, BF16, "fwd", "win7", stats=True, layout=2),
@@ -172,6 +182,7 @@ def _nonfinite_specs():
                 Spec(E_PATCH2, 3, BF16, "fwd", "patch", stats=True, poison=poison, layout=1),
                 Spec((128, 64, 4, 1, 1, False, 6, 9, False), 3, BF16, "dgrad", "patch", mask=1, poison=poison, layout=1),
                 Spec((16, 32, 3, 2, 1, False, 6, 10, False), 3, F32, "dgrad", "generic", mask=0, poison=poison, layout=0, n=4),
+                Spec((16, 32, 3, 2, 1, False, 7, 13, False), 3, F32, "dgrad", "generic", mask=0, poison=poison, layout=0, n=4),      # an odd strided input gradient
                 Spec((128, 64, 3, 2, 1, True, 6, 10, False), 3, BF16, "fwd", "patch", poison=poison, layout=1, n=2),      # paired: the widened footprint
                 Spec((256, 128, 3, 2, 1, True, 6, 10, False), 3, BF16, "fwd", "patch", poison=poison, n=4, some=[(("layout", 1), ("static_taps", 4)), (("layout", 0),)]),     # unpaired
                 Spec(E_CHAIN, 3, BF16, "dgrad", "patch", chain=True, poison=poison, layout=1)]
@@ -402,6 +413,7 @@ def result(make, S):
 # ------------------------------------------------------------------------------------------------ the reference a result is held to
 class Ref:
     drop_tap = swap_taps = zero_pad = bias_after = mask_off = swap_phase = no_outpad = rounded_stats = unrounded_chain = missing_image = False
+    even_extent = False
     slope = 0.2
 
 
@@ -412,7 +424,8 @@ def _wrong(name, **kw):
 WRONG = [_wrong("TapDropped", drop_tap=True), _wrong("TapRowsAndColumnsSwapped", swap_taps=True), _wrong("ZeroPaddingForReflect", zero_pad=True),
          _wrong("BiasAfterActivation", bias_after=True), _wrong("SlopeZero", slope=0.0), _wrong("MaskOnePixelOff", mask_off=True),
          _wrong("PhaseRowAndColumnSwapped", swap_phase=True), _wrong("NoOutputPadding", no_outpad=True), _wrong("StatisticsOfTheRoundedResult", rounded_stats=True),
-         _wrong("ChainSumsOfTheUnroundedGradient", unrounded_chain=True), _wrong("OneImageMissing", missing_image=True)]
+         _wrong("ChainSumsOfTheUnroundedGradient", unrounded_chain=True), _wrong("OneImageMissing", missing_image=True),
+         _wrong("PhasesOfOneExtent", even_extent=True)]
 
 _refs = {}
 
@@ -464,6 +477,10 @@ def stated(res, ref):
     if ref.missing_image and S.B > 1:
         val = val.clone()
         val[S.B - 1] = val[0]
+    if ref.even_extent and S.op == "dgrad" and S.g.s == 2 and not S.g.tr:      # every phase H // 2 x W // 2: the last row / column of an odd map is left out
+        val = val.clone()
+        val[:, :, 2 * (S.g.H // 2):, :] = 0.0
+        val[:, :, :, 2 * (S.g.W // 2):] = 0.0
     tol, et = R.elem_tol(t, A, K, S.act, mf, res["u_out"], res["b64"] is not None)
     return val, tol, t, et
 
@@ -614,14 +631,19 @@ def check_predicates(hip_ops, S):
 
 # ------------------------------------------------------------------------------------------------ wrong references
 REJECT_ON = {
-    "TapDropped": [Spec(E_GEN, 3, F32, "fwd", "generic", layout=0), Spec(E_PATCH, 3, BF16, "fwd", "patch", layout=1), Spec(E_TO3, 3, BF16, "fwd", "win7", layout=2)],
+    "TapDropped": [Spec(E_GEN, 3, F32, "fwd", "generic", layout=0), Spec((3, 16, 4, 2, 1, False, 9, 5, False), 3, BF16, "dgrad", "generic", layout=0, n=4), Spec(E_PATCH, 3, BF16, "fwd", "patch", layout=1), Spec(E_TO3, 3, BF16, "fwd", "win7", layout=2)],
     "TapRowsAndColumnsSwapped": [Spec(E_GEN, 3, BF16, "fwd", "generic", layout=0), Spec(E_PATCH, 3, BF16, "fwd", "patch", layout=1), Spec(E_FROM3, 3, BF16, "fwd", "win7", layout=2)],
     "ZeroPaddingForReflect": [Spec(E_PATCH, 3, BF16, "fwd", "patch", layout=1), Spec(E_GEN3, 3, F32, "fwd", "generic", layout=0)],
     "BiasAfterActivation": [Spec(E_GEN, 3, BF16, "fwd", "generic", act=R.ACT_RELU, layout=0), Spec(E_PATCH, 3, BF16, "fwd", "patch", act=R.ACT_LRELU, layout=1),
                             Spec(E_TO3, 3, BF16, "fwd", "win7", act=R.ACT_TANH, layout=2)],
     "SlopeZero": [Spec(E_GEN, 3, F32, "fwd", "generic", act=R.ACT_LRELU, layout=0), Spec((128, 64, 4, 1, 1, False, 6, 9, False), 3, BF16, "dgrad", "patch", mask=1, layout=1)],
     "MaskOnePixelOff": [Spec((16, 32, 4, 1, 1, False, 6, 9, False), 3, F32, "dgrad", "generic", mask=1, layout=0),
+                        Spec((16, 32, 4, 2, 1, False, 9, 7, False), 3, F32, "dgrad", "generic", mask=1, layout=0, n=4),
+                        Spec((128, 256, 4, 2, 1, False, 9, 11, False), 3, BF16, "dgrad", "patch", mask=0, layout=1, n=4, static_taps=4),
                         Spec((128, 128, 4, 2, 1, False, 6, 10, False), 3, BF16, "dgrad", "patch", mask=0, layout=1, n=4)],
+    "PhasesOfOneExtent": [Spec((16, 32, 3, 2, 1, False, 7, 13, False), 3, F32, "dgrad", "generic", layout=0, n=4),
+                          Spec((64, 128, 3, 2, 1, False, 6, 13, False), 3, BF16, "dgrad", "generic", layout=0, n=4),
+                          Spec((128, 256, 4, 2, 1, False, 9, 11, False), 3, BF16, "dgrad", "patch", layout=1, n=4)],
     "PhaseRowAndColumnSwapped": [Spec((16, 32, 3, 2, 1, False, 6, 10, False), 3, F32, "dgrad", "generic", mask=0, layout=0, n=4),
                                  Spec((128, 64, 3, 2, 1, True, 3, 9, False), 3, BF16, "fwd", "patch", layout=1, n=2, cols=128)],
     "NoOutputPadding": [Spec((128, 64, 3, 2, 1, True, 3, 9, False), 3, BF16, "fwd", "patch", layout=1, n=2, cols=128), Spec((128, 64, 3, 2, 1, True, 3, 9, False), 3, F32, "fwd", "generic", layout=0, n=4)],

@@ -199,6 +199,63 @@ def optional_cases(device, tol, tags=("ms3", "sn2")):
         D.train()
 
 
+def odd_map_cases(device, tol, tags=("ms2_72", "sn_36")):
+    """Discriminators on image sizes whose maps are odd, against torch autograd (no golden exists at these sizes, none is needed):
+    ms2_72: two scales at 72x72 against the oracle -- the first scale is 72 -> 36 -> 18 -> 9, the pooled one 36 -> 18 -> 9 -> 4, so both
+            meet a 4x4 stride-2 layer on a 9x9 map;
+    sn_36:  one scale with spectral norm at 36x36 against the same layers under torch.nn.utils.spectral_norm (torch's own power
+            iteration, one per training-mode forward, from the same u and v).
+    Outputs, the loss of a hinge D-step + G-step mix, its input gradient and every parameter gradient; sn_36 also u and v afterwards."""
+    from gan_variant_research_amd import losses as L
+    gen = torch.Generator().manual_seed(7)
+    for tag in tags:
+        ns, sn, S = (2, False, 72) if tag == "ms2_72" else (1, True, 36)
+        torch.manual_seed(11)
+        D = C.MultiscaleDiscriminator(3, 4, 3, num_scales=ns, use_spectral_norm=sn)
+        sd = {k: v.detach().clone() for k, v in D.state_dict().items()}
+        D = D.to(device)
+        x, y = torch.rand(2, 3, S, S, generator=gen) * 2 - 1, torch.rand(2, 3, S, S, generator=gen) * 2 - 1
+        xo = x.clone().requires_grad_(True)
+        if sn:
+            import torch.nn as nn
+            chans = [3, 4, 8, 16, 32, 1]
+            seq = []
+            for i in range(5):
+                seq.append(nn.utils.spectral_norm(nn.Conv2d(chans[i], chans[i + 1], 4, 2 if i < 3 else 1, 1)))
+                if i < 4:
+                    seq.append(nn.LeakyReLU(0.2))
+            twin = nn.Sequential(*seq)
+            twin.load_state_dict({k[len("discriminators.0.model."):]: v for k, v in sd.items()})
+            twin(x)
+            D(x.to(device))                             # every training-mode forward runs one power iteration, on both sides
+            outs_o, po = [twin(xo)], dict(twin.named_parameters())
+            fake_o = [twin(y)]
+            names_o = {f"discriminators.0.model.{k}": v for k, v in po.items()}
+        else:
+            po = {k: v.clone().requires_grad_(True) for k, v in sd.items()}
+            outs_o, fake_o, names_o = cut_ref.discriminator_forward(po, xo, 3, ns), cut_ref.discriminator_forward(po, y, 3, ns), po
+        xr = x.clone().to(device).requires_grad_(True)
+        outs = D(xr)
+        assert len(outs) == ns
+        for i, (o, oo) in enumerate(zip(outs, outs_o)):
+            assert o.shape == oo.shape
+            _close(o, oo, tol, f"{tag} out{i}")
+        loss = L.discriminator_hinge_loss(outs, D(y.to(device))) + 0.25 * L.generator_hinge_loss(outs)
+        loss_o = cut_ref.d_hinge(outs_o, fake_o) + 0.25 * cut_ref.g_hinge(outs_o)
+        _close(loss, loss_o, tol, f"{tag} loss")
+        names = [k for k, _ in D.named_parameters()]
+        grads = torch.autograd.grad(loss, [xr] + [p_ for _, p_ in D.named_parameters()])
+        grads_o = torch.autograd.grad(loss_o, [xo] + [names_o[k] for k in names])
+        _close(grads[0], grads_o[0], tol * 5, f"{tag} dL/dx")
+        for k, gr, go in zip(names, grads[1:], grads_o[1:]):
+            _close(gr, go, tol * 5, f"{tag} grad {k}")
+        if sn:
+            tsd = twin.state_dict()
+            for k, v in D.state_dict().items():
+                if k.endswith("_u") or k.endswith("_v"):
+                    _close(v, tsd[k[len("discriminators.0.model."):]], tol, f"{tag} buffer {k} after the forwards")
+
+
 def generator_variant_cases(device, tol, tags=("gz", "grl")):
     """ResNetGenerator with padding_type='zero' (no pad modules: other state_dict indices, zero halos, no gradient folding) and / or
     activation='leaky_relu' in the residual blocks, against vectors the reference produced (cut_optional.npz: gz = zero + leaky_relu,
@@ -303,6 +360,14 @@ def test_optional_discriminators_on_emulator(monkeypatch, tag):
     from gan_variant_research_amd import losses as L
     monkeypatch.setattr(L, "_PLANS", {})
     optional_cases(torch.device("cpu"), 2e-4, tags=(tag,))
+
+
+@pytest.mark.parametrize("tag", ["ms2_72", "sn_36"])
+def test_discriminators_on_odd_maps_on_emulator(monkeypatch, tag):
+    monkeypatch.setattr(AG, "_OPS_FACTORY", lambda device: EmuOps())
+    from gan_variant_research_amd import losses as L
+    monkeypatch.setattr(L, "_PLANS", {})
+    odd_map_cases(torch.device("cpu"), 2e-4, tags=(tag,))
 
 
 def test_autograd_bridge_on_emulator(monkeypatch):

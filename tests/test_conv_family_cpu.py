@@ -23,7 +23,7 @@ def make(dtype):
 
 # ---------------------------------------------------------------------------------------------- the reference against float64 torch
 @pytest.mark.parametrize("g", [(5, 7, 3, 1, 1, False, 6, 11, True), (4, 6, 4, 2, 1, False, 6, 10, False), (6, 5, 3, 2, 1, True, 3, 7, False),
-                               (3, 4, 7, 1, 3, False, 9, 5, True)], ids=str)
+                               (3, 4, 7, 1, 3, False, 9, 5, True), (4, 6, 4, 2, 1, False, 7, 9, False), (4, 6, 3, 2, 1, False, 7, 13, False)], ids=str)
 def test_reference_equals_float64_torch_on_non_square_maps(g):
     cin, cout, k, s, p, tr, H, W, reflect = g
     gen = torch.Generator().manual_seed(3)

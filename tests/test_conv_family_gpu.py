@@ -5,7 +5,8 @@ same bodies on the emulator and shows that the bounds admit it and reject the li
 What the cases reach that the square twins of tests/test_gpu_parity.py do not: H != W on every kernel, B = 1 / 3 / 20, maps smaller than
 a tile, Ho * Wo = 128 / 129, the persistent walk with skipped virtual tiles, the 256-row Nw = 16 tile, 7- and 9-slice buffers, 256- and
 288-row and 128- and 256-column tiles, every static tap schedule and the generic tap loop, M_img around a tile, Wo = 2 and Wo = 1, both
-paired-phase launches, both window kernels in both directions; every activation with and without bias, cout 1 / 3 / 20, the LeakyReLU'
+paired-phase launches, the input gradient of stride-2 layers on odd maps (phases of different extents, never paired), both window
+kernels in both directions; every activation with and without bias, cout 1 / 3 / 20, the LeakyReLU'
 mask with zeros and -0.0 through halo 0 and 1, fused partials and chain sums, and one NaN / +Inf.  Each case asserts from the library's
 own plan that it reached the kernel and branch it names."""
 import pytest

@@ -117,6 +117,17 @@ def test_fused_trainer_matches_module_step_dfamily(monkeypatch, num_scales, sn, 
     fused_vs_module_case("cpu", num_scales, sn, S, 3, DFamilyEmuOps)
 
 
+@pytest.mark.parametrize("num_scales,sn,S", [(2, False, 72), (1, True, 36)])
+def test_fused_trainer_matches_module_step_on_odd_maps(monkeypatch, num_scales, sn, S):
+    """72 -> 36 -> 18 -> 9 and, pooled, 36 -> 18 -> 9 -> 4: the third 4x4 stride-2 layer of every scale sees a 9x9 map, whose input gradient
+    has phases of different extents; one scale with spectral norm at 36.  One step, fused trainer against the autograd bridge."""
+    from gan_variant_research_amd import losses as L
+    monkeypatch.setattr(AG, "_OPS_FACTORY", lambda device: EmuOps())
+    monkeypatch.setattr(L, "_PLANS", {})
+    torch.set_num_threads(4)
+    fused_vs_module_case("cpu", num_scales, sn, S, 1, DFamilyEmuOps)
+
+
 def test_default_discriminator_builds_todays_programs():
     """One scale without spectral norm: no power iteration, no pack inside a forward, the merged real | fake pass of 2B images."""
     cfg = dfamily_config(1, False, small_g=True)

@@ -137,6 +137,16 @@ def test_fused_trainer_dfamily_matches_module_step_fp32_hip(monkeypatch):
     fused_vs_module_case(DEV, 2, True, 64, 3, _ops)
 
 
+@pytest.mark.parametrize("num_scales,sn,S", [(2, False, 72), (1, True, 36)])
+def test_fused_trainer_dfamily_on_odd_maps_hip(monkeypatch, num_scales, sn, S):
+    """9x9 maps under the third 4x4 stride-2 layer of every scale (72 -> 36 -> 18 -> 9; pooled 36 -> 18 -> 9 -> 4), and one spectral-norm
+    scale at 36: one fp32 step, fused trainer against module_step.train_step on the same kernels."""
+    from gan_variant_research_amd import losses as L
+    from tests.test_dfamily_cpu import fused_vs_module_case
+    monkeypatch.setattr(L, "_PLANS", {})
+    fused_vs_module_case(DEV, num_scales, sn, S, 1, _ops)
+
+
 def test_multistream_dfamily_step_is_deterministic():
     """Two runs of the multi-stream step (discriminator stream, weight-gradient side stream) give bit-identical losses and parameters."""
     from tests.test_dfamily_cpu import _inputs, dfamily_config

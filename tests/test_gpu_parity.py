@@ -394,14 +394,25 @@ def test_cut_train_step_bf16_vs_oracle_at_benchmark_resolution(monkeypatch):
     assert float((img - ref_img).abs().max()) < 5e-2
 
 
-@pytest.mark.parametrize("B,S", [(1, 64), (3, 64), (5, 64), (2, 80), (3, 96)])
+@pytest.mark.parametrize("B,S", [(1, 64), (3, 64), (5, 64), (2, 80), (3, 96), (3, 36), (2, 100)])
 def test_cut_train_step_ragged_shapes_vs_oracle(B, S):
     """Batch sizes that are not powers of two (and a single image) and image sizes whose maps are no multiple of any tile (80 -> 20x20 and
     40x40 maps, 96 -> 24x24): GEMM row counts with tails in every tile size (128, 256, 288), persistent blocks with uneven tile counts,
     weight-gradient stages that straddle image rows and images (the general addressing path), split-K over 2B = 2 ... 10 images -- fp32
-    mode against the oracle within 1e-3."""
+    mode against the oracle within 1e-3.  36 and 100 are no multiple of 8: the discriminator's third 4x4 stride-2 layer sees a 9x9 / 25x25
+    map, whose input gradient has sub-pixel phases of different extents."""
     tr, img, ref_img = cases.run_cut_steps(DEV, HipOps(torch.device(DEV)), True, amp=False, S=S, B=B, nsteps=1, tol0=1e-3)
     np.testing.assert_allclose(img.numpy(), ref_img.numpy(), rtol=1e-3, atol=1e-3)
+
+
+def test_cut_train_step_on_odd_discriminator_maps_vs_oracle():
+    """36 -> 18 -> 9: one image, one step, fp32 mode, at run_cut_steps' own tolerances (tests/test_oplib_family_cpu.py: the emulator's twin)"""
+    tr, img, ref_img = cases.run_cut_steps(DEV, HipOps(torch.device(DEV)), False, S=36, B=1, nsteps=1)
+    torch.testing.assert_close(img, ref_img, rtol=2e-4, atol=2e-4)
+
+
+def test_basic_gan_iteration_on_odd_discriminator_maps_vs_oracle():
+    cases.run_basic_iterations(DEV, HipOps(torch.device(DEV)), S=36, B=1, niter=1)
 
 
 def test_cut_train_step_bf16_vs_oracle():
@@ -451,6 +462,16 @@ def test_optional_discriminators_hip(monkeypatch, tag):
     from tests.test_autograd_bridge import optional_cases
     monkeypatch.setattr(L, "_PLANS", {})
     optional_cases(torch.device(DEV), 5e-4, tags=(tag,))
+
+
+@pytest.mark.parametrize("tag", ["ms2_72", "sn_36"])
+def test_discriminators_on_odd_maps_hip(monkeypatch, tag):
+    """Two scales at 72x72 against the oracle and one spectral-norm scale at 36x36 against torch's own spectral_norm, under torch autograd:
+    outputs, input gradient, parameter gradients (9x9 maps under the 4x4 stride-2 layers)."""
+    from gan_variant_research_amd import losses as L
+    from tests.test_autograd_bridge import odd_map_cases
+    monkeypatch.setattr(L, "_PLANS", {})
+    odd_map_cases(torch.device(DEV), 5e-4, tags=(tag,))
 
 
 @pytest.mark.parametrize("tag", ["gz", "grl"])

@@ -209,7 +209,8 @@ def test_ops_are_registered_with_schemas():
     from gan_variant_research_amd import ops_library as L  # noqa: F401
     for name in ("conv2d_fwd", "conv2d_dgrad", "conv2d_wgrad", "conv_transpose2d_fwd", "conv_transpose2d_dgrad", "conv_transpose2d_wgrad",
                  "instance_norm_fwd", "instance_norm_bwd", "reflection_pad2d", "reflection_pad2d_bwd", "replication_pad2d", "replication_pad2d_bwd",
-                 "fused_clip_adam_ema_", "patchnce_fwd", "patchnce_bwd", "diffaugment_fwd", "diffaugment_bwd", "allreduce_bucket_"):
+                 "fused_clip_adam_ema_", "patchnce_fwd", "patchnce_bwd", "diffaugment_fwd", "diffaugment_bwd", "allreduce_bucket_",
+                 "act_bwd", "palette_stats", "palette_prior_fwd", "palette_prior_bwd"):
         op = getattr(torch.ops.mi355x_gan, name)
         assert "Tensor" in str(op.default._schema), name
 
