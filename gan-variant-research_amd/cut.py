@@ -507,6 +507,9 @@ class CutTrainer:
         self.D32 = self.D if self.ctx32 is self.ctxD else d_net(self.ctx32)
         self.nce_layers = feature_layers_present(config["patchnce"]["nce_layers"], nb) if lw["patchnce"] > 0 else []
         self.P = config["patchnce"]["num_patches"]
+        # negatives from the whole (global) minibatch instead of the query's own image: the gan_patchnce_all_* entry points
+        self.nce_all = bool(config["patchnce"].get("nce_includes_all_negatives_from_minibatch", False))
+        self.nce_exchanges = 0               # collectives of normalised source rows performed so far (data parallel: one per step)
         # Identity warm-up (identity weight > 0): G(photos) and G(monets) are two full passes through the same weights, and
         # InstanceNorm is per sample -> they run as ONE pass over 2B images (half the launches, one split-K reduction per layer);
         # after the warm-up the generator pass holds the photos only.  `merge_identity_pass: false` keeps three separate passes.
@@ -567,6 +570,21 @@ class CutTrainer:
             return
         import torch.distributed as dist
         dist.all_reduce(self.pal_batch, group=self.pg)
+
+    def _nce_exchange(self, parts, send, recv):
+        """Data parallel, whole-minibatch negatives: the normalised source rows of ALL PatchNCE layers (Sn at the head of each layer's
+        workspace) travel in ONE all-gather per step, queued on the main stream between the layers' gathers and their forwards.  recv holds
+        world_size segments of send's length in rank order: layer l reads its keys at recv[offset_l:] with that length as segment stride."""
+        import contextlib
+        import torch.distributed as dist
+        # the copies and the collective are ordered on the stream the gathers were queued on (RCCL orders itself after the stream that is
+        # current at the call, and the forwards that read recv follow on the same stream)
+        on = torch.cuda.stream(self.ops._ts()) if self.device.type == "cuda" else contextlib.nullcontext()
+        with on:
+            for ws, off, n in parts:
+                send[off:off + n].copy_(ws[:n])
+            dist.all_gather(list(recv.view(self.world_size, send.numel()).unbind(0)), send, group=self.pg)
+        self.nce_exchanges += 1
 
     def _scale_sum(self, v, name) -> float:
         return sum(v[LOSS_SLOTS[name] if s == 0 else len(LOSS_SLOTS) + len(SCALE_SLOTS) * (s - 1) + SCALE_SLOTS.index(name)]
@@ -663,7 +681,9 @@ class CutTrainer:
             pf.add(self.p2.fwd_program(fake))
             pf.add(ops.fill(self._slot("nce"), 0.0))
             wl = lw["patchnce"] / len(self.nce_layers)
-            for li, ids in zip(self.nce_layers, self.nce_ids):
+            if self.nce_all:
+                self._build_nce_all(pf, hooks, src_feat, wl)
+            for li, ids in zip(() if self.nce_all else self.nce_layers, self.nce_ids):
                 src, tgt = src_feat(li), self.p2.acts[li]
                 P = ids.numel()
                 ws = ctx.f32(ops.patchnce_ws_floats(B, P, src.C))
@@ -737,6 +757,40 @@ class CutTrainer:
         return {"p1": p1, "p3": p3, "photos_v": photos_v, "prog_gfwd": prog_gfwd, "prog_d_compute": pd, "prog_g_features": pf,
                 "prog_g_adversarial": pa, "prog_g_features_bwd": pg0, "prog_g_compute": pg,
                 "prog_g_identity": pi, "prog_fake_out": pfo, "prog_palette": ppal}
+
+    def _build_nce_all(self, pf: Program, hooks: dict, src_feat, wl: float):
+        """patchnce.nce_includes_all_negatives_from_minibatch: per layer gather -> [one exchange of every layer's source rows] -> forward, and
+        the backward hooks, on the gan_patchnce_all_* entry points.  One process: the keys of a layer are its workspace's own Sn.  Rank r
+        of W: the keys are all ranks' Sn in rank order (W segments), the positives sit in segment r, the mean is over the rank's own rows:
+        the rank-mean of the losses and sum / W of the gradients are then the one-process values at batch W B.  A one-rank group
+        (`force_allreduce`) exchanges nothing: its only segment is the workspace's own."""
+        cfg, ops, ctx, B, W = self.config, self.ops, self.ctx, self.B, self.world_size
+        T = cfg["patchnce"]["temperature"]
+        layers, parts, off = [], [], 0
+        for li, ids in zip(self.nce_layers, self.nce_ids):
+            src, tgt = src_feat(li), self.p2.acts[li]
+            P = ids.numel()
+            ws = ctx.f32(ops.patchnce_all_ws_floats(B, P, src.C))
+            pf.add(ops.patchnce_all_gather(src, tgt, ids, P, src.C, ws))
+            layers.append((li, tgt, ids, P, ws, off))
+            parts.append((ws, off, B * P * src.C))
+            off += B * P * src.C
+        me = 0
+        if W > 1:
+            import torch.distributed as dist
+            me = dist.get_rank(self.pg)
+            send, recv = ctx.f32(off), ctx.f32(W * off)
+            pf.add(lambda: self._nce_exchange(parts, send, recv))
+        for li, tgt, ids, P, ws, o in layers:
+            keys, segs, stride = (recv[o:], W, off) if W > 1 else (ws, 1, 0)
+            pf.add(ops.patchnce_all_fwd(tgt, P, tgt.C, T, wl, keys, segs, stride, me, self._slot("nce"), ws))
+
+            def mk(tgt=tgt, ids=ids, P=P, ws=ws, keys=keys, segs=segs, stride=stride, me=me):
+                def hook(gv: View):
+                    assert (gv.H, gv.W, gv.C) == (tgt.H, tgt.W, tgt.C)
+                    return [ops.patchnce_all_bwd(tgt, ids, P, tgt.C, T, wl, keys, segs, stride, me, gv, ws)]
+                return hook
+            hooks[li] = mk()
 
     def _build_updates(self):
         """R1 and the optimiser updates with their operand-copy refresh: built after every mode planned so far, because a

@@ -145,7 +145,7 @@ def cycle_loss(rec, real, lambda_cycle: float = 10.0):
 
 # ------------------------------------------------------------------------------------------------ PatchNCE (a8)
 class _NcePlan(_Plan):
-    def __init__(self, shape, device, P, temperature):
+    def __init__(self, shape, device, P, temperature, all_negatives=False):
         super().__init__(device)
         B, C, H, W = shape
         self.src = torch.zeros(shape, dtype=torch.float32, device=device)
@@ -160,26 +160,38 @@ class _NcePlan(_Plan):
         self.fwd.add(ops.nchw_to_view(self.src, C, vs, HALO_NONE))
         self.fwd.add(ops.nchw_to_view(self.tgt, C, vt, HALO_NONE))
         self.fwd.add(ops.fill(self.loss, 0.0))
-        self.fwd.add(ops.patchnce_fwd(vs, vt, self.ids, P, C, temperature, 1.0, self.loss, ws))
+        if all_negatives:                                    # one process: the keys are the workspace's own normalised source rows
+            self.fwd.add(ops.patchnce_all_gather(vs, vt, self.ids, P, C, ws))
+            self.fwd.add(ops.patchnce_all_fwd(vt, P, C, temperature, 1.0, ws, 1, 0, 0, self.loss, ws))
+        else:
+            self.fwd.add(ops.patchnce_fwd(vs, vt, self.ids, P, C, temperature, 1.0, self.loss, ws))
         self.fwd.add(ops.zero_(gv.t))                       # the backward kernel ADDS into the feature gradient
-        self.fwd.add(ops.patchnce_bwd(vt, self.ids, P, C, temperature, 1.0, gv, ws))
+        if all_negatives:
+            self.fwd.add(ops.patchnce_all_bwd(vt, self.ids, P, C, temperature, 1.0, ws, 1, 0, 0, gv, ws))
+        else:
+            self.fwd.add(ops.patchnce_bwd(vt, self.ids, P, C, temperature, 1.0, gv, ws))
         self.fwd.add(ops.view_to_nchw(gv, C, self.g))
 
 
 class PatchNCELoss(nn.Module):
     """patchnce_cut.py:7-110.  One patch-id draw per layer (`torch.randint(0, H*W, (num_patches,), device=...)`, :63) shared by
-    the batch and by source / target; the source features carry no gradient (compute_patchnce_loss detaches them)."""
+    the batch and by source / target; the source features carry no gradient (compute_patchnce_loss detaches them).
+    all_negatives (patchnce.nce_includes_all_negatives_from_minibatch; this project's statement, include/mi355x_gan.h): every target row is
+    scored against the source rows of the whole batch, not of its own image only."""
 
-    def __init__(self, temperature: float = 0.07, num_patches: int = 256, nce_layers: Sequence[int] = (0, 4, 8, 12, 16)):
+    def __init__(self, temperature: float = 0.07, num_patches: int = 256, nce_layers: Sequence[int] = (0, 4, 8, 12, 16), *,
+                 all_negatives: bool = False):
         super().__init__()
         self.temperature, self.num_patches, self.nce_layers = temperature, num_patches, list(nce_layers)
+        self.all_negatives = bool(all_negatives)
 
     def _compute_nce_loss(self, src_feat, tgt_feat, patch_ids: Optional[torch.Tensor] = None):
         B, C, H, W = tgt_feat.shape
         if patch_ids is None:
             patch_ids = torch.randint(0, H * W, (self.num_patches,), device=tgt_feat.device)
         from . import ops_library  # noqa: F401  (registers torch.ops.mi355x_gan.*)
-        loss, _ = torch.ops.mi355x_gan.patchnce_fwd(src_feat.detach(), tgt_feat, patch_ids.to(torch.int32), self.temperature)
+        op = torch.ops.mi355x_gan.patchnce_all_fwd if self.all_negatives else torch.ops.mi355x_gan.patchnce_fwd
+        loss, _ = op(src_feat.detach(), tgt_feat, patch_ids.to(torch.int32), self.temperature)
         return loss
 
     def forward(self, src_feats, tgt_feats, patch_ids: Optional[List[torch.Tensor]] = None):
@@ -189,9 +201,9 @@ class PatchNCELoss(nn.Module):
         return total / len(src_feats)
 
 
-def compute_patchnce_loss(generator, src_images, tgt_images, nce_layers, temperature=0.07, num_patches=256):
+def compute_patchnce_loss(generator, src_images, tgt_images, nce_layers, temperature=0.07, num_patches=256, *, all_negatives=False):
     """patchnce_cut.py:113-149."""
-    fn = PatchNCELoss(temperature, num_patches, nce_layers)
+    fn = PatchNCELoss(temperature, num_patches, nce_layers, all_negatives=all_negatives)
     with torch.no_grad():
         src_feats = generator.get_feature_layers(src_images, nce_layers)
     src_feats = [f.detach() for f in src_feats]

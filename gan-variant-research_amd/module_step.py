@@ -66,7 +66,8 @@ def train_step(step, photos, monets, generator, discriminator, opt_G, opt_D, ema
         nce_loss = torch.tensor(0.0, device=device)
         if lw["patchnce"] > 0:
             pn = config["patchnce"]
-            fn = PatchNCELoss(pn["temperature"], pn["num_patches"], pn["nce_layers"])
+            fn = PatchNCELoss(pn["temperature"], pn["num_patches"], pn["nce_layers"],
+                              all_negatives=bool(pn.get("nce_includes_all_negatives_from_minibatch", False)))
             with torch.no_grad():
                 src_feats = generator.get_feature_layers(photos, pn["nce_layers"])
             tgt_feats = generator.get_feature_layers(fake, pn["nce_layers"])

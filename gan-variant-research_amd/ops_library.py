@@ -136,6 +136,8 @@ _LIB.define("fused_clip_adam_ema_(Tensor(a!)[] params, Tensor[] grads, Tensor(b!
             "float weight_decay=0.0, bool decoupled=False) -> (Tensor, Tensor)")
 _LIB.define("patchnce_fwd(Tensor src_feat, Tensor tgt_feat, Tensor ids, float temperature) -> (Tensor, Tensor)")
 _LIB.define("patchnce_bwd(Tensor saved, Tensor grad_loss) -> Tensor")
+_LIB.define("patchnce_all_fwd(Tensor src_feat, Tensor tgt_feat, Tensor ids, float temperature) -> (Tensor, Tensor)")
+_LIB.define("patchnce_all_bwd(Tensor saved, Tensor grad_loss) -> Tensor")
 _LIB.define("diffaugment_fwd(Tensor x, Tensor params) -> Tensor")
 _LIB.define("diffaugment_bwd(Tensor gy, Tensor params) -> Tensor")
 _LIB.define("allreduce_bucket_(Tensor(a!) flat, str group) -> Tensor(a!)")
@@ -317,10 +319,11 @@ _LIB.impl("fused_clip_adam_ema_", _fused_adam, _IMPL)
 
 # ---- PatchNCE (patchnce_cut.py:42-110) and DiffAugment (diffaugment.py:94-106): value and input gradient come out of one pass each,
 #      so the forward op hands the gradient for a unit upstream gradient to its backward op as `saved`
-def _nce_fwd(src, tgt, ids, temperature):
+def _nce_fwd(src, tgt, ids, temperature, all_negatives=False):
     from . import losses as LS
     P = int(ids.numel())
-    p = cached_plan(LS._PLANS, ("nce", tuple(tgt.shape), tgt.device, P, float(temperature)), tgt.device, lambda: LS._NcePlan(tuple(tgt.shape), tgt.device, P, temperature))
+    key = ("nce_all" if all_negatives else "nce", tuple(tgt.shape), tgt.device, P, float(temperature))
+    p = cached_plan(LS._PLANS, key, tgt.device, lambda: LS._NcePlan(tuple(tgt.shape), tgt.device, P, temperature, all_negatives))
     p.src.copy_(src); p.tgt.copy_(tgt); p.ids.copy_(ids)
     p.fwd.run()
     return p.loss.clone().reshape(()), p.g.clone()
@@ -351,6 +354,8 @@ def _allreduce_bucket(flat, group):
 
 _LIB.impl("patchnce_fwd", lambda src, tgt, ids, temperature: _nce_fwd(_f(src), _f(tgt), ids.to(torch.int32), temperature), _IMPL)
 _LIB.impl("patchnce_bwd", lambda saved, g: saved * g, _IMPL)
+_LIB.impl("patchnce_all_fwd", lambda src, tgt, ids, temperature: _nce_fwd(_f(src), _f(tgt), ids.to(torch.int32), temperature, True), _IMPL)
+_LIB.impl("patchnce_all_bwd", lambda saved, g: saved * g, _IMPL)
 _LIB.impl("diffaugment_fwd", lambda x, prm: _aug_run(_f(x), prm, False), _IMPL)
 _LIB.impl("diffaugment_bwd", lambda gy, prm: _aug_run(_f(gy), prm, True), _IMPL)
 _LIB.impl("allreduce_bucket_", _allreduce_bucket, _IMPL)
@@ -451,6 +456,9 @@ def _aug_setup(ctx, inputs, output):
 
 
 torch.library.register_autograd("mi355x_gan::patchnce_fwd", _nce_backward, setup_context=_nce_setup)
+torch.library.register_autograd("mi355x_gan::patchnce_all_fwd",
+                                lambda ctx, g_loss, g_saved: (None, torch.ops.mi355x_gan.patchnce_all_bwd(ctx.saved_tensors[0], g_loss), None, None),
+                                setup_context=_nce_setup)
 # the prior is a constant for the gradient
 torch.library.register_autograd("mi355x_gan::palette_prior_fwd", lambda ctx, g_loss, g_saved: (torch.ops.mi355x_gan.palette_prior_bwd(ctx.saved_tensors[0], g_loss), None, None),
                                 setup_context=_nce_setup)

@@ -938,6 +938,24 @@ class HipOps:
         return self._call("gan_patchnce_bwd", self._v(tgt), self._p(ids), P, Cc, C.c_float(temperature), C.c_float(weight), self._v(gtgt),
                           self._p(ws), self._s())
 
+    # ---- PatchNCE with negatives from the whole minibatch (include/mi355x_gan.h): keys = fp32 tensor of `segs` segments of B*P rows of Cc
+    #      floats, `seg_stride` floats apart; single rank: keys = ws (its own Sn), 1, 0, 0
+    def patchnce_all_ws_floats(self, B, P, Cc) -> int:
+        return int(self.lib.gan_patchnce_all_ws_floats(B, P, Cc))
+
+    def patchnce_all_gather(self, src: View, tgt: View, ids, P, Cc, ws) -> Op:
+        return self._call("gan_patchnce_all_gather", self._v(src), self._v(tgt), self._p(ids), P, Cc, self._p(ws), self._s())
+
+    def patchnce_all_fwd(self, tgt: View, P, Cc, temperature, weight, keys, segs, seg_stride, self_seg, loss, ws) -> Op:
+        assert keys.dtype == torch.float32 and keys.numel() >= (segs - 1) * seg_stride + tgt.B * P * Cc
+        return self._call("gan_patchnce_all_fwd", self._v(tgt), P, Cc, C.c_float(temperature), C.c_float(weight), self._p(keys), int(segs),
+                          C.c_int64(seg_stride), int(self_seg), self._p(loss), self._p(ws), self._s())
+
+    def patchnce_all_bwd(self, tgt: View, ids, P, Cc, temperature, weight, keys, segs, seg_stride, self_seg, gtgt: View, ws) -> Op:
+        assert keys.dtype == torch.float32 and keys.numel() >= (segs - 1) * seg_stride + tgt.B * P * Cc
+        return self._call("gan_patchnce_all_bwd", self._v(tgt), self._p(ids), P, Cc, C.c_float(temperature), C.c_float(weight), self._p(keys),
+                          int(segs), C.c_int64(seg_stride), int(self_seg), self._v(gtgt), self._p(ws), self._s())
+
     # ---- optimiser
     def adam_step(self, table, ntensors, chunk_tensor, chunk_off, nchunks, lr, b1, b2, eps, max_norm, grad_scale, ema_decay, norm_out, ws,
                   lr_dev=None, inv_scale=None, skip_nonfinite=False) -> Op:

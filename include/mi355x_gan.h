@@ -841,6 +841,34 @@ int gan_patchnce_fwd(const gan_view* src, const gan_view* tgt, const int32_t* id
 int gan_patchnce_bwd(const gan_view* tgt, const int32_t* ids, int P, int C, float temperature, float weight,
                      const gan_view* gtgt, float* ws, void* stream);
 
+/* ---- PatchNCE with negatives from the whole minibatch (patchnce.nce_includes_all_negatives_from_minibatch; the reference holds only
+ *      the key, so the statement is this project's: the per-image statement above with the batch loop removed).
+ *      One call scores the Q = B*P normalised target rows (queries; row b*P + i) against K = segs*Q normalised source rows (keys): segment
+ *      s is keys + s*seg_stride, Q rows of C floats; segment `self` holds the keys of the call's own rows, and the positive of query i is
+ *      key self*Q + i.  Single rank: keys = ws (the workspace's own Sn), segs 1, seg_stride 0, self 0.  Data parallel, rank r of W: every
+ *      rank's Sn in rank order, segs = W, self = r.
+ *        raw_ij    = <Tn_i, Key_j> / T;   lg = clamp(raw, -50, 50)   (a NaN stays a NaN)
+ *        rowloss_i = logsumexp_j lg_ij - lg_{i, self*Q+i}
+ *        call      = mean_i rowloss_i;   flag = isfinite(call);   *loss += weight * (flag ? call : 0)
+ *        dlg_ij    = weight * flag * (softmax_ij - [j = self*Q+i]) / Q,   0 where raw is outside [-50, 50]
+ *        dTn = dlg . Key / T;   dX_i = (dTn_i - Tn_i <Tn_i, dTn_i>) / ||x_i||  where ||x_i|| > 1e-6, else dTn_i / 1e-6
+ *      With B = 1, segs = 1 this is gan_patchnce_fwd / bwd's statement.  One non-finite key row anywhere, or one non-finite target row,
+ *      makes the call's flag 0: nothing is added to the loss, every row of dX is exactly 0 and `gtgt` keeps its bits.
+ *      gan_patchnce_all_gather writes Sn, Tn, tnorm (and nothing else); gan_patchnce_all_fwd reads Tn and the keys and writes lse, rowloss
+ *      and all B entries of flag (each the call's flag); gan_patchnce_all_bwd reads Tn, tnorm, lse, flag and the keys, writes dX and ADDS
+ *      its rows into `gtgt` (duplicates in ids accumulate; channels >= C and halos are never written).  The keys are only read.
+ *      Workspace: gan_patchnce_all_ws_floats = gan_patchnce_ws_floats, the same layout in the same order (tests read it), rows indexed
+ *      b*P + i; no logit is ever stored and the kernels need no further scratch.  Q rows in tiles of 16, keys in trips of 256, channels
+ *      in chunks of 64 on v_mfma_f32_16x16x4_f32 where C % 64 == 0, C <= 256 and Q % 16 == 0; a scalar path takes every other shape
+ *      (1 <= P <= 256, 1 <= C <= 512 as above).  Fixed-order sums, no atomics: repeated calls repeat their bits.
+ *      Refused arguments (also: keys NULL, self outside 0..segs-1, segs > 1 with seg_stride < Q*C) return their error and write nothing. */
+int64_t gan_patchnce_all_ws_floats(int B, int P, int C);
+int gan_patchnce_all_gather(const gan_view* src, const gan_view* tgt, const int32_t* ids, int P, int C, float* ws, void* stream);
+int gan_patchnce_all_fwd(const gan_view* tgt, int P, int C, float temperature, float weight, const float* keys, int segs,
+                         int64_t seg_stride, int self, float* loss, float* ws, void* stream);
+int gan_patchnce_all_bwd(const gan_view* tgt, const int32_t* ids, int P, int C, float temperature, float weight, const float* keys,
+                         int segs, int64_t seg_stride, int self, const gan_view* gtgt, float* ws, void* stream);
+
 /* ---- fused clip_grad_norm_ + Adam + EMA (amp_utils.py:29-41, sched_optim.py:5-27, io_ckpt.py:23-29) over a
  *      tensor list.  The table is a device array of gan_adam_tensor; tensors with g == NULL are skipped. */
 typedef struct gan_adam_tensor {
