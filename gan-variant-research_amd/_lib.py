@@ -196,6 +196,8 @@ PROTOTYPES = {
     "gan_palette_prior_update": (C.c_int, [vp, f32, vp, vp, C.c_int, f32, vp]),
     "gan_palette_loss": (C.c_int, [vp, vp, C.c_int, f32, vp, vp, vp]),
     "gan_palette_bwd": (C.c_int, [PV, C.c_int, vp, vp, vp, f32, PV, C.c_int, vp]),
+    "gan_featmatch_ws_floats": (C.c_int64, [PV]),
+    "gan_featmatch": (C.c_int, [PV, PV, C.c_int, f32, vp, f32, C.c_int, PV, C.c_int, vp, vp]),
     "gan_patchnce_ws_floats": (C.c_int64, [C.c_int, C.c_int, C.c_int]),
     "gan_patchnce_fwd": (C.c_int, [PV, PV, vp, C.c_int, C.c_int, f32, f32, vp, vp, vp]),
     "gan_patchnce_bwd": (C.c_int, [PV, vp, C.c_int, C.c_int, f32, f32, PV, vp, vp]),

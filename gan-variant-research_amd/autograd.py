@@ -18,7 +18,7 @@ from typing import Callable, Dict, List, Optional, Sequence, Tuple
 import torch
 
 from . import _lib
-from ._lib import F32, BF16, HALO_NONE, HALO_ZERO
+from ._lib import ACT_LRELU, F32, BF16, HALO_NONE, HALO_ZERO
 from .nets import DiscriminatorFamilyNet, GeneratorNet, generator_keys
 from .runtime import Ctx, HipOps, Program, View, cpad
 
@@ -414,10 +414,39 @@ class _DiscBridge(_Bridge):
         s.gx = torch.zeros_like(s.xin)
         return s
 
-    def forward(self, x, keep: bool):
+    def _make_feat_slot(self, B, H, W):
+        """The slot of get_intermediate_features: the same forward, and as outputs every scale's LeakyReLU activations (acts[0 .. L-1],
+        real channels) instead of the logits."""
+        ops = self.ctx.ops
+        s = self._new_slot(B, H, W)
+        L = self.net.nconv - 1
+        s.feats = [(sc, j, dp.acts[j], net.chans[j + 1]) for sc, (dp, net) in enumerate(zip(s.dp.dps, s.net.nets)) for j in range(L)]
+        s.fwd = Program("D.features.fwd")
+        s.fwd.add(ops.nchw_to_view(s.xin, self.net.in_c, s.dp.x, HALO_ZERO))
+        s.fwd.add(s.dp.fwd_program())
+        s.outs = [torch.zeros(B, cr, a.H, a.W, dtype=torch.float32, device=self.device) for _, _, a, cr in s.feats]
+        s.fwd.add([ops.view_to_nchw(a, cr, out) for (_, _, a, cr), out in zip(s.feats, s.outs)])
+        s.g_outs = [torch.zeros_like(out) for out in s.outs]
+        s.gx = torch.zeros_like(s.xin)
+        return s
+
+    def _feat_hooks(self, s: _Slot) -> list:
+        """DFamilyPass.bwd_program hooks that add the incoming feature gradients: g_out (NCHW) -> a view, times LeakyReLU'(activation), added
+        to the gradient the input-gradient launch has just written (which sits in front of that LeakyReLU)."""
+        ops, ctx = self.ctx.ops, self.ctx
+        hooks = [dict() for _ in s.dp.dps]
+        for (sc, j, a, cr), g_out in zip(s.feats, s.g_outs):
+            t1, t2 = ctx.view(a.B, a.H, a.W, a.C, 0), ctx.view(a.B, a.H, a.W, a.C, 0)
+
+            def hook(gv, a=a, cr=cr, g_out=g_out, t1=t1, t2=t2):
+                return [ops.nchw_to_view(g_out, cr, t1, HALO_NONE), ops.act_bwd(a, ACT_LRELU, t1, False, None, t2), ops.fold_add(gv, t2, False, gv)]
+            hooks[sc][j] = hook
+        return hooks
+
+    def forward(self, x, keep: bool, feats: bool = False):
         B, C, H, W = x.shape
         assert C == self.net.in_c
-        s = self._lease((B, H, W), lambda: self._make_slot(B, H, W))
+        s = self._lease(("feats", B, H, W), lambda: self._make_feat_slot(B, H, W)) if feats else self._lease((B, H, W), lambda: self._make_slot(B, H, W))
         try:
             self._prepare_weights(s)
             s.xin.copy_(x)
@@ -437,8 +466,12 @@ class _DiscBridge(_Bridge):
         if prog is None:
             prog = Program("D.autograd.bwd")
             gls = s.dp.grad_logits_views()
-            prog.add([ops.nchw_to_view(g_out, 1, gl, HALO_ZERO) for g_out, gl in zip(s.g_outs, gls)])
-            prog.add(s.dp.bwd_program(gls, wgrad=need_w, accumulate=False, need_input_grad=need_x))
+            if getattr(s, "feats", None) is not None:        # the logits are no output of this node: their gradient is zero
+                prog.add([ops.zero_(gl.t) for gl in gls])
+                prog.add(s.dp.bwd_program(gls, wgrad=need_w, accumulate=False, need_input_grad=need_x, hooks=self._feat_hooks(s)))
+            else:
+                prog.add([ops.nchw_to_view(g_out, 1, gl, HALO_ZERO) for g_out, gl in zip(s.g_outs, gls)])
+                prog.add(s.dp.bwd_program(gls, wgrad=need_w, accumulate=False, need_input_grad=need_x))
             if need_x:
                 prog.add(ops.view_to_nchw(s.dp.g_input, self.net.in_c, s.gx))
             if need_w and self.sn:
@@ -474,6 +507,22 @@ class _DiscFn(torch.autograd.Function):
         need_w = any(ctx.needs_input_grad[3:])
         gx = b.backward(ctx.slot, [g.detach().float().contiguous() for g in gs], ctx.needs_input_grad[2], need_w)
         return (None, None, gx) + (b.param_grads(ctx.needs_input_grad[3:]) if need_w else (None,) * len(b.plist))
+
+
+class _DiscFeatFn(torch.autograd.Function):
+    """MultiscaleDiscriminator.get_intermediate_features: every feature of every scale from one node."""
+
+    @staticmethod
+    def forward(ctx, bridge: _DiscBridge, keep, x, *params):
+        slot, outs = bridge.forward(x.detach(), keep, feats=True)
+        ctx.bridge = bridge
+        if keep:
+            ctx.slot, ctx.lease = slot, _Lease(slot)
+            ctx.save_for_backward(x)
+            slot.node = weakref.ref(ctx)
+        return outs
+
+    backward = _DiscFn.backward
 
 
 # ------------------------------------------------------------------------------------------------ module-facing helpers
@@ -513,6 +562,14 @@ def discriminator_forward(module, x: torch.Tensor, style: str, prefix, ndf: int,
     keep = torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in b.plist))
     outs = _DiscFn.apply(b, keep, x.float().contiguous(), *b.plist)
     return outs[0] if isinstance(prefix, str) else list(outs)
+
+
+def discriminator_features(module, x: torch.Tensor, style: str, prefixes, ndf: int, n_layers: int) -> list:
+    """MultiscaleDiscriminator.get_intermediate_features (discriminator_patchgan.py:118-128) with autograd: the flat list, scale-major,
+    of every LeakyReLU output (B, C, h, w) fp32 from ONE autograd node, differentiable wrt x and the parameters."""
+    b = _bridge_of(module, lambda dev, dt: _DiscBridge(module, dev, dt, style, prefixes, ndf, n_layers))
+    keep = torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in b.plist))
+    return list(_DiscFeatFn.apply(b, keep, x.float().contiguous(), *b.plist))
 
 
 # ------------------------------------------------------------------------------------------------ R1 (double backward)

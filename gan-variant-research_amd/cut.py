@@ -19,7 +19,7 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from ._lib import ACT_NONE, BF16, F32, HALO_NONE, HALO_ZERO
+from ._lib import ACT_LRELU, ACT_NONE, BF16, F32, HALO_NONE, HALO_ZERO
 from .nets import DiscriminatorFamilyNet, GeneratorNet, SpectralNorm, fp8_switches
 from .runtime import AdamPlan, Ctx, HipOps, Program, View, check_palette_size, check_weight_decay, cpad
 
@@ -219,6 +219,15 @@ class MultiscaleDiscriminator(nn.Module):
         (AvgPool2d(3, 2, 1, count_include_pad=False), :100); differentiable, one autograd node (autograd.py)."""
         from . import autograd as AG
         return AG.discriminator_forward(self, x, "cut", [f"discriminators.{i}.model." for i in range(self.num_scales)], self.ndf, self.n_layers)
+
+    def get_intermediate_features(self, x):
+        """discriminator_patchgan.py:65-72, 118-128: per scale the list of every LeakyReLU output (n_layers + 1 tensors (B, C, h, w) fp32; the
+        logits are no feature), scale i on the input average-pooled i times; differentiable with respect to x and the parameters (spectral
+        norm included, with forward()'s power iteration in training mode), one autograd node (autograd.py)."""
+        from . import autograd as AG
+        flat = AG.discriminator_features(self, x, "cut", [f"discriminators.{i}.model." for i in range(self.num_scales)], self.ndf, self.n_layers)
+        L = self.n_layers + 1
+        return [flat[s * L:(s + 1) * L] for s in range(self.num_scales)]
 
 
 def build_models(config, device):
@@ -464,6 +473,12 @@ class CutTrainer:
         self.pal_T, self.pal_ema, self.pal_decay = int(pp.get("low_freq_size", 32)), bool(pp.get("use_ema", True)), float(pp.get("ema_decay", 0.99))
         if self.palette:
             check_palette_size(self.pal_T)
+        # Feature matching (csrc/featmatch.hip): active iff loss_weights.featmatch > 0.  fm = mean over scales and over the n_layers + 1
+        # LeakyReLU outputs of each of mean |F(aug(fake)) - F(aug(photos)).detach()|: the pair the D step calls fake and real, aligned row by
+        # row (fake = G(photos)), under the same DiffAugment draws and the same (updated) discriminator weights.  This project's formula:
+        # the reference keeps the key and get_intermediate_features, its losses/feat_matching.py is gone.
+        self.featmatch_w = float(lw.get("featmatch", 0) or 0)
+        self.featmatch = self.featmatch_w > 0
         self.policy = config["diffaugment"].get("policy", ["color", "translation", "cutout"]) if config["diffaugment"].get("enable", False) else None
         self.aug = DiffAugment(self.policy) if self.policy is not None else None
         self.generator, self.discriminator = generator, discriminator
@@ -520,12 +535,13 @@ class CutTrainer:
         self.d_rf = self.D.new_pass(B if self.sn is not None else 2 * B, S, S)
         self.d_fake = self.D.new_pass(B, S, S)
         self.d_r1 = self.D32.new_pass(B, S, S)
+        self.d_fm = self.D.new_pass(B, S, S) if self.featmatch else None      # forward only: the real branch's features
 
         f32 = self.ctx.f32
         self.both = torch.zeros(2 * B, 3, S, S, dtype=torch.float32, device=self.device)   # photos | monets, one staging tensor
         self.photos, self.monets = self.both[:B], self.both[B:]
         self.fake_out = torch.zeros_like(self.photos)
-        self.losses = f32(max(16, len(LOSS_SLOTS) + len(SCALE_SLOTS) * (K - 1) + (1 if self.palette else 0)))
+        self.losses = f32(max(16, len(LOSS_SLOTS) + len(SCALE_SLOTS) * (K - 1) + (1 if self.palette else 0) + (1 if self.featmatch else 0)))
         if self.palette:
             # statistics of the fake and the Monet batch (cells kept for the backward), the batch means, the prior and its update count
             n = B * self.pal_T * self.pal_T * 3
@@ -562,6 +578,38 @@ class CutTrainer:
     def _palette_slot_index(self) -> int:
         """The palette loss lives behind the per-scale slots: no other slot moves."""
         return len(LOSS_SLOTS) + len(SCALE_SLOTS) * (self.num_scales - 1)
+
+    def _featmatch_slot_index(self) -> int:
+        """Feature matching lives behind every other slot, the palette's included: no other slot moves."""
+        return self._palette_slot_index() + (1 if self.palette else 0)
+
+    def _build_featmatch(self, pa: Program, dp, photos_v: View) -> list:
+        """Queues the real branch on the discriminator's stream behind the fake pass's forward -- aug(photos) under the generator step's
+        draws, the scales only (the fake pass's power iteration and pack filled the operand copies: one power iteration per G step), the
+        slot's fill -- and returns the hooks of the fake pass's backward: one gan_featmatch per scale and feature layer, which adds the
+        layer's mean |f - r| / (K L) to the slot and w / (K L) times its gradient, through the LeakyReLU, into the gradient the backward
+        has just written.  Nothing flows into the real branch or into the discriminator's parameters (that backward has wgrad=False)."""
+        ops, dfm, K, L = self.opsD, self.d_fm, self.num_scales, self.D.nconv - 1
+        pa.add(self._aug_fwd(photos_v, dfm.x, self.prm["fake_g"]))
+        pa.add(dfm.fwd_program(spectral=False))
+        i = self._featmatch_slot_index()
+        slot = self.losses[i:i + 1]
+        pa.add(ops.fill(slot, 0.0))
+        hooks = []
+        for s in range(K):
+            per_layer = {}
+            for j in range(L):
+                f, r, Cr = dp.dps[s].acts[j], dfm.dps[s].acts[j], self.D.nets[s].chans[j + 1]
+                ws = self.ctxD.f32(ops.featmatch_ws_floats(f))
+
+                def mk(f=f, r=r, Cr=Cr, ws=ws):
+                    def hook(gv: View):
+                        assert (gv.B, gv.H, gv.W, gv.C) == (f.B, f.H, f.W, f.C)
+                        return [ops.featmatch(f, r, Cr, 1.0 / (K * L), slot, self.featmatch_w / (K * L), ACT_LRELU, gv, True, ws)]
+                    return hook
+                per_layer[j] = mk()
+            hooks.append(per_layer)
+        return hooks
 
     def _palette_allreduce(self):
         """Data parallel: the six batch means of the Monet statistics become their sum over the ranks (the prior update divides by the
@@ -700,10 +748,11 @@ class CutTrainer:
         dp = self.d_fake
         pa.add(self._aug_fwd(fake, dp.x, self.prm["fake_g"]))
         pa.add(dp.fwd_program())
+        fm_hooks = self._build_featmatch(pa, dp, photos_v) if self.featmatch else None
         gls = dp.grad_logits_views()
         for s, (lg, gl) in enumerate(zip(dp.logits, gls)):
             pa.add(self.opsD.patch_loss(lg, 2, 0.0, lw["adv"] / K, self._slot("g_adv", s), gl))
-        pa.add(dp.bwd_program(gls, wgrad=False, need_input_grad=True))
+        pa.add(dp.bwd_program(gls, wgrad=False, need_input_grad=True, hooks=fm_hooks))
         if self.aug is not None:
             g_adv_img = self.ctxD.view(B, S, S, 8, 0)
             pa.add(self.opsD.diffaug_bwd(dp.g_input, 3, self.prm["fake_g"], g_adv_img, self.ctxD.scratch("aug_ws", B + 16)))
@@ -1071,6 +1120,9 @@ class CutTrainer:
         if self.palette:                 # the key exists only when the term is active: every other configuration's dict is what it was
             out["palette"] = v[self._palette_slot_index()] / self.palette_w
             out["g_loss"] += self.palette_w * out["palette"]
+        if self.featmatch:               # likewise: the slot holds the unweighted term
+            out["featmatch"] = v[self._featmatch_slot_index()]
+            out["g_loss"] += self.featmatch_w * out["featmatch"]
         if any(not math.isfinite(x) for k, x in out.items() if k != "identity_weight"):
             raise ValueError(f"NaN loss detected at step {step}. Training stopped to prevent corruption.")   # train_cutpp.py:326-329
         return out

@@ -14,7 +14,7 @@ import torch
 import torch.nn as nn
 
 from . import autograd as AG
-from ._lib import F32, HALO_NONE, HALO_ZERO
+from ._lib import ACT_NONE, F32, HALO_NONE, HALO_ZERO
 from .cut import DiffAugment as _DiffAugmentSampler
 from .runtime import Program, cached_plan, cpad
 
@@ -141,6 +141,64 @@ def identity_loss(generator, monet_images):
 def cycle_loss(rec, real, lambda_cycle: float = 10.0):
     """Basic_GAN/src/losses.py:24-26."""
     return lambda_cycle * l1_loss(rec, real)
+
+
+# ------------------------------------------------------------------------------------------------ feature matching
+class _FeatmatchPlan(_Plan):
+    """gan_featmatch for one feature shape: mean |fake - real| and its gradient wrt fake (act = none), through NCHW staging tensors."""
+
+    def __init__(self, shape, device):
+        super().__init__(device)
+        B, C, H, W = shape
+        self.f = torch.zeros(shape, dtype=torch.float32, device=device)
+        self.r = torch.zeros(shape, dtype=torch.float32, device=device)
+        self.g = torch.zeros(shape, dtype=torch.float32, device=device)
+        self.loss = self.ctx.f32(1)
+        ops, ctx = self.ops, self.ctx
+        vf, vr, gv = ctx.view(B, H, W, cpad(C), 0), ctx.view(B, H, W, cpad(C), 0), ctx.view(B, H, W, cpad(C), 0)
+        self.prog = Program("featmatch")
+        self.prog.add(ops.nchw_to_view(self.f, C, vf, HALO_NONE))
+        self.prog.add(ops.nchw_to_view(self.r, C, vr, HALO_NONE))
+        self.prog.add(ops.fill(self.loss, 0.0))
+        self.prog.add(ops.featmatch(vf, vr, C, 1.0, self.loss, 1.0, ACT_NONE, gv, False, ctx.f32(ops.featmatch_ws_floats(vf))))
+        self.prog.add(ops.view_to_nchw(gv, C, self.g))
+
+
+class _FeatmatchFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, fake, real):
+        p = cached_plan(_PLANS, ("featmatch", tuple(fake.shape), fake.device), fake.device, lambda: _FeatmatchPlan(tuple(fake.shape), fake.device))
+        p.f.copy_(fake); p.r.copy_(real)
+        p.prog.run()
+        ctx.save_for_backward(p.g.clone())
+        return p.loss.clone().reshape(())
+
+    @staticmethod
+    def backward(ctx, g):
+        return ctx.saved_tensors[0] * g, None
+
+
+def _flat_feats(feats) -> list:
+    return [t for f in feats for t in (_flat_feats(f) if isinstance(f, (list, tuple)) else [f])]
+
+
+def feature_matching_loss(real_feats, fake_feats):
+    """The name the reference's trainer imported from losses/feat_matching.py (a file it no longer has; the formula is this project's,
+    DESIGN 3.11): over MultiscaleDiscriminator.get_intermediate_features' nested lists [scale][layer], or flat lists, of NCHW tensors,
+    mean over scales of mean over a scale's layers of mean |fake - real.detach()|.  Gradient with respect to fake_feats only."""
+    nested = bool(real_feats) and isinstance(real_feats[0], (list, tuple))
+    groups_r = [list(g) for g in real_feats] if nested else [list(real_feats)]
+    groups_f = [list(g) for g in fake_feats] if nested else [list(fake_feats)]
+    assert len(groups_r) == len(groups_f) and groups_r, "feature_matching_loss: the two feature lists differ in structure"
+    total = 0.0
+    for gr, gf in zip(groups_r, groups_f):
+        assert len(gr) == len(gf) and gr, "feature_matching_loss: the two feature lists differ in structure"
+        layer_sum = 0.0
+        for r, f in zip(gr, gf):
+            assert r.shape == f.shape and f.dim() == 4, "feature_matching_loss: features are (B, C, h, w) tensors of equal shape"
+            layer_sum = layer_sum + _FeatmatchFn.apply(f.float().contiguous(), r.detach().float().contiguous())
+        total = total + layer_sum / len(gr)
+    return total / len(groups_r)
 
 
 # ------------------------------------------------------------------------------------------------ PatchNCE (a8)

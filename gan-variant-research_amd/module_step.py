@@ -16,7 +16,7 @@ import torch
 
 from .cut import identity_weight_at
 from .autograd import r1_regularization
-from .losses import PalettePriorLoss, PatchNCELoss, discriminator_hinge_loss, generator_hinge_loss, identity_loss
+from .losses import PalettePriorLoss, PatchNCELoss, discriminator_hinge_loss, feature_matching_loss, generator_hinge_loss, identity_loss
 
 _PALETTE = {}      # id(generator) -> (generator, PalettePriorLoss): the prior of a run whose caller passes no module of its own
 
@@ -33,9 +33,12 @@ def palette_prior_for(generator, config) -> PalettePriorLoss:
 def train_step(step, photos, monets, generator, discriminator, opt_G, opt_D, ema_G, amp_ctx, diffaugment, config, device, rnd: Optional[dict] = None,
                palette_prior: Optional[PalettePriorLoss] = None):
     """palette_prior (optional, not in the reference's signature): the module that holds the palette prior when `loss_weights.palette` > 0
-    (default: one per generator, kept here).  The loss dict gains `palette` only then, as in cut.CutTrainer."""
+    (default: one per generator, kept here).  The loss dict gains `palette` only then, as in cut.CutTrainer.
+    loss_weights.featmatch > 0 adds cut.CutTrainer's feature-matching term: the discriminator's intermediate features of aug(fake) against
+    those of aug(photos), detached, under the generator step's DiffAugment draws; the dict gains `featmatch` only then."""
     lw = config["loss_weights"]
     palette_w = float(lw.get("palette", 0) or 0)
+    featmatch_w = float(lw.get("featmatch", 0) or 0)
     identity_weight = identity_weight_at(step, config)                                    # :224-228
     rnd = rnd or {}
 
@@ -62,7 +65,9 @@ def train_step(step, photos, monets, generator, discriminator, opt_G, opt_D, ema
     opt_G.zero_grad()
     with amp_ctx.autocast():
         fake = generator(photos)
-        g_adv_loss = generator_hinge_loss(discriminator(aug(fake, "aug_fake_g")))
+        fake_aug = aug(fake, "aug_fake_g")
+        fm_draws = None if diffaugment is None else diffaugment.last_draws      # the real branch is augmented with the SAME draws
+        g_adv_loss = generator_hinge_loss(discriminator(fake_aug))
         nce_loss = torch.tensor(0.0, device=device)
         if lw["patchnce"] > 0:
             pn = config["patchnce"]
@@ -80,6 +85,18 @@ def train_step(step, photos, monets, generator, discriminator, opt_G, opt_D, ema
             fn = palette_prior if palette_prior is not None else palette_prior_for(generator, config)
             palette_loss = fn(fake, monets)
             g_loss = g_loss + palette_w * palette_loss
+        if featmatch_w > 0:
+            # eval mode for both feature passes: with spectral norm the weights are those of discriminator(fake_aug) above, whose power
+            # iteration was this generator step's only one
+            was_training = discriminator.training
+            discriminator.eval()
+            try:
+                with torch.no_grad():
+                    real_feats = discriminator.get_intermediate_features(photos if diffaugment is None else diffaugment(photos, draws=fm_draws))
+                featmatch_loss = feature_matching_loss(real_feats, discriminator.get_intermediate_features(fake_aug))
+            finally:
+                discriminator.train(was_training)
+            g_loss = g_loss + featmatch_w * featmatch_loss
     amp_ctx.scale_backward(g_loss)
     amp_ctx.step_optimizer(opt_G, max_grad_norm=config.get("grad_clip_g", 10.0))
     if ema_G is not None:
@@ -88,6 +105,8 @@ def train_step(step, photos, monets, generator, discriminator, opt_G, opt_D, ema
               "r1": r1_loss.item(), "identity_weight": identity_weight}
     if palette_w > 0:
         losses["palette"] = palette_loss.item()
+    if featmatch_w > 0:
+        losses["featmatch"] = featmatch_loss.item()
     if any(not math.isfinite(v) for k, v in losses.items() if k != "identity_weight"):
         raise ValueError(f"NaN loss detected at step {step}. Training stopped to prevent corruption.")   # :325-329
     return losses

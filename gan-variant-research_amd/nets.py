@@ -535,11 +535,18 @@ class DPass:
         return self.net.gbuf("g_logits", self.B, lg.H, lg.W, lg.C, 2)
 
     def bwd_program(self, g_logits: View, wgrad: bool = True, accumulate: bool = False, need_input_grad: bool = False,
-                    keep: Optional[list] = None, write_only: Sequence[int] = ()) -> Program:
+                    keep: Optional[list] = None, write_only: Sequence[int] = (),
+                    hooks: Optional[Dict[int, Callable[[View], list]]] = None) -> Program:
         """Backward from dL/dlogits.  keep: if a list, the per-layer output gradients (delta_i) are appended to it and
         live in dedicated buffers (R1's second-order pass needs them).  write_only: indices of convolutions whose weight gradient is
-        written even when `accumulate` (spectral norm's dL/dW_sn scratch); their bias gradients still follow `accumulate`."""
+        written even when `accumulate` (spectral norm's dL/dW_sn scratch); their bias gradients still follow `accumulate`.
+        hooks[i](g_view) returns ops queued right after the launch that wrote g_view, the gradient of activation i BEFORE its LeakyReLU
+        (the input gradient with the mask fused), and before the next layer's weight or input gradient reads it: a loss on acts[i] adds
+        its gradient, times LeakyReLU'(acts[i]), there (feature matching) -- GPass.bwd_program's contract.  Style "cut" only."""
         net, ops, B = self.net, self.net.ctx.ops, self.B
+        hooks = hooks or {}
+        assert not hooks or net.style == "cut", "hooks sit behind a fused LeakyReLU mask: Basic_GAN's activations pass through InstanceNorm"
+        assert all(0 <= i < net.nconv - 1 for i in hooks), "hooks: the logits are no feature"
         prog = Program("D.bwd")
         dy = g_logits
         self.g_input = None
@@ -573,6 +580,8 @@ class DPass:
                 prog.add(conv.dgrad(dy, g_a))
                 nxt = net.gbuf(tag, B, a.H, a.W, a.C, halo)
                 prog.add(ops.in_bwd(self.raw[li - 1], self.stats[li - 1], ACT_LRELU, g_a, False, None, nxt, net.in_ws(B, a.C)))
+            if li - 1 in hooks:
+                prog.add(hooks[li - 1](nxt))
             dy = nxt
         return prog
 
@@ -676,12 +685,13 @@ class DFamilyPass:
         self.logits = [dp.logits for dp in self.dps]
         self.g_input = None
 
-    def fwd_program(self) -> Program:
+    def fwd_program(self, spectral: bool = True) -> Program:
         """With spectral norm: one power iteration over every normalised convolution, the pack of their operand copies with
-        scale = sigma, then the scales."""
+        scale = sigma, then the scales.  spectral=False: the pools and the scales only, on the operand copies the last pack filled (a second
+        forward through the same weights, e.g. the real branch of feature matching: one power iteration per step, not two)."""
         net, ops = self.net, self.net.ctx.ops
         prog = Program("D.family.fwd")
-        if net.sn is not None:
+        if net.sn is not None and spectral:
             prog.add(net.sn.fwd_op())
             prog.add(lambda: net._pack())
         for s, dp in enumerate(self.dps):
@@ -698,14 +708,18 @@ class DFamilyPass:
         ops = self.net.ctx.ops
         return [ops.avgpool_bwd(self.dps[i + 1].g_input, self.dps[i].g_input, True) for i in range(len(self.dps) - 2, -1, -1)]
 
-    def bwd_program(self, g_logits: Sequence[View], wgrad: bool = True, accumulate: bool = False, need_input_grad: bool = False) -> Program:
+    def bwd_program(self, g_logits: Sequence[View], wgrad: bool = True, accumulate: bool = False, need_input_grad: bool = False,
+                    hooks: Optional[Sequence[dict]] = None) -> Program:
         """Per-scale backward; input gradients summed down to scale 0 through the pools (self.g_input).  The normalised convolutions'
         weight gradients (dL/dW_sn) overwrite the scratch and one batched spectral-norm backward adds / writes dL/dweight_orig (it reads
-        the snapshots of this pass's own forward: run it before the next); biases and plain weights take theirs directly."""
+        the snapshots of this pass's own forward: run it before the next); biases and plain weights take theirs directly.
+        hooks: one dict per scale, DPass.bwd_program's."""
         sn = self.net.sn
         prog = Program("D.family.bwd")
-        for dp, gl, idx in zip(self.dps, g_logits, self.net.sn_layers):
-            prog.add(dp.bwd_program(gl, wgrad=wgrad, accumulate=accumulate, need_input_grad=need_input_grad, write_only=idx))
+        assert hooks is None or len(hooks) == len(self.dps)
+        for s, (dp, gl, idx) in enumerate(zip(self.dps, g_logits, self.net.sn_layers)):
+            prog.add(dp.bwd_program(gl, wgrad=wgrad, accumulate=accumulate, need_input_grad=need_input_grad, write_only=idx,
+                                    hooks=None if hooks is None else hooks[s]))
         if need_input_grad:
             prog.add(self._pool_input_grads())
             self.g_input = self.dps[0].g_input

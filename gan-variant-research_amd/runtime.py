@@ -927,6 +927,16 @@ class HipOps:
         return self._call("gan_palette_bwd", self._v(x), int(T), self._p(cells), self._p(stats), self._p(gstats), C.c_float(scale), self._v(gx),
                           int(bool(accumulate)), self._s())
 
+    # ---- feature matching (csrc/featmatch.hip): *loss += loss_scale * mean |f - r| over C real channels; g (accumulate: +=) its gradient
+    #      wrt f times grad_scale / loss_scale, through act' (f is a LeakyReLU output when g is the gradient in front of that LeakyReLU)
+    def featmatch_ws_floats(self, f: View) -> int:
+        return int(self.lib.gan_featmatch_ws_floats(self._v(f)))
+
+    def featmatch(self, f: View, r: View, Cr, loss_scale, loss, grad_scale, act, g: Optional[View], accumulate, ws) -> Op:
+        assert ws.dtype == torch.float32 and ws.numel() >= self.featmatch_ws_floats(f) and loss.dtype == torch.float32
+        return self._call("gan_featmatch", self._v(f), self._v(r), int(Cr), C.c_float(loss_scale), self._p(loss), C.c_float(grad_scale), int(act),
+                          self._v(g), int(bool(accumulate)), self._p(ws), self._s())
+
     def patchnce_ws_floats(self, B, P, Cc) -> int:
         return int(self.lib.gan_patchnce_ws_floats(B, P, Cc))
 

@@ -816,6 +816,36 @@ int gan_palette_loss(const float* stats, const float* prior, int B, float scale,
 int gan_palette_bwd(const gan_view* x, int T, const float* cells, const float* stats, const float* gstats, float scale,
                     const gan_view* gx, int accumulate, void* stream);
 
+/* ---- feature matching between two discriminator feature maps (csrc/featmatch.hip): the term behind loss_weights.featmatch, over what
+ *      MultiscaleDiscriminator.get_intermediate_features returns (GAN_Variant1/models/discriminator_patchgan.py:65-72, 118-128).  The
+ *      reference's file that made a loss of them (losses/feat_matching.py) is gone; the statement is this project's.
+ *      f (fake), r (real) and g share B, H, W and dtype (GAN_F32 or GAN_BF16); each has its own halo and its own C >= the C of the
+ *      call (the real channels).  With n = B*H*W*C, over the interior elements of channels [0, C):
+ *        *loss += (float)(S * ((double)loss_scale / (double)n)),   S = sum |f - r|      (one fp32 `+=` onto the slot, as gan_patchnce_fwd:
+ *                                                                                        one slot collects every layer after one fill)
+ *        g (accumulate: +=) v,   v = +m where f - r > 0, -m where f - r < 0, else 0 (sign(0) = 0; a NaN difference gives 0),
+ *                                m = act == GAN_ACT_LRELU and not f > 0 ? inv02 : inv   (gan_act_bwd's convention: factor 0.2 at f == 0)
+ *        in fp32, exactly:  inv = grad_scale / (float)n  (n converted to fp32, round to nearest; one division),  inv02 = 0.2f * inv  (one
+ *        product);  f - r is one fp32 subtraction of the stored values;  accumulate = 0: g = round_to_dtype(v);  accumulate = 1:
+ *        g = round_to_dtype((float)g + v), one fp32 addition.  Nothing else rounds: tests hold g to this bit for bit.
+ *      g may be NULL (loss only).  act: GAN_ACT_NONE or GAN_ACT_LRELU.  Halos and channels >= C of f and r have no effect on any result and
+ *      those of g keep their bits (g's zero halo is what the next input gradient relies on).  Mismatched geometry, another dtype or act,
+ *      C outside (0, min C of the views], B*H*W*ceil(C/N) >= 2^31 or a workspace that is not 8-byte aligned: error, nothing is launched.
+ *      Accumulation of S (N = 8 bf16 or 4 fp32 elements per 16-byte chunk): the chunks of the interior, items = B*H*W*ceil(C/N) in
+ *      (b, y, x, chunk) order, are dealt round-robin to nblocks * 256 lanes, nblocks = min(2048, ceil(items / 256)).  A lane adds |f - r| of
+ *      its chunks' real elements to ONE fp32 sum in that order: a chain of at most L = N * ceil(items / (256 nblocks)) terms.  Lanes are
+ *      added in fp64 (fixed tree) to one fp64 partial per block in ws (2 floats each: gan_featmatch_ws_floats(f) = 2 * nblocks at C = f->C,
+ *      enough for every C), and a one-block second launch adds the partials in fp64 in a fixed order.  No atomics: a repeated call repeats
+ *      its bits.  Error bound that follows: every term takes one rounding in its subtraction and every fp32 partial sum of non-negative
+ *      terms one more, so |S_computed - S| <= L * 2^-24 * S (first order; the fp64 stages add 2^-53 per step); the value added to the
+ *      slot is then rounded to fp32 once and the `+=` rounds once:
+ *        |*loss_after - (*loss_before + loss_scale S / n)| <= (L + 1) * 2^-24 * loss_scale S / n + 2^-24 * |*loss_after|.
+ *      Non-finite data, as gan_l1_loss: one NaN in a real, interior element of f or r makes *loss NaN; the gradient of that element is
+ *      unspecified, the gradients of the other elements are unaffected. */
+int64_t gan_featmatch_ws_floats(const gan_view* f);
+int gan_featmatch(const gan_view* f, const gan_view* r, int C, float loss_scale, float* loss, float grad_scale, int act,
+                  const gan_view* g, int accumulate, float* ws, void* stream);
+
 /* ---- PatchNCE (GAN_Variant1/losses/patchnce_cut.py:42-110) for one feature layer.
  *      ids: device int32 [P] positions in [0,H*W).  ws: fp32 workspace >= gan_patchnce_ws_floats(B,P,C).
  *      fwd: *loss += weight * mean_b CE.  bwd: grad rows of tgt (scaled by weight) are ADDED into `gtgt`
